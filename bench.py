@@ -13,13 +13,19 @@ optimizer sweep, all_to_all of the updated parameter slices; AMDKGE_DP_MERGE=all
 Contract: `python bench.py --gpus N --steps K --warmup W`.  For N>1 the driver launches it under torch.distributed.run (one
 rank per GPU); started WITHOUT a launcher (`python bench.py --gpus N`, WORLD_SIZE unset) the script launches its own N ranks
 the same way and fails loudly when the node has fewer than N GPUs (AMDKGE_BENCH_BACKEND=gloo: development, N ranks on the GPUs
-there are).  Rank 0 prints ONE JSON line.  The timed region contains nothing but the K calls of the step (no event records):
-it is repeated --reps times (each bracketed by barrier + synchronize, max over ranks) and `ms_per_step` / `value` are the
-MEDIAN repetition; the per-phase HIP events are recorded in a separate, untimed pass of the same steps.  Extra objects: `roofline` (the train-step kernel pair,
-HBM-bound, algorithmic bytes 2*(3+eta)*4K per positive; duration = HIP events on the launch
-stream around the pair, i.e. the sum of the two kernels' durations + one launch gap), `cpu_baseline`
-(oracle/ref_cpu.py, the op-for-op torch-CPU port, on a bounded sample) and `eval` (filtered
-ranks/s of evaluate() on the 20 438 synthetic test triples, N=1 only).
+there are).  Rank 0 prints ONE JSON line.  The timed region contains nothing but the K calls of the step (no event records),
+bracketed by barrier + synchronize (max over ranks).
+
+A plain run does only what the headline needs: set up, W warm-up steps, ONE timed region of exactly K steps, the line.
+`--full` adds everything else, as the default command did before it existed: the timed region repeated --reps times (default 5;
+`ms_per_step` / `value` are then the MEDIAN repetition), the per-phase HIP events of a separate, untimed pass of the same steps,
+`roofline` (the train-step kernel pair, HBM-bound, algorithmic bytes 2*(3+eta)*4K per positive; duration = HIP
+events on the launch stream around the pair, i.e. the sum of the two kernels' durations + one launch gap), `cpu_baseline`
+(oracle/ref_cpu.py, the op-for-op torch-CPU port, on a bounded sample), `eval` (filtered ranks/s of evaluate() on the 20 438
+synthetic test triples, N=1 only), the drop-in class's fit() / evaluate() and the other presets under `extra_configs`.
+
+`--dump-outputs DIR` writes, right after the timed steps, what a caller of the timed path holds after its last step (see
+dump_outputs) as DIR/<name>.npy.  The inputs depend on the arguments only (seeded graph, tables and negatives).
 """
 import argparse
 import json
@@ -75,14 +81,19 @@ def parse():
     ap.add_argument("--skew-mode", default="auto", choices=["auto", "none", "atomic", "hot"],
                     help="development: how the positives' own rows of hot entities are handled (auto = configure_for_data decides; none = all "
                          "staged; atomic = AMDKGE_TILED_POS_ATOMIC; hot = replica rows for the hot entities only)")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed K-step region; the median is reported (min / max beside it)")
-    ap.add_argument("--phase-steps", type=int, default=32, help="steps of the separate, untimed pass that records the per-phase HIP events")
-    ap.add_argument("--also", default=None, help="comma-separated presets run after the main one in the same process (N=1 only); their "
-                    "lines go under `extra_configs`.  Default: C3 (BASELINE.json's MFMA-path config) beside the default C2 run; 'none' = off")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: repeated timed regions, per-phase events, roofline, "
+                    "evaluation, drop-in calls, CPU baselines, the other presets (a plain run times ONE region of --steps steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the timed path's outputs after its last timed step as "
+                    "DIR/<name>.npy (fp32 / fp64, at most 64 MB in all)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step region; the median is reported (min / max beside "
+                    "it).  Default: 1, with --full 5")
+    ap.add_argument("--phase-steps", type=int, default=32, help="--full: steps of the separate, untimed pass that records the per-phase HIP events")
+    ap.add_argument("--also", default=None, help="--full: comma-separated presets run after the main one in the same process (N=1 only); their "
+                    "lines go under `extra_configs`.  Default: C1, C3, C4, C5 beside the default C2 run; 'none' = off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-eval", action="store_true")
-    ap.add_argument("--dropin", action="store_true", help="also time whole fit() / evaluate() calls of the drop-in class (always on for the C2 preset)")
-    ap.add_argument("--trained-eval", action="store_true", help="also time evaluate() on trained-like tables (always on for the C2 preset)")
+    ap.add_argument("--dropin", action="store_true", help="--full: also time whole fit() / evaluate() calls of the drop-in class (always on for the C2 preset)")
+    ap.add_argument("--trained-eval", action="store_true", help="--full: also time evaluate() on trained-like tables (always on for the C2 preset)")
     ap.add_argument("--cpu-steps", type=int, default=8)
     ap.add_argument("--parallelism", default=None, choices=["replicated", "sharded-local", "sharded-global", "columns"],
                     help="N>1: replicated tables + gradient merge (right for tables that fit one GPU), the "
@@ -101,9 +112,13 @@ def parse():
     if args.optimizer_mode is None:
         args.optimizer_mode = "dense"
     args.preset = args.config or ("C2" if all(getattr(args, k_) == v_ for k_, v_ in PRESETS["C2"].items()) else None)
-    if args.also is None:   # the driver's single command also reports C1, C3, C4 and one GPU's C5 shard (VERDICT r3 #8, r5 #3 / missing #3)
-        args.also = "C1,C3,C4,C5" if (args.preset == "C2" and args.gpus == 1 and args.popularity == "uniform" and not args.deterministic
-                                   and args.optimizer_mode == "dense") else "none"
+    if not args.full and ((args.also or "none") != "none" or args.dropin or args.trained_eval):
+        ap.error("--also, --dropin and --trained-eval are measurements beside the headline: they need --full")
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if args.also is None:   # the full run also reports C1, C3, C4 and one GPU's C5 shard (VERDICT r3 #8, r5 #3 / missing #3)
+        args.also = "C1,C3,C4,C5" if (args.full and args.preset == "C2" and args.gpus == 1 and args.popularity == "uniform"
+                                   and not args.deterministic and args.optimizer_mode == "dense") else "none"
     return args
 
 
@@ -117,6 +132,7 @@ def preset_args(base, name):
     a.config = a.preset = name
     a.optimizer_mode = PRESETS[name].get("optimizer_mode", "dense")
     a.also = "none"
+    a.dump_outputs = None   # the outputs written are the headline configuration's
     if name in ("C1", "C4") and base.preset != name:   # riding along in another config's line: the CPU legs (C4: a 123 k-row dense Adam on the host) are left out
         a.no_cpu_baseline = True
     if name == "C5" and base.preset != "C5":
@@ -401,6 +417,28 @@ def plant_fitted_triples(eng, data, model, k, noise_rel=0.5, seed=1):
     return np.stack([s_id, p_id, o_id], 1).astype(np.int32)
 
 
+DUMP_TABLE_BYTES = {"entity": 48 << 20, "relation": 8 << 20}   # --dump-outputs: under 64 MB in all, row ids included
+
+
+def dump_outputs(path, eng, n_rows, loss_mean):
+    """--dump-outputs: what a caller of the timed path (the step loop) holds after its last timed step -- both trained tables
+    in the dense [n, K] fp32 layout get_tables() returns (this rank's rows: its shard when the entity table is row-sharded, its
+    column slice when column-sharded) and the mean batch loss since the warm-up began (fp64, what fit() reports).  A table
+    larger than its share of the budget is written as a fixed, seeded sample of rows; <table>_rows.npy holds the row ids (fp64)."""
+    os.makedirs(path, exist_ok=True)
+    for name, table, n in (("entity", eng.ent, n_rows), ("relation", eng.rel, eng.n_rels)):
+        per_row = 4 * eng.K + 8
+        if n * per_row <= DUMP_TABLE_BYTES[name]:
+            ids = np.arange(n, dtype=np.int64)
+            rows = eng.unpack(table[:n])
+        else:
+            ids = np.sort(np.random.default_rng(0).choice(n, DUMP_TABLE_BYTES[name] // per_row, replace=False))
+            rows = eng.unpack(table.index_select(0, torch.as_tensor(ids, device=table.device)))
+        np.save(os.path.join(path, f"{name}_table.npy"), rows.cpu().numpy().astype(np.float32, copy=False))
+        np.save(os.path.join(path, f"{name}_table_rows.npy"), ids.astype(np.float64))
+    np.save(os.path.join(path, "mean_batch_loss.npy"), np.array([loss_mean], dtype=np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script under torch.distributed.run (what the
     driver's own command line does) and pass their output through.  One rank per GPU: a node with fewer than N GPUs is an
@@ -523,7 +561,7 @@ def main():
             import copy
 
             ca = copy.copy(args)
-            ca.parallelism, ca.cols_of, ca.no_eval, ca.no_cpu_baseline, ca.also = "columns", 8, True, True, "none"
+            ca.parallelism, ca.cols_of, ca.no_eval, ca.no_cpu_baseline, ca.also, ca.dump_outputs = "columns", 8, True, True, "none", None
             t_extra = time.perf_counter()
             try:
                 torch.cuda.empty_cache()
@@ -577,6 +615,7 @@ def run_config(args, ctx):
     rel0 = rng.uniform(-lim_r, lim_r, size=(R, Kf)).astype(np.float32)
     opt = optimizers.get("adam")
     opt.lazy = args.optimizer_mode == "lazy"
+    rows_held = N   # entity rows this rank's table holds (row-sharded: its shard)
 
     def fill_rows(eng, lo, hi):
         """rows [lo, hi) of the whole-table initial values into eng.ent[0 : hi - lo] (host draw for small tables, a seeded
@@ -611,6 +650,7 @@ def run_config(args, ctx):
         cap = ShardedStepLoop.rows_needed(args.batch, args.eta, negs, world, N, cap_factor=cap_factor)
         cap_default = ShardedStepLoop.rows_needed(args.batch, args.eta, negs, world, N)   # what the product sizes the lists at
         eng = KgeEngine(args.model, args.k, spec.n_local + cap, R, max_rel_size=R)
+        rows_held = spec.n_local
         fill_rows(eng, spec.lo, spec.hi)
         eng.pack(rel0, out=eng.rel)
         loop = ShardedStepLoop(eng, spec, args.eta, loss_functions.get(args.loss), opt, None, 0, dist, negatives=negs)
@@ -685,11 +725,13 @@ def run_config(args, ctx):
         rank_ms = [float(x) for x in rk.tolist()]
     dt = float(np.median(rep_s))
     loss_mean = loop.mean_batch_loss()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, rows_held, loss_mean)
 
-    # ---- untimed: the per-phase split, HIP events on the stream the kernels are launched on (torch's current stream) at
-    #      the phase boundaries of the same step (single GPU: the kernel pair IS the step -- one phase)
+    # ---- untimed (--full): the per-phase split, HIP events on the stream the kernels are launched on (torch's current stream)
+    #      at the phase boundaries of the same step (single GPU: the kernel pair IS the step -- one phase)
     phases = list(loop.PHASES) if (ctx.multi or sharded or cols) else ["kernels"]
-    n_ph = max(1, min(args.phase_steps, args.steps)) if args.steps else 0
+    n_ph = max(1, min(args.phase_steps, args.steps)) if (args.steps and args.full) else 0
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(loop.PHASES) + 1)] for _ in range(n_ph)]
     cur = {"i": None}
 
@@ -721,7 +763,7 @@ def run_config(args, ctx):
         # PMC traffic cannot be collected inside this process (rocprofv3 wraps the command): the figure below is REPLAYED from
         # the committed counter passes of the headline workload (scripts/profile_bench.sh) and labelled as such; null otherwise
         traffic, traffic_source = None, None
-        if not ctx.multi and not cols and args.preset == "C2" and args.popularity == "uniform" and not opt.lazy and not loop.deterministic:
+        if args.full and not ctx.multi and not cols and args.preset == "C2" and args.popularity == "uniform" and not opt.lazy and not loop.deterministic:
             for cand in ("r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "pmc_traffic.json"):
                 pmc = os.path.join(ROOT, "profiles", cand)
                 if os.path.exists(pmc):
@@ -791,7 +833,9 @@ def run_config(args, ctx):
                                  "single GPU: the pair also applies the optimizer (7*4K*(N+R) B/step dense), which is NOT counted "
                                  "in the algorithmic bytes; traffic = L2<->fabric bytes (PMC, Infinity-Cache hits included)"},
         }
-        if not ctx.multi and not args.no_eval and data["test"] is not None:
+        if not args.full:   # both come from the per-phase pass of --full
+            del out["phases_ms"], out["roofline"]
+        if args.full and not ctx.multi and not args.no_eval and data["test"] is not None:
             out["eval"] = eval_bench(eng, data, rank)
             if args.preset == "C2" or args.trained_eval:
                 # the same evaluation on TRAINED-LIKE tables (VERDICT r3 #10 iv): untrained tables are the kindest case for the
@@ -813,7 +857,7 @@ def run_config(args, ctx):
                     e2["how"] = "300 more steps of the same workload at lr 1e-2, evaluated on the first n_test TRAINING triples (filter = train + valid + test)"
                 out["eval_trained_like"] = {k_: e2[k_] for k_ in ("ranks_per_s", "ranks_per_s_incl_filter_build", "ms", "n_test", "screening", "exact_fp32_kernel_alone", "roofline", "mrr_untrained_tables", "how") if k_ in e2}
                 out["eval_trained_like"]["mrr"] = out["eval_trained_like"].pop("mrr_untrained_tables")
-        if (not ctx.multi and not cols and not args.no_eval and data["train"] is not None and not big and not opt.lazy and not loop.deterministic
+        if (args.full and not ctx.multi and not cols and not args.no_eval and data["train"] is not None and not big and not opt.lazy and not loop.deterministic
                 and (args.preset == "C2" or args.dropin)):
             try:
                 d_in = dropin_bench(args, data, dt / args.steps * 1e3, out.get("eval", {}).get("ms"))
@@ -822,7 +866,7 @@ def run_config(args, ctx):
                 out["fit_epoch_ms"], out["evaluate_call_ms"] = d_in["fit_epoch_ms"], d_in["evaluate_call_ms"]
             except Exception as exc:   # noqa: BLE001 -- reported, never costs the headline line
                 out["dropin"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not ctx.multi and not args.no_cpu_baseline and not big and data["train"] is not None and not opt.lazy:
+        if args.full and not ctx.multi and not args.no_cpu_baseline and not big and data["train"] is not None and not opt.lazy:
             out["cpu_baseline"] = cpu_baseline(args, data, ent0, rel0)
             if not args.no_eval and data["test"] is not None:
                 out["cpu_baseline"]["eval"] = cpu_eval_baseline(args, data, ent0, rel0)

@@ -8,7 +8,7 @@ flags=$1; shift
 tag=$(echo $flags | tr -c "A-Za-z0-9" "_")
 cd /tmp && export TMPDIR=/tmp
 for dbg in "$@"; do
-  AMDKGE_DEBUG=$dbg rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}d$dbg -o r -- python $ROOT/bench.py $flags --no-cpu-baseline --no-eval --steps 100 --warmup 10 > $O/${tag}d$dbg.json 2> $O/${tag}d$dbg.err
+  AMDKGE_DEBUG=$dbg rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}d$dbg -o r -- python $ROOT/bench.py --full $flags --no-cpu-baseline --no-eval --steps 100 --warmup 10 > $O/${tag}d$dbg.json 2> $O/${tag}d$dbg.err
   f=$(find $O/${tag}d$dbg -name "*kernel_stats.csv" | head -1); echo "== $flags dbg=$dbg"; python - "$f" <<PY
 import csv,sys
 for r in list(csv.DictReader(open(sys.argv[1])))[:3]: print("  ", r["Name"][:56], r["Calls"], round(float(r["AverageNs"])/1e3,1))

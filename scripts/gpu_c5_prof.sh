@@ -7,7 +7,7 @@ TAG=${1:-r03}; shift || true
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 O=$ROOT/gpurun_out/c5_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $ROOT/bench.py --config C5 --no-cpu-baseline --no-eval"
+B="python $ROOT/bench.py --full --config C5 --no-cpu-baseline --no-eval"
 for mode in lazy dense; do
   timeout 900 $B --optimizer-mode $mode --steps 6 --warmup 2 --reps 3 "$@" >> $O/bench.jsonl 2>> $O/bench.err
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$mode -o r -- $B --optimizer-mode $mode --steps 4 --warmup 1 --reps 1 --phase-steps 1 "$@" > /dev/null 2> $O/stats_$mode.err

@@ -3,7 +3,7 @@
 TAG=${1:-evt}; M=${2:-TransE}
 O=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
-cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_$M -o r -- python $GRAFT_REPO_ROOT/bench.py --model $M --no-cpu-baseline --trained-eval --also none --steps 20 --warmup 5 --reps 1 > $O/bench_$M.json 2> $O/err_$M.log
+R=$(cd "$(dirname "$0")/.." && pwd); cd "$TMPDIR" && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_$M -o r -- python $R/bench.py --full --model $M --no-cpu-baseline --trained-eval --also none --steps 20 --warmup 5 --reps 1 > $O/bench_$M.json 2> $O/err_$M.log
 f=$(find $O/trace_$M -name "*kernel_trace.csv" | head -1)
 [ -n "$f" ] && python3 - "$f" <<'PY'
 import csv, sys

@@ -3,7 +3,7 @@
 R=$PWD; export TMPDIR=/tmp; cd /tmp
 for m in DistMult TransE RotatE; do
   O=$R/gpurun_out/model_$m; rm -rf $O; mkdir -p $O
-  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o r -- python $R/bench.py --model $m --steps 140 --warmup 14 --reps 1 --phase-steps 1 --no-eval --no-cpu-baseline > $O/bench.json 2>/dev/null
+  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o r -- python $R/bench.py --full --model $m --steps 140 --warmup 14 --reps 1 --phase-steps 1 --no-eval --no-cpu-baseline > $O/bench.json 2>/dev/null
   python - <<PY
 import csv, glob, json
 f = glob.glob("$O/**/*kernel_stats.csv", recursive=True)[0]

@@ -5,8 +5,8 @@ TAG=$1; shift
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 O=$ROOT/gpurun_out/pmc_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $O/a -o r -- python $ROOT/bench.py --no-cpu-baseline --no-eval --steps 10 --warmup 2 "$@" > /dev/null 2> $O/a.err
-rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE SQ_INSTS_SMEM --output-format csv -d $O/b -o r -- python $ROOT/bench.py --no-cpu-baseline --no-eval --steps 10 --warmup 2 "$@" > /dev/null 2> $O/b.err
+rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $O/a -o r -- python $ROOT/bench.py --full --no-cpu-baseline --no-eval --steps 10 --warmup 2 "$@" > /dev/null 2> $O/a.err
+rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE SQ_INSTS_SMEM --output-format csv -d $O/b -o r -- python $ROOT/bench.py --full --no-cpu-baseline --no-eval --steps 10 --warmup 2 "$@" > /dev/null 2> $O/b.err
 python - <<PY
 import csv,glob,collections
 for sub in ("a","b"):

@@ -115,8 +115,8 @@ def main():
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     n = str(a.gpus)
-    common = ["--no-cpu-baseline", "--no-eval", "--also", "none", "--steps", str(a.steps), "--warmup", "5", "--reps", "3"]
-    c5 = ["--config", "C5", "--steps", "6", "--warmup", "2", "--reps", "2", "--no-cpu-baseline", "--no-eval", "--also", "none"]
+    common = ["--full", "--no-cpu-baseline", "--no-eval", "--also", "none", "--steps", str(a.steps), "--warmup", "5", "--reps", "3"]
+    c5 = ["--full", "--config", "C5", "--steps", "6", "--warmup", "2", "--reps", "2", "--no-cpu-baseline", "--no-eval", "--also", "none"]
     if not a.full_c5:
         c5 += ["--ents-per-gpu", "500000", "--batch", "16384"]
     py = sys.executable

@@ -42,7 +42,7 @@ def pmc(sub, counter):
 
 fetch, write = pmc("fetch", "FETCH_SIZE"), pmc("write", "WRITE_SIZE")
 out = {"command": "scripts/profile_bench.sh " + tag + " : rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE (separate passes), "
-                  "each over `python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-eval`",
+                  "each over `python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-eval --also none`",
        "correction": "MI355X_MICROARCH.md (HBM section): on gfx950 FETCH_SIZE reports half the bytes of 16 B/lane coalesced "
                      "reads -> doubled here; WRITE_SIZE used as reported (KB). Both count L2<->fabric traffic, Infinity-Cache "
                      "hits included, so for these cache-resident tables they bound HBM traffic from above.",
