@@ -49,7 +49,7 @@ class EarlyStopping:
                 eng = self.model._engine
                 eng.ent.copy_(self.best_weights[0])
                 eng.rel.copy_(self.best_weights[1])
-                self.model._full_ent = None
+                self.model._placement.tables_written()
                 if self.verbose:
                     print(f"Restoring model weights from the end of the best epoch: {self.best_epoch + 1}.")
 

@@ -47,9 +47,8 @@ def query_topn(model, top_n=10, head=None, relation=None, tail=None, ents_to_con
             raise ValueError("`rels_to_consider` must be a list or numpy array.")
         if not _known(ix, rels_to_consider, "r"):
             raise ValueError("Relations in `rels_to_consider` have not been seen by the model.")
-    eng = model._engine
+    eng, pl = model._engine, model._placement
     dev = eng.device
-    sp = getattr(model, "_spec", None)
     one = lambda v, t: int(ix.get_indexes(np.asarray([v]), t)[0])   # noqa: E731
 
     if relation is None:   # complete the relation: a handful of candidates, scored as ordinary triples
@@ -58,7 +57,7 @@ def query_topn(model, top_n=10, head=None, relation=None, tail=None, ents_to_con
         else:
             cand = np.asarray(ix.get_indexes(np.asarray(rels_to_consider), "r"), dtype=np.int32)
         tri = np.stack([np.full_like(cand, one(head, "e")), cand, np.full_like(cand, one(tail, "e"))], 1)
-        scores = model._score_dev(torch.as_tensor(tri).to(dev))
+        scores = pl.score(torch.as_tensor(tri).to(dev))
         n = min(int(top_n), len(cand))
         idx, val = eng.topk_rows(scores.view(1, -1), n)
         out = tri[idx[0].cpu().numpy().astype(np.int64)]
@@ -75,37 +74,9 @@ def query_topn(model, top_n=10, head=None, relation=None, tail=None, ents_to_con
     n_cand = model._n_ents if cand_ids is None else len(cand_ids)
     n = min(int(top_n), n_cand)
     # (top_n > 1024: engine.topk_rows sorts the whole score row on the device instead of the streaming selection)
-    if sp is None:
-        ids_dev = None if cand_ids is None else torch.as_tensor(cand_ids.astype(np.int32)).to(dev)
-        pos, val = eng.corruption_topk(torch.as_tensor(q).to(dev), side, n, ent_ids=ids_dev)
-        pos = pos[0].cpu().numpy().astype(np.int64)
-        ents = pos if cand_ids is None else cand_ids[pos]
-        val = val[0].cpu().numpy()
-    else:
-        # row-sharded table: every rank selects among ITS rows (the query's own rows are fetched behind the shard), the
-        # W partial lists (global ids, scores) are gathered and merged by a second selection
-        d = model._dist()
-        ql = model._localise(torch.as_tensor(q).to(dev))
-        if cand_ids is None:
-            loc, n_loc = None, sp.n_local
-        else:
-            loc = sp.local_subset(torch.as_tensor(cand_ids).to(dev))[0]
-            n_loc = int(loc.shape[0])
-        k_loc = n
-        gid = torch.full((1, k_loc), -1, dtype=torch.int32, device=dev)
-        gval = torch.full((1, k_loc), float("-inf"), dtype=torch.float32, device=dev)
-        if n_loc > 0:
-            kk = min(k_loc, n_loc)
-            pos, val = eng.corruption_topk(ql, side, kk, ent_ids=loc, ent_lo=0, ent_hi=n_loc)
-            rows = pos[0].to(torch.int64) if loc is None else loc[pos[0].to(torch.int64)].to(torch.int64)
-            gid[0, :kk] = (rows + sp.lo).to(torch.int32)
-            gval[0, :kk] = val[0]
-        parts_i = [torch.empty_like(gid) for _ in range(sp.world)]
-        parts_v = [torch.empty_like(gval) for _ in range(sp.world)]
-        d.all_gather(parts_i, gid)
-        d.all_gather(parts_v, gval)
-        ents, val = eng.topk_rows(torch.cat(parts_v, 1).contiguous(), n, payload=torch.cat(parts_i, 1).contiguous())
-        ents, val = ents[0].cpu().numpy().astype(np.int64), val[0].cpu().numpy()
+    ql = pl.localise(torch.as_tensor(q).to(dev))   # (row-sharded table: the query's own rows are fetched behind the shard)
+    ents, val = pl.select(lambda ids, hi, kk: eng.corruption_topk(ql, side, kk, ent_ids=ids, ent_hi=hi), cand_ids, 1, n)
+    ents, val = ents[0], val[0]
     rel_col = np.full(n, r_id, dtype=np.int64)
     fix_col = np.full(n, fixed, dtype=np.int64)
     out = np.stack([fix_col, rel_col, ents], 1) if tail is None else np.stack([ents, rel_col, fix_col], 1)
@@ -132,9 +103,8 @@ def find_nearest_neighbours(kge_model, entities, n_neighbors=10, entities_subset
         all_neighbors = None
     n_all = kge_model._n_ents if cand is None else len(cand)
     assert n_neighbors < n_all, "n_neighbors must be less than the number of entities being fit!"
-    eng = kge_model._engine
+    eng, pl = kge_model._engine, kge_model._placement
     dev = eng.device
-    sp = getattr(kge_model, "_spec", None)
     qid = np.asarray(ix.get_indexes(np.asarray(entities), "e"), dtype=np.int64)
     k = int(n_neighbors)
     if metric not in ("euclidean", "l2", "minkowski", "cosine") or k > 1024:
@@ -146,37 +116,9 @@ def find_nearest_neighbours(kge_model, entities, n_neighbors=10, entities_subset
         dist, idx = knn.kneighbors(kge_model.get_embeddings(np.asarray(entities)))
         return np.asarray(labels)[idx], dist
     met = "cosine" if metric == "cosine" else "euclidean"
-    if sp is None:
-        Q = eng.ent[torch.as_tensor(qid).to(dev)]
-        ids_dev = None if cand is None else torch.as_tensor(cand.astype(np.int32)).to(dev)
-        pos, dist = eng.nearest_rows(Q, k, met, ent_ids=ids_dev)
-        pos = pos.cpu().numpy().astype(np.int64)
-        ids = pos if cand is None else cand[pos]
-        dist = dist.cpu().numpy()
-    else:
-        d = kge_model._dist()
-        fake = np.stack([qid, np.zeros_like(qid), qid], 1).astype(np.int32)
-        ql = kge_model._localise(torch.as_tensor(fake).to(dev))          # query rows, fetched behind the shard where remote
-        Q = eng.ent[ql[:, 0].to(torch.int64)]
-        if cand is None:
-            loc, n_loc = None, sp.n_local
-        else:
-            loc = sp.local_subset(torch.as_tensor(cand).to(dev))[0]
-            n_loc = int(loc.shape[0])
-        nq = len(qid)
-        gid = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
-        gd = torch.full((nq, k), float("inf"), dtype=torch.float32, device=dev)
-        if n_loc > 0:
-            kk = min(k, n_loc)
-            pos, dl = eng.nearest_rows(Q, kk, met, ent_ids=loc, ent_lo=0, ent_hi=n_loc)
-            rows = pos.to(torch.int64) if loc is None else loc[pos.to(torch.int64)].to(torch.int64)
-            gid[:, :kk] = (rows + sp.lo).to(torch.int32)
-            gd[:, :kk] = dl
-        parts_i = [torch.empty_like(gid) for _ in range(sp.world)]
-        parts_d = [torch.empty_like(gd) for _ in range(sp.world)]
-        d.all_gather(parts_i, gid)
-        d.all_gather(parts_d, gd)
-        ids, dist = eng.topk_rows(torch.cat(parts_d, 1).contiguous(), k, largest=False, payload=torch.cat(parts_i, 1).contiguous())
-        ids, dist = ids.cpu().numpy().astype(np.int64), dist.cpu().numpy()
+    fake = np.stack([qid, np.zeros_like(qid), qid], 1).astype(np.int32)
+    ql = pl.localise(torch.as_tensor(fake).to(dev))          # query rows, fetched behind the shard where remote
+    Q = eng.ent[ql[:, 0].to(torch.int64)]
+    ids, dist = pl.select(lambda ids_, hi, kk: eng.nearest_rows(Q, kk, met, ent_ids=ids_, ent_hi=hi), cand, len(qid), k, largest=False)
     labels = ix.get_indexes(ids.reshape(-1), "e", "ind2raw").reshape(ids.shape)
     return labels, dist.astype(np.float32)

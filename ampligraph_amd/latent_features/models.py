@@ -18,7 +18,6 @@ from .. import _ffi
 from ..datasets.filters import FilterIndex
 from ..datasets.indexer import DataIndexer
 from ..evaluation.metrics import hits_at_n_score, mr_score, mrr_score
-from ..trainer import StepLoop
 from . import loss_functions, optimizers, regularizers
 from .initializers import RowSource, initialise, stream_cost
 
@@ -53,13 +52,6 @@ def _load_triples(x):
     return x
 
 
-class _NoDist:
-    """Stand-in that makes _dist() report a single rank (used while a rank evaluates its own share)."""
-
-    def get_world_size(self):
-        return 1
-
-
 class ScoringBasedEmbeddingModel:
     def __init__(self, eta, k, scoring_type="DistMult", seed=0, max_ent_size=None, max_rel_size=None):
         if scoring_type not in SCORING_LAYER_REGISTRY:
@@ -78,13 +70,17 @@ class ScoringBasedEmbeddingModel:
         self.use_focusE = False
         self.history = None
         self.stop_training = False
-        self._engine = None
+        self._placement = None       # ampligraph_amd/placement.py: where the tables live across the ranks
         self._loop = None
-        self._spec = None            # ShardSpec in row-sharded mode
         self._sharding = "replicated"
         self._sharded_negatives = "local"
+        self._deterministic = False
         self._dist_override = None   # tests: an object with the torch.distributed collective surface
-        self._full_ent = None        # row-sharded mode: cached gathered entity table
+
+    @property
+    def _engine(self):
+        """The engine predict / evaluate / checkpoints read (row-sharded: this rank's rows and the scratch rows behind them)."""
+        return None if self._placement is None else self._placement.engine
 
     # ------------------------------------------------------------------------------------ config (:56-98)
     @classmethod
@@ -121,7 +117,7 @@ class ScoringBasedEmbeddingModel:
         all-reduce of the partial scores per step -- ampligraph_amd/colsharded.py.  Memory and host cost of that mode: every rank
         keeps the WHOLE tables and their whole optimizer slots next to its slice -- predict / evaluate / save_weights / callbacks
         read them -- and they are refreshed from the slices through host numpy (all_gather + column merge) after each fit(),
-        before each validation pass and, when callbacks are given, before the callbacks of every epoch)."""
+        before each validation pass and, when any rank's fit() was given callbacks, on every rank before the callbacks of every epoch)."""
         optimizer_mode = kwargs.pop("optimizer_mode", "dense")
         if optimizer_mode not in ("dense", "lazy"):
             raise ValueError("optimizer_mode must be 'dense' (the reference's behaviour) or 'lazy' (touched rows only)")
@@ -164,9 +160,7 @@ class ScoringBasedEmbeddingModel:
     EVAL_CHUNK_SHARDED = 4096   # test triples per sharded evaluation / prediction pass (2 scratch rows each)
 
     def _build(self, n_ents, n_rels, batch_size=None, tables=None):
-        import torch
-
-        from ..engine import KgeEngine  # raises loudly without the HIP library / a GPU
+        from .. import placement
 
         self.max_ent_size, self.max_rel_size = int(n_ents), int(n_rels)
         self._n_ents, self._n_rels = int(n_ents), int(n_rels)
@@ -187,71 +181,10 @@ class ScoringBasedEmbeddingModel:
             ent, rel = tables
             ent_rows = ent if callable(ent) else (lambda lo, hi: ent[lo:hi])
         d = self._dist()
-        self._spec = None
-        lo, hi = 0, int(n_ents)
-        if self._sharding == "rows" and d is not None:
-            from ..sharded import ShardedStepLoop, ShardSpec
-
-            # same initial values as one GPU: rows [lo, hi) of the whole-table draw
-            sp = self._spec = ShardSpec(n_ents, d.get_world_size(), d.get_rank())
-            per_rank = -(-int(batch_size or 1000) // sp.world)
-            cap = max(ShardedStepLoop.rows_needed(per_rank, self.eta, self._sharded_negatives, sp.world, n_ents),
-                      2 * self.EVAL_CHUNK_SHARDED)
-            self._engine = KgeEngine(self.scoring_type, self.k, sp.n_local + cap, n_rels, max_rel_size=n_rels)
-            lo, hi = sp.lo, sp.hi
-        else:
-            self._engine = KgeEngine(self.scoring_type, self.k, n_ents, n_rels, max_rel_size=n_rels)
-        self._upload_rows(self._engine.ent, ent_rows, lo, hi)
-        self._engine.pack(rel, out=self._engine.rel)
-        self._full_ent = None
-        self._col_engine = None
-        if self._sharding == "columns" and d is not None:
-            from ..colsharded import check_columns
-
-            W = d.get_world_size()
-            check_columns(self.scoring_type, self.k, W, lambda kk: int(self._engine.lib.amdkge_padded_k(kk)))
-            # the slice this rank trains on; filled from the whole tables (and optimizer slots) when fit() starts
-            self._col_engine = KgeEngine(self.scoring_type, self.k // W, n_ents, n_rels, max_rel_size=n_rels, k_full=self.k)
-            self._cols_pull = True
-
-    def _upload_rows(self, dst, rows, lo, hi, chunk_elems=1 << 24):
-        """dst[0 : hi-lo] <- rows(lo, hi) (dense rows, packed into the engine's stored layout), in host chunks of
-        <= chunk_elems floats (C5 shards do not fit host RAM twice)."""
-        eng = self._engine
-        step = max(1, chunk_elems // eng.K)
-        for r0 in range(int(lo), int(hi), step):
-            r1 = min(int(hi), r0 + step)
-            blk = np.ascontiguousarray(rows(r0, r1), dtype=np.float32)
-            if blk.shape != (r1 - r0, eng.K):
-                raise ValueError(f"table rows have shape {blk.shape}, expected {(r1 - r0, eng.K)}")
-            eng.pack(blk, out=dst[r0 - lo:r1 - lo])
-
-    def _ensure_shard_capacity(self, batch_size):
-        """Row-sharded mode, continued training: the scratch rows behind the shard were sized for the first fit()'s
-        batch (or for the default batch by load_weights); a larger batch gets a larger engine, tables and optimizer
-        state carried over."""
-        if self._spec is None:
-            return
-        from ..engine import KgeEngine
-        from ..sharded import ShardedStepLoop
-
-        sp, old = self._spec, self._engine
-        per_rank = -(-int(batch_size) // sp.world)
-        need = max(ShardedStepLoop.rows_needed(per_rank, self.eta, self._sharded_negatives, sp.world, sp.n_ents),
-                   2 * self.EVAL_CHUNK_SHARDED)
-        if need <= int(old.ent.shape[0]) - sp.n_local:
-            return
-        new = KgeEngine(self.scoring_type, self.k, sp.n_local + need, self._n_rels, max_rel_size=self._n_rels)
-        new.ent[:sp.n_local].copy_(old.ent[:sp.n_local])
-        new.rel.copy_(old.rel)
-        old_slots = dict(getattr(old, "slots", {}))
-        self._engine = new
-        self._loop = self._make_loop() if self.is_compiled else None   # allocates fresh slots on the new engine
-        for name, t in old_slots.items():
-            if name in new.slots:
-                (new.slots[name][:sp.n_local] if name.endswith("_e") else new.slots[name]).copy_(
-                    t[:sp.n_local] if name.endswith("_e") else t)
-        self._full_ent = None
+        kind = placement.Replicated   # (what a single rank uses, whatever entity_sharding says)
+        if d is not None and self._sharding != "replicated":
+            kind = placement.Rows if self._sharding == "rows" else placement.Columns
+        self._placement = kind(self, d, n_ents, n_rels, ent_rows, rel, batch_size)
 
     def _dist(self):
         if self._dist_override is not None:
@@ -260,100 +193,8 @@ class ScoringBasedEmbeddingModel:
 
         return dist if (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1) else None
 
-    # ---- column-sharded training (entity_sharding="columns"): whole tables <-> this rank's slice ----
-    def _cols_pull_now(self):
-        """whole tables (+ optimizer slots) of self._engine -> this rank's column slice (local)."""
-        from ..colsharded import column_slice
-
-        d, col, eng = self._dist(), self._col_engine, self._engine
-        W, r = d.get_world_size(), d.get_rank()
-        ent, rel = eng.get_tables()
-        col.set_tables(column_slice(ent, self.scoring_type, self.k, W, r), column_slice(rel, self.scoring_type, self.k, W, r))
-        for name, t in getattr(col, "slots", {}).items():
-            if name in getattr(eng, "slots", {}):
-                col.pack(column_slice(eng.unpack(eng.slots[name]).cpu().numpy(), self.scoring_type, self.k, W, r), out=t)
-        self._cols_pull = False
-
-    def _cols_push(self):
-        """the ranks' column slices (+ optimizer slots) -> the whole tables every rank keeps (collective)."""
-        import torch
-
-        from ..colsharded import column_merge
-
-        if getattr(self, "_col_engine", None) is None:
-            return
-        d, col, eng = self._dist(), self._col_engine, self._engine
-        W = d.get_world_size()
-
-        def gathered(stored):
-            mine = col.unpack(stored).contiguous()
-            parts = [torch.empty_like(mine) for _ in range(W)]
-            d.all_gather(parts, mine)
-            return column_merge([p_.cpu().numpy() for p_ in parts], self.scoring_type)
-
-        eng.set_tables(gathered(col.ent), gathered(col.rel))
-        for name, t in getattr(col, "slots", {}).items():
-            if name in getattr(eng, "slots", {}):
-                eng.pack(gathered(t), out=eng.slots[name])
-        self._full_ent = None
-
     def _make_loop(self):
-        reg = self._regularizers[0]
-        if getattr(self, "_col_engine", None) is not None:
-            from ..colsharded import ColumnStepLoop
-
-            if getattr(self, "_deterministic", False):
-                raise ValueError("entity_sharding='columns': deterministic mode is not offered")
-            loop = ColumnStepLoop(self._col_engine, self.eta, self.loss, self.optimizer, reg, self.seed, self._dist())
-            loop.reg_rel = self._regularizers[1]
-            self._engine.prepare_training(self.optimizer.name)   # the whole tables' optimizer slots: what checkpoints hold
-            return loop
-        if self._spec is not None:
-            from ..sharded import ShardedStepLoop
-
-            loop = ShardedStepLoop(self._engine, self._spec, self.eta, self.loss, self.optimizer, reg, self.seed,
-                                   self._dist(), negatives=self._sharded_negatives)
-        else:
-            loop = StepLoop(self._engine, self.eta, self.loss, self.optimizer, reg, self.seed, self._dist())
-        loop.reg_rel = self._regularizers[1]   # the relation table's own regulariser (or None)
-        if getattr(self, "_deterministic", False):
-            loop.deterministic = True   # AMDKGE_TILED_DETERMINISTIC: bitwise reproducible tables (include/amdkge.h)
-        return loop
-
-    def _entity_table(self):
-        """(N, Ks) entity table in the engine's STORED layout as a device tensor (row-sharded mode: gathered once and
-        cached until the next fit); engine.unpack() gives dense rows."""
-        if self._spec is None:
-            return self._engine.ent
-        if self._full_ent is None:
-            import torch
-
-            sp, eng = self._spec, self._engine
-            mine = torch.zeros(sp.rows_per, eng.Ks, dtype=eng.ent.dtype, device=eng.ent.device)
-            mine[:sp.n_local] = eng.ent[:sp.n_local]
-            parts = [torch.empty_like(mine) for _ in range(sp.world)]
-            self._dist().all_gather(parts, mine)
-            self._full_ent = torch.cat(parts)[:sp.n_ents]
-        return self._full_ent
-
-    def _localise(self, Xd):
-        """Row-sharded mode: fetch the remote s/o rows of the int32 device triples Xd behind the shard and return
-        the triples re-indexed into the local index space."""
-        import torch
-
-        from ..sharded import RowExchange
-
-        sp, eng = self._spec, self._engine
-        x = Xd.to(torch.int64)
-        n = int(x.shape[0])
-        ids = torch.cat([x[:, 0], x[:, 2]])
-        remote = (ids < sp.lo) | (ids >= sp.hi)
-        rid, rinv = torch.unique(ids[remote], return_inverse=True)
-        ex = RowExchange(sp, self._dist(), rid)
-        ex.fetch(eng.ent, sp.n_local)
-        loc = ids - sp.lo
-        loc[remote] = sp.n_local + ex.slots()[rinv]
-        return torch.stack([loc[:n], x[:, 1], loc[n:]], 1).to(torch.int32).contiguous()
+        return self._placement.make_loop()
 
     # ------------------------------------------------------------------------------------ fit
     def fit(self, x=None, batch_size=1000, epochs=100, verbose=True, callbacks=None, validation_split=0.0,
@@ -397,19 +238,16 @@ class ScoringBasedEmbeddingModel:
             self._build(self.data_indexer.get_entities_count(), self.data_indexer.get_relations_count(), batch_size)
         else:  # continue training (initial_epoch > 0): same id map, same tables
             Xi = self.data_indexer.get_indexes(X[:, :3])
-            self._ensure_shard_capacity(batch_size)
+            self._placement.ensure_capacity(batch_size)
         eng = self._engine
         if self._loop is None:
             self._loop = self._make_loop()
         loop = self._loop
-        if getattr(self, "_col_engine", None) is not None:
-            if self.use_focusE:
-                raise ValueError("entity_sharding='columns': FocusE is not offered")
-            self._cols_pull_now()   # (a fresh model, a checkpoint just loaded, or the tables the previous fit() left)
+        cbs = list(callbacks or [])
+        self._placement.begin_fit(bool(cbs))
         # negatives are keyed by a step counter that continues where the optimizer's iteration count stands: a run resumed
         # from a checkpoint draws what the uninterrupted run would have drawn, and a second fit() draws fresh negatives
         rng_base = int(self.optimizer.iterations)
-        self._full_ent = None
         if hasattr(loop, "configure_for_data"):
             loop.configure_for_data(Xi, batch_size)
         train = torch.as_tensor(np.ascontiguousarray(Xi, dtype=np.int32)).to(eng.device)
@@ -422,7 +260,6 @@ class ScoringBasedEmbeddingModel:
         batch_size = int(batch_size)
         steps = (n + batch_size - 1) // batch_size
         self.history = History()
-        cbs = list(callbacks or [])
         for cb in cbs:
             if hasattr(cb, "set_model"):
                 cb.set_model(self)
@@ -431,8 +268,6 @@ class ScoringBasedEmbeddingModel:
         self.stop_training = False
         if isinstance(validation_entities_subset, str) and validation_entities_subset == "all":
             validation_entities_subset = None
-        # column-sharded training: are the whole tables (what evaluate / callbacks / checkpoints read) current with the slices?
-        cols_current = False
         for epoch in range(int(initial_epoch), int(epochs)):
             self.current_epoch = epoch
             loop.reset_loss()
@@ -457,14 +292,12 @@ class ScoringBasedEmbeddingModel:
                     loop.step(train[b0:b0 + batch_size], rng_base + (epoch - int(initial_epoch)) * steps + step, focus)
                 else:
                     loop.step(train[b0:b0 + batch_size], rng_base + (epoch - int(initial_epoch)) * steps + step)
-            cols_current = cols_current and steps <= first
             logs = {"loss": loop.mean_batch_loss()}
             validate = (epoch >= (validation_burn_in - 1) and validation_data is not None
                         and (epoch + 1) % int(validation_freq) == 0)
             if validate:
                 self.is_fitted = True
-                self._cols_push()   # (column-sharded training: refresh the whole tables the evaluation reads)
-                cols_current = True
+                self._placement.publish()
                 ranks = self.evaluate(validation_data, batch_size=validation_batch_size or batch_size,
                                       use_filter=validation_filter, dataset_type="valid",
                                       corrupt_side=validation_corrupt_side,
@@ -475,18 +308,15 @@ class ScoringBasedEmbeddingModel:
             self.history._log(epoch, logs)
             if verbose:
                 print(f"Epoch {epoch + 1}/{epochs} - " + " - ".join(f"{k}: {v:.4f}" for k, v in logs.items()))
-            if cbs and not cols_current:
-                # callbacks read AND write the whole tables (EarlyStopping snapshots them, and restores the best ones just before it
-                # stops the run): they must see this epoch's, and a push after them would overwrite what they restored
-                self._cols_push()
-                cols_current = True
+            # callbacks read AND write the tables (EarlyStopping snapshots them, and restores the best ones just before it stops
+            # the run): they see this epoch's, and nothing published after them overwrites what they restored
+            self._placement.before_callbacks()
             for cb in cbs:
                 if hasattr(cb, "on_epoch_end"):
                     cb.on_epoch_end(epoch, logs)
             if self.stop_training:
                 break
-        if not cols_current:
-            self._cols_push()
+        self._placement.publish()
         for cb in cbs:
             if hasattr(cb, "on_train_end"):
                 cb.on_train_end()
@@ -538,119 +368,28 @@ class ScoringBasedEmbeddingModel:
         Xi = self._index_test(x)
         if Xi.shape[0] == 0:
             return np.zeros(0, dtype=np.float32)
-        return self._score_dev(torch.as_tensor(Xi).to(self._engine.device)).cpu().numpy()
-
-    def _score_dev(self, Xd):
-        """Scores of the int32 device triples Xd (global ids) as a device tensor."""
-        import torch
-
-        if self._spec is None:
-            return self._engine.score(Xd)
-        outs = []   # row-sharded: every rank fetches the rows it lacks and scores all triples (replicated result)
-        for c0 in range(0, int(Xd.shape[0]), self.EVAL_CHUNK_SHARDED):
-            outs.append(self._engine.score(self._localise(Xd[c0:c0 + self.EVAL_CHUNK_SHARDED])))
-        return torch.cat(outs) if outs else torch.zeros(0, dtype=torch.float32, device=Xd.device)
+        return self._placement.score(torch.as_tensor(Xi).to(self._engine.device)).cpu().numpy()
 
     # ------------------------------------------------------------------------------------ evaluate
     def evaluate(self, x=None, batch_size=10, verbose=True, use_filter=False, corrupt_side="s,o",
                  entities_subset=None, ranking_strategy="worst", callbacks=None, dataset_type="test"):
         """:1516-1692: int32 ranks (n, 1|2), 1-based, reference tie/filter semantics.  `batch_size` (the reference's default, 10,
         :1519) only chunked the TF graph in the reference; results do not depend on it and it is ignored here."""
-        import torch
-
         assert corrupt_side in ["s", "o", "s,o", "s+o"], "Invalid value for corrupt_side"
         assert ranking_strategy in ["best", "middle", "worst"], "Invalid value for ranking_strategy"
         Xi = self._index_test(x)
-        eng = self._engine
         n = Xi.shape[0]
         sides = [sd for sd in ("s", "o") if sd in corrupt_side]
         if n == 0:
             return np.zeros((0, 1 if corrupt_side in ("s", "o", "s+o") else 2), dtype=np.int32)
-        if self._spec is not None:
-            return self._evaluate_sharded(Xi, sides, use_filter, corrupt_side, entities_subset, ranking_strategy)
-        d = self._dist()
-        if d is not None and n >= d.get_world_size():
-            # replicated tables, several ranks: every rank ranks its contiguous share of the test triples (all filters
-            # are built from the full data, so the ranks are those of the single-GPU run) and the shares are gathered
-            return self._evaluate_split_queries(d, x, Xi, use_filter, corrupt_side, entities_subset, ranking_strategy)
         # filters (graph_data_loader.py:184-190,652-653): True -> the evaluated data filters itself;
         # dict -> union of the given datasets, all indexed with the training id map
         fi = self._filter_index(use_filter, Xi)
-        dev = eng.device
-        ent_ids = subset_pos = None
-        if entities_subset is not None and len(entities_subset) > 0:
-            sub = np.asarray(self.data_indexer.get_indexes(np.asarray(entities_subset), "e"), dtype=np.int32)
-            pos = np.full(eng.n_ents, -1, dtype=np.int32)
-            pos[sub] = np.arange(sub.shape[0], dtype=np.int32)  # DenseHashTable.insert: last wins (:1639-1643)
-            ent_ids, subset_pos = torch.as_tensor(sub).to(dev), torch.as_tensor(pos).to(dev)
-        Xd = torch.as_tensor(Xi).to(dev)
-        ranks = torch.empty(n, len(sides), dtype=torch.int32, device=dev)
-        CH = 1 << 16
-        for c0 in range(0, n, CH):
-            xs = Xd[c0:c0 + CH]
-            jobs = []
-            for col, sd in enumerate(sides):
-                flt = fi.device_filter(eng, xs, sd) if fi is not None else None   # range lookup on the device
-                jobs.append((_ffi.SIDE_S if sd == "s" else _ffi.SIDE_O, flt, ranks[c0:c0 + CH, col], len(sides)))
-            eng.rank_sides(xs, jobs, ranking_strategy, ent_ids, subset_pos)   # the sides run beside each other
-        r = ranks.cpu().numpy()
-        if corrupt_side == "s+o":  # :1459-1463 sums the two 0-based sides, then +1 (:1684)
-            r = (r.sum(1, keepdims=True) - 1).astype(np.int32)
-        return r
-
-    def _evaluate_split_queries(self, d, x, Xi, use_filter, corrupt_side, entities_subset, ranking_strategy):
-        import torch
-
-        from ..trainer import shard_bounds
-
-        W, r = d.get_world_size(), d.get_rank()
-        n = Xi.shape[0]
-        lo, hi = shard_bounds(n, W, r)
-        flt = use_filter
-        if use_filter is True:   # "the evaluated data filters itself": keep filtering with the WHOLE evaluated set
-            flt = {"self": self.data_indexer.get_indexes(Xi, "t", "ind2raw")}
-        override, self._dist_override = self._dist_override, _NoDist()
-        try:
-            mine = self.evaluate(self.data_indexer.get_indexes(Xi[lo:hi], "t", "ind2raw"), use_filter=flt,
-                                 corrupt_side=corrupt_side, entities_subset=entities_subset,
-                                 ranking_strategy=ranking_strategy, verbose=False)
-        finally:
-            self._dist_override = override
-        cols = mine.shape[1]
-        width = -(-n // W)
-        buf = torch.zeros(width, cols, dtype=torch.int32, device=self._engine.device)
-        buf[:hi - lo] = torch.as_tensor(mine).to(buf.device)
-        parts = [torch.empty_like(buf) for _ in range(W)]
-        d.all_gather(parts, buf)
-        out = [parts[q][:shard_bounds(n, W, q)[1] - shard_bounds(n, W, q)[0]] for q in range(W)]
-        return torch.cat(out).cpu().numpy()
-
-    def _evaluate_sharded(self, Xi, sides, use_filter, corrupt_side, entities_subset, ranking_strategy):
-        """Row-sharded evaluate(): every rank counts against ITS rows, counts are summed over ranks
-        (the reference's loop over entity partitions, :1431-1452, across GPUs); identical result on every rank."""
-        import torch
-
-        from ..sharded import sharded_rank_counts
-
-        eng, d = self._engine, self._dist()
         subset = None
         if entities_subset is not None and len(entities_subset) > 0:
-            sub = np.asarray(self.data_indexer.get_indexes(np.asarray(entities_subset), "e"), dtype=np.int64)
-            subset = self._spec.local_subset(torch.as_tensor(sub).to(eng.device))
-        fi = self._filter_index(use_filter, Xi)
-        dev = eng.device
-        n = Xi.shape[0]
-        ranks = torch.empty(n, len(sides), dtype=torch.int32, device=dev)
-        CH = self.EVAL_CHUNK_SHARDED
-        Xd = torch.as_tensor(Xi).to(dev)
-        for c0 in range(0, n, CH):
-            for col, sd in enumerate(sides):
-                flt = fi.device_filter(eng, Xd[c0:c0 + CH], sd) if fi is not None else None
-                counts, sub = sharded_rank_counts(eng, self._spec, d, Xd[c0:c0 + CH],
-                                                  _ffi.SIDE_S if sd == "s" else _ffi.SIDE_O, flt, subset)
-                eng.compose_ranks(counts, sub, ranking_strategy, out=ranks[c0:c0 + CH, col], out_stride=len(sides))
-        r = ranks.cpu().numpy()
-        if corrupt_side == "s+o":
+            subset = np.asarray(self.data_indexer.get_indexes(np.asarray(entities_subset), "e"))
+        r = self._placement.rank(Xi, sides, fi, subset, ranking_strategy).cpu().numpy()
+        if corrupt_side == "s+o":  # :1459-1463 sums the two 0-based sides, then +1 (:1684)
             r = (r.sum(1, keepdims=True) - 1).astype(np.int32)
         return r
 
@@ -681,7 +420,7 @@ class ScoringBasedEmbeddingModel:
         idx = np.asarray(self.data_indexer.get_indexes(np.asarray(entities), embedding_type), dtype=np.int64)
         import torch
 
-        tab = self._entity_table() if embedding_type == "e" else self._engine.rel
+        tab = self._placement.entity_table() if embedding_type == "e" else self._engine.rel
         return self._engine.unpack(tab[torch.as_tensor(idx).to(tab.device)]).cpu().numpy()
 
     # ------------------------------------------------------------------------------------ calibration
@@ -723,9 +462,9 @@ class ScoringBasedEmbeddingModel:
         weight_neg = (1.0 - positive_base_rate) / positive_base_rate
         dev = eng.device
         Xpd = torch.as_tensor(Xp).to(dev)
-        # row-sharded tables: the same code, scores come from _score_dev (replicated result on every rank)
-        sp_all = self._score_dev(Xpd) if pos_size else None    # the embeddings are frozen: score once
-        sn_all = self._score_dev(torch.as_tensor(Xn).to(dev)) if Xn is not None and neg_size else None
+        # row-sharded tables: the same code, the placement's scores are the same on every rank
+        sp_all = self._placement.score(Xpd) if pos_size else None    # the embeddings are frozen: score once
+        sn_all = self._placement.score(torch.as_tensor(Xn).to(dev)) if Xn is not None and neg_size else None
         slots = [(0.0, 0.0), (0.0, 0.0)]
         t = 0
         for epoch in range(int(epochs)):
@@ -736,7 +475,7 @@ class ScoringBasedEmbeddingModel:
                 else:
                     neg = eng.sample_corruptions(Xpd[bi * batch_size:(bi + 1) * batch_size], 1, self.seed, t,
                                                  sample_range=self._n_ents)
-                    sn = self._score_dev(neg)
+                    sn = self._placement.score(neg)
                 if sp.shape[0] == 0:
                     continue
                 t += 1
@@ -766,70 +505,40 @@ class ScoringBasedEmbeddingModel:
         return (1.0 / (1.0 + np.exp((w * s + b).astype(np.float64)))).astype(np.float32)
 
     # ------------------------------------------------------------------------------------ persistence
-    @staticmethod
-    def _shard_file(filepath, rank, world):
-        return "{}.shard{:03d}-of-{:03d}.npz".format(filepath, rank, world)
-
     def save_weights(self, filepath):
         """Own flat format (the reference writes a TF checkpoint, :1046-1071): <filepath>.npz holds tables,
-        optimizer slots and id maps; <filepath>.json the hyper-parameters.
+        optimizer slots and id maps; <filepath>.json the hyper-parameters.  Collective under torch.distributed: call on
+        every rank; rank 0 writes these files.
 
-        Row-sharded mode (collective: call on every rank): rank r writes ITS rows of the entity table and of the
-        optimizer slots to <filepath>.shardRRR-of-WWW.npz; rank 0 writes the replicated part (relation table + slots,
-        id maps, `shard_world`) to <filepath>.npz and the .json.  Nothing is gathered, so it works at C5 scale;
-        load_weights() re-slices, so a checkpoint can be resumed on a different number of GPUs (or on one)."""
+        Row-sharded mode: rank r also writes ITS rows of the entity table and of the optimizer slots to
+        <filepath>.shardRRR-of-WWW.npz, and <filepath>.npz holds the replicated part (relation table + slots, id maps,
+        `shard_world`).  Nothing is gathered, so it works at C5 scale; load_weights() re-slices, so a checkpoint can be resumed
+        on a different number of GPUs (or on one)."""
         assert self.is_fitted, "Model is not fit on the data yet!"
-        eng = self._engine
-        arrays = {}
-        if self._spec is not None:
-            sp = self._spec
-            dense = lambda t: eng.unpack(t).cpu().numpy()   # noqa: E731  checkpoints hold dense rows, whatever the engine stores
-            mine = {"ent": dense(eng.ent[:sp.n_local]), "lo": np.int64(sp.lo), "hi": np.int64(sp.hi)}
-            for kname, t in getattr(eng, "slots", {}).items():
-                if kname.endswith("_e"):
-                    mine["slot_" + kname] = dense(t[:sp.n_local])
-            np.savez(self._shard_file(filepath, sp.rank, sp.world), **mine)
-            arrays = {"rel": dense(eng.rel), "shard_world": np.int64(sp.world), "n_ents": np.int64(sp.n_ents)}
-            for kname, t in getattr(eng, "slots", {}).items():
-                if kname.endswith("_r"):
-                    arrays["slot_" + kname] = dense(t)
-            self._dist().barrier()
-            if sp.rank != 0:
-                return
-        else:
-            if self._loop is not None and hasattr(self._loop, "sync_optimizer_slots"):
-                self._loop.sync_optimizer_slots()   # data-parallel sharded merge: collective, call on every rank
-            d = self._dist()
-            if d is not None and d.get_rank() != 0:
-                d.barrier()   # replicated tables: every rank holds the same bytes, rank 0 writes them (barrier: file complete)
-                return
-            ent, rel = eng.get_tables()
-            arrays = {"ent": ent, "rel": rel}
-            for kname, t in getattr(eng, "slots", {}).items():
-                arrays["slot_" + kname] = eng.unpack(t).cpu().numpy()
-        st = self.data_indexer.state()
-        arrays["ent_raw"], arrays["rel_raw"] = st["ent_raw"], st["rel_raw"]
-        # written under a temporary name and renamed: a reader never sees a torn archive
-        with open(filepath + ".npz.tmp", "wb") as f:
-            np.savez(f, **arrays)
-        os.replace(filepath + ".npz.tmp", filepath + ".npz")
-        meta = {"eta": self.eta, "k": self.k, "scoring_type": self.scoring_type, "seed": self.seed,
-                "optimizer": self.optimizer.get_config() if self.is_compiled else None,
-                "iterations": self.optimizer.iterations if self.is_compiled else 0,
-                "loss": {"name": self.loss.name, "params": self.loss._loss_parameters} if self.is_compiled else None,
-                "calibration": self.calibration_parameters if self.is_calibrated else None,
-                "regularizer": ([None if r is None else {"p": r.p, "lambda": r.lam, "p2": r.p2, "lambda2": r.lam2} for r in self._regularizers]
-                                if self.is_compiled else None)}
-        with open(filepath + ".json.tmp", "w") as f:
-            json.dump(meta, f)
-        os.replace(filepath + ".json.tmp", filepath + ".json")
-        if self._spec is None and self._dist() is not None:
-            self._dist().barrier()
+        arrays = self._placement.save(filepath, self._loop)
+        if arrays is not None:   # (the writing rank)
+            st = self.data_indexer.state()
+            arrays["ent_raw"], arrays["rel_raw"] = st["ent_raw"], st["rel_raw"]
+            # written under a temporary name and renamed: a reader never sees a torn archive
+            with open(filepath + ".npz.tmp", "wb") as f:
+                np.savez(f, **arrays)
+            os.replace(filepath + ".npz.tmp", filepath + ".npz")
+            meta = {"eta": self.eta, "k": self.k, "scoring_type": self.scoring_type, "seed": self.seed,
+                    "optimizer": self.optimizer.get_config() if self.is_compiled else None,
+                    "iterations": self.optimizer.iterations if self.is_compiled else 0,
+                    "loss": {"name": self.loss.name, "params": self.loss._loss_parameters} if self.is_compiled else None,
+                    "calibration": self.calibration_parameters if self.is_calibrated else None,
+                    "regularizer": ([None if r is None else {"p": r.p, "lambda": r.lam, "p2": r.p2, "lambda2": r.lam2} for r in self._regularizers]
+                                    if self.is_compiled else None)}
+            with open(filepath + ".json.tmp", "w") as f:
+                json.dump(meta, f)
+            os.replace(filepath + ".json.tmp", filepath + ".json")
+        if self._placement.dist is not None:
+            self._placement.dist.barrier()   # every rank returns once the files are complete
 
     def load_weights(self, filepath):
         """Whole-table or row-sharded checkpoint -> this model, whatever its own sharding (rows are re-sliced)."""
-        import torch
-
+        from ..placement import shard_file
         from ..sharded import ShardSpec
 
         z = np.load(filepath + ".npz", allow_pickle=False)
@@ -853,7 +562,7 @@ class ScoringBasedEmbeddingModel:
                         continue
                     if r not in shards:
                         shards.clear()   # one shard file in memory at a time
-                        shards[r] = np.load(self._shard_file(filepath, r, saved_world), allow_pickle=False)[key]
+                        shards[r] = np.load(shard_file(filepath, r, saved_world), allow_pickle=False)[key]
                     out.append(shards[r][max(lo, s.lo) - s.lo:min(hi, s.hi) - s.lo])
                 return np.concatenate(out) if out else np.zeros((0, self.internal_k), np.float32)
             return rows
@@ -861,17 +570,16 @@ class ScoringBasedEmbeddingModel:
         self._build(n_ents, z["rel"].shape[0], tables=(rows_of("ent"), z["rel"]))
         slot_keys = [k[5:] for k in z.files if k.startswith("slot_")]
         if saved_world:
-            s0 = np.load(self._shard_file(filepath, 0, saved_world), allow_pickle=False)
+            s0 = np.load(shard_file(filepath, 0, saved_world), allow_pickle=False)
             slot_keys += [k[5:] for k in s0.files if k.startswith("slot_")]
         if slot_keys and self.is_compiled:
             self._loop = self._make_loop()
             eng = self._engine
-            lo, hi = (self._spec.lo, self._spec.hi) if self._spec is not None else (0, n_ents)
             for kname in slot_keys:
                 if kname not in eng.slots:
                     continue   # checkpoint of another optimizer
-                if kname.endswith("_e"):
-                    self._upload_rows(eng.slots[kname], rows_of("slot_" + kname), lo, hi)
+                if kname.endswith("_e"):   # (this rank's rows of them)
+                    self._placement.upload_rows(eng.slots[kname], rows_of("slot_" + kname))
                 else:
                     eng.pack(z["slot_" + kname], out=eng.slots[kname])
             if os.path.exists(filepath + ".json"):

@@ -199,6 +199,7 @@ def test_drop_in_class_column_sharded_fit_equals_single_gpu(gpu_lib, tmp_path):
     from threaded_dist import ThreadedWorld
 
     from ampligraph_amd.latent_features import ScoringBasedEmbeddingModel, optimizers
+    from ampligraph_amd.placement import Columns
 
     X = toy_graph(n=900, N=70, R=4)
     Xt = X[:80]
@@ -213,7 +214,7 @@ def test_drop_in_class_column_sharded_fit_equals_single_gpu(gpu_lib, tmp_path):
     def body(dist):
         m = new(dist, entity_sharding="columns")
         h = m.fit(X, batch_size=256, epochs=2, verbose=False, validation_data=Xt, validation_freq=1, validation_filter={"train": X})
-        assert m._col_engine is not None and m._loop.world == 2
+        assert isinstance(m._placement, Columns) and m._loop.world == 2
         m.save_weights(ck)
         h2 = m.fit(X, batch_size=256, epochs=4, initial_epoch=2, verbose=False)
         ents = np.array([f"e{i}" for i in range(70)])
@@ -287,3 +288,46 @@ def test_column_sharded_fit_keeps_what_early_stopping_restored(gpu_lib):
         for a, b in zip(seen, seen1):                                        # every epoch's callback saw THAT epoch's tables
             assert (np.abs(a - b) <= 1e-4 + 2e-2 * np.abs(b)).mean() > 0.97
     assert np.array_equal(res[0][4], res[1][4])
+
+
+def test_column_sharded_fit_with_callbacks_on_one_rank(gpu_lib):
+    """a column-sharded fit() whose callbacks are given on rank 0 only (the usual way to pass a checkpoint or a
+    logger) used to refresh the whole tables -- an all_gather -- on rank 0 alone and deadlock at the end of the first epoch.  Every
+    rank now refreshes them before the callbacks when ANY rank has callbacks: the run completes and equals the one with the callback
+    on both ranks."""
+    from test_gpu_model import toy_graph
+    from threaded_dist import ThreadedWorld
+
+    from ampligraph_amd.latent_features import ScoringBasedEmbeddingModel, optimizers
+
+    X = toy_graph(n=900, N=70, R=4)
+    ents = np.array([f"e{i}" for i in range(70)])
+
+    class Snapshots:
+        def __init__(self):
+            self.seen = []
+
+        def set_model(self, m):
+            self.m = m
+
+        def on_epoch_end(self, epoch, logs=None):
+            self.m.is_fitted = True
+            self.seen.append(self.m.get_embeddings(ents).copy())
+
+    def run(dist, ranks_with_callback):
+        m = ScoringBasedEmbeddingModel(eta=4, k=24, scoring_type="ComplEx", seed=3)
+        m._dist_override = dist
+        m.compile(optimizer=optimizers.get("adam", {"learning_rate": 1e-2}), loss="self_adversarial", entity_sharding="columns")
+        snap = Snapshots()
+        h = m.fit(X, batch_size=256, epochs=4, verbose=False, callbacks=[snap] if dist.get_rank() in ranks_with_callback else None)
+        return h.history["loss"], snap.seen, m.get_embeddings(ents)
+
+    one = ThreadedWorld(2).run(lambda dist: run(dist, (0,)))
+    both = ThreadedWorld(2).run(lambda dist: run(dist, (0, 1)))
+    assert len(one[0][1]) == 4 and one[1][1] == []
+    assert np.array_equal(one[0][2], one[1][2])   # the whole tables of the two ranks: the same bits
+    for (hist, seen, final), (hist_b, seen_b, final_b) in zip(one, both):
+        assert np.allclose(hist, hist_b, rtol=2e-4)
+        assert (np.abs(final - final_b) <= 1e-5 + 1e-3 * np.abs(final_b)).mean() > 0.995
+    for a, b in zip(one[0][1], both[0][1]):        # what the callback saw at every epoch's end
+        assert (np.abs(a - b) <= 1e-5 + 1e-3 * np.abs(b)).mean() > 0.995

@@ -348,6 +348,7 @@ def test_model_row_sharded_matches_single_gpu(gpu_lib):
     from threaded_dist import ThreadedWorld
 
     from ampligraph_amd.latent_features import ScoringBasedEmbeddingModel, optimizers
+    from ampligraph_amd.placement import Rows
 
     X = toy_graph(n=600, N=50, R=3)
     Xtest = X[:60]
@@ -363,7 +364,7 @@ def test_model_row_sharded_matches_single_gpu(gpu_lib):
         m.compile(optimizer=optimizers.get("adam", {"learning_rate": 1e-2}), loss="self_adversarial",
                   entity_relation_regularizer="l2", entity_sharding="rows", sharded_negatives="global")
         h = m.fit(X, batch_size=bs, epochs=epochs, verbose=False)
-        assert m._spec is not None and m._engine.ent.shape[0] < 50 + 2 * m.EVAL_CHUNK_SHARDED + 1000
+        assert isinstance(m._placement, Rows) and m._engine.ent.shape[0] < 50 + 2 * m.EVAL_CHUNK_SHARDED + 1000
         ents = np.array([f"e{i}" for i in range(50)])
         return (h.history["loss"], m.get_embeddings(ents), m.predict(Xtest),
                 m.evaluate(Xtest, use_filter={"train": X}, corrupt_side="s,o", verbose=False),

@@ -11,7 +11,7 @@ import torch
 class ThreadedWorld:
     def __init__(self, world):
         self.world = world
-        self.barrier = threading.Barrier(world)
+        self.barrier = threading.Barrier(world, timeout=300)   # mismatched collectives fail (BrokenBarrierError) instead of hanging
         self.slots = [None] * world
         self.errors = []
 
