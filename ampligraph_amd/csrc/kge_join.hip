@@ -1,0 +1,255 @@
+// Exact self-join of a dense fp32 matrix X [n, d] in squared euclidean distance: the device side of find_duplicates
+// (the reference's discovery/discovery.py:714-982).  The reference fills a float64 n x n distance_matrix from
+// Python for its tolerance bound and runs a full sklearn radius_neighbors pass over all pairs at every bisection step;
+// here one pass over the pairs gives every row's nearest other row plus the largest pair distance (amdkge_join_nearest),
+// the bisection runs on the host over those n numbers, and a second pass emits the pairs within the chosen radius
+// (amdkge_join_radius).
+//
+// A pair's value is ONE fp32 expression of its two rows, d2 = fma chain over c = 0 .. d-1 of (x_ic - x_jc)^2 in column
+// order, computed by the same tile routine in both entry points; (x_i - x_j)^2 == (x_j - x_i)^2 exactly, so the value does
+// not depend on which side of the diagonal the pair lands either.  A row's nearest distance and the radius decisions
+// therefore agree bit for bit.  The direct form on purpose: the GEMM form |a|^2 + |b|^2 - 2<a,b> cancels for near pairs
+// (see pair_dist_kernel in kge_discovery.hip), and near pairs are what duplicate search is about.
+#include "kge_host.h"
+
+namespace kge {
+
+constexpr int JT = 128;           // rows per tile side
+constexpr int JKT = 16;           // columns per LDS stage
+constexpr int JLD = JT + 4;       // LDS row pitch (floats)
+constexpr int64_t JOIN_MAX_BLOCKS = 65536;   // persistent grid: every block walks tiles blockIdx.x, + gridDim.x, ...
+
+typedef float jf2 __attribute__((ext_vector_type(2)));
+
+// Tile t of the upper triangle (diagonal included), enumerated column by column: t = tb (tb + 1) / 2 + ta, ta <= tb.
+// (t < 2^47 for n = 2^31 - 1: 8 t + 1 is exact in a double; the two loops correct the square root's rounding.)
+__device__ __forceinline__ void join_tile_of(int64_t t, int64_t& ta, int64_t& tb) {
+    int64_t b = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (b > 0 && b * (b + 1) / 2 > t) --b;
+    while ((b + 1) * (b + 2) / 2 <= t) ++b;
+    tb = b;
+    ta = t - b * (b + 1) / 2;
+}
+
+// columns k0 .. k0 + JKT of rows r0 .. r0 + JT -> S[column][row] (rows beyond n repeat row n - 1, columns beyond d are 0 on
+// both sides: fma(0, 0, acc) == acc, so the padding leaves every sum as it is)
+template <bool V4>
+__device__ __forceinline__ void join_stage(const float* __restrict__ X, int64_t n, int d, int64_t r0, int k0, float (*S)[JLD], int tid) {
+    const int lrow = tid >> 1, lc = (tid & 1) * 8;
+    const int64_t r = r0 + lrow < n ? r0 + lrow : n - 1;
+    const float* row = X + r * (int64_t)d;
+    float v[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int c = k0 + lc + 4 * h;
+        if (V4) {   // d % 4 == 0: a group is either wholly inside the row or wholly beyond it
+            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (c < d) t = *reinterpret_cast<const float4*>(row + c);
+            v[4 * h] = t.x; v[4 * h + 1] = t.y; v[4 * h + 2] = t.z; v[4 * h + 3] = t.w;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[4 * h + u] = (c + u < d) ? row[c + u] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) S[lc + u][lrow] = v[u];
+}
+
+// Squared distances of the thread's 8 x 8 pairs of tile (ta, tb).  Thread (tq, te) = (tid / 16, tid % 16) owns A rows
+// ra0 + arow(x) and B rows rb0 + arow(y), arow(v) = v < 4 ? 4 t + v : 64 + 4 t + v - 4 (contiguous 16-byte LDS reads).
+// The inner step is the VALU tile of rank_count_kernel<MODE_L1>: a packed subtract forms a - b for two B rows at once (a
+// broadcast), and a packed FMA accumulates d * d -- strictly in column order for every pair.
+template <bool V4>
+__device__ __forceinline__ void join_tile(const float* __restrict__ X, int64_t n, int d, int64_t ra0, int64_t rb0, float (*As)[JLD], float (*Bs)[JLD],
+                                          jf2 (&acc)[8][4], int tid) {
+    const int tq = tid >> 4, te = tid & 15;
+    const bool diag = ra0 == rb0;
+    float (*B)[JLD] = diag ? As : Bs;
+#pragma unroll
+    for (int x = 0; x < 8; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) acc[x][y] = jf2{0.f, 0.f};
+    for (int k0 = 0; k0 < d; k0 += JKT) {
+        __syncthreads();   // the previous stage (or tile) is no longer read
+        join_stage<V4>(X, n, d, ra0, k0, As, tid);
+        if (!diag) join_stage<V4>(X, n, d, rb0, k0, Bs, tid);
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < JKT; ++kk) {
+            const float4 a0 = *reinterpret_cast<const float4*>(&As[kk][tq * 4]), a1 = *reinterpret_cast<const float4*>(&As[kk][64 + tq * 4]);
+            const float4 b0 = *reinterpret_cast<const float4*>(&B[kk][te * 4]), b1 = *reinterpret_cast<const float4*>(&B[kk][64 + te * 4]);
+            const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+            const jf2 bv[4] = {{b0.x, b0.y}, {b0.z, b0.w}, {b1.x, b1.y}, {b1.z, b1.w}};
+#pragma unroll
+            for (int x = 0; x < 8; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) {
+                    const jf2 dd = jf2{av[x], av[x]} - bv[y];
+                    acc[x][y] = __builtin_elementwise_fma(dd, dd, acc[x][y]);
+                }
+        }
+    }
+}
+
+__device__ __forceinline__ int join_row(int t, int v) { return v < 4 ? 4 * t + v : 64 + 4 * t + v - 4; }
+__device__ __forceinline__ float join_val(const jf2 (&acc)[8][4], int x, int v) { return (v & 1) ? acc[x][v >> 1].y : acc[x][v >> 1].x; }
+// nearest-row key: non-negative floats order like their bit patterns, so the 64-bit minimum is the smallest distance and,
+// among equal distances, the lowest index -- whatever order the atomics arrive in
+__device__ __forceinline__ unsigned long long join_key(float v, int64_t idx) {
+    return ((unsigned long long)__float_as_uint(v) << 32) | (unsigned long long)(uint32_t)idx;
+}
+__device__ __forceinline__ unsigned long long umin64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+template <bool V4>
+__global__ __launch_bounds__(256) void join_nearest_kernel(const float* __restrict__ X, int64_t n, int d, int64_t total,
+                                                           unsigned long long* __restrict__ keys, unsigned int* __restrict__ max_bits) {
+    __shared__ __attribute__((aligned(16))) float As[JKT][JLD];
+    __shared__ __attribute__((aligned(16))) float Bs[JKT][JLD];
+    __shared__ unsigned long long red[4][JT];
+    const int tid = threadIdx.x, tq = tid >> 4, te = tid & 15, wave = tid >> 6;
+    uint32_t mx = 0u;
+    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
+        int64_t ta, tb;
+        join_tile_of(t, ta, tb);
+        const int64_t ra0 = ta * JT, rb0 = tb * JT;
+        jf2 acc[8][4];
+        join_tile<V4>(X, n, d, ra0, rb0, As, Bs, acc, tid);
+        const bool diag = ta == tb;
+        // A side: the nearest B row of each A row (a diagonal tile holds both orders of its pairs: this side alone covers it)
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+            const int64_t ra = ra0 + join_row(tq, x);
+            unsigned long long m = ~0ull;
+#pragma unroll
+            for (int v = 0; v < 8; ++v) {
+                const int64_t rb = rb0 + join_row(te, v);
+                if (ra < n && rb < n && ra != rb) {
+                    const float val = join_val(acc, x, v);
+                    m = umin64(m, join_key(val, rb));
+                    mx = max(mx, __float_as_uint(val));
+                }
+            }
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) m = umin64(m, __shfl_xor(m, o, 64));
+            if (te == 0 && m != ~0ull) atomicMin(&keys[ra], m);
+        }
+        if (!diag) {
+            // B side: the nearest A row of each B row -- over the thread's 8, the wave's 4 A-row groups, then the 4 waves
+#pragma unroll
+            for (int v = 0; v < 8; ++v) {
+                const int64_t rb = rb0 + join_row(te, v);
+                unsigned long long m = ~0ull;
+#pragma unroll
+                for (int x = 0; x < 8; ++x) {
+                    const int64_t ra = ra0 + join_row(tq, x);
+                    if (ra < n && rb < n) m = umin64(m, join_key(join_val(acc, x, v), ra));
+                }
+                m = umin64(m, __shfl_xor(m, 16, 64));
+                m = umin64(m, __shfl_xor(m, 32, 64));
+                if ((tq & 3) == 0) red[wave][join_row(te, v)] = m;
+            }
+            __syncthreads();
+            if (tid < JT) {
+                const unsigned long long m = umin64(umin64(red[0][tid], red[1][tid]), umin64(red[2][tid], red[3][tid]));
+                if (m != ~0ull) atomicMin(&keys[rb0 + tid], m);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
+    if ((tid & 63) == 0 && mx != 0u) atomicMax(max_bits, mx);
+}
+
+__global__ __launch_bounds__(256) void join_keys_kernel(const unsigned long long* __restrict__ keys, int64_t n, float* __restrict__ dist,
+                                                        int32_t* __restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long k = keys[i];
+    dist[i] = k == ~0ull ? INFINITY : __uint_as_float((uint32_t)(k >> 32));
+    idx[i] = k == ~0ull ? -1 : (int32_t)(uint32_t)k;
+}
+
+template <bool V4>
+__global__ __launch_bounds__(256) void join_radius_kernel(const float* __restrict__ X, int64_t n, int d, int64_t total, double thr,
+                                                          int32_t* __restrict__ pairs, int64_t cap, unsigned long long* __restrict__ count) {
+    __shared__ __attribute__((aligned(16))) float As[JKT][JLD];
+    __shared__ __attribute__((aligned(16))) float Bs[JKT][JLD];
+    const int tid = threadIdx.x, tq = tid >> 4, te = tid & 15;
+    for (int64_t t = blockIdx.x; t < total; t += gridDim.x) {
+        int64_t ta, tb;
+        join_tile_of(t, ta, tb);
+        const int64_t ra0 = ta * JT, rb0 = tb * JT;
+        jf2 acc[8][4];
+        join_tile<V4>(X, n, d, ra0, rb0, As, Bs, acc, tid);
+        // every unordered pair once: i < j (off the diagonal every A row is below every B row); the fp32 value is compared
+        // with the double threshold as it is
+        uint64_t hit = 0ull;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+            const int64_t ra = ra0 + join_row(tq, x);
+#pragma unroll
+            for (int v = 0; v < 8; ++v) {
+                const int64_t rb = rb0 + join_row(te, v);
+                if (rb < n && ra < rb && (double)join_val(acc, x, v) <= thr) hit |= 1ull << (8 * x + v);
+            }
+        }
+        if (hit) {   // one counter update per thread and tile (filter_pairs_kernel's counter-and-capacity pattern)
+            unsigned long long pos = atomicAdd(count, (unsigned long long)__popcll(hit));
+            for (; hit; hit &= hit - 1ull, ++pos) {
+                const int b = __ffsll((unsigned long long)hit) - 1;
+                if ((int64_t)pos < cap) {
+                    pairs[2 * pos] = (int32_t)(ra0 + join_row(tq, b >> 3));
+                    pairs[2 * pos + 1] = (int32_t)(rb0 + join_row(te, b & 7));
+                }
+            }
+        }
+    }
+}
+
+inline int64_t join_tiles(int64_t n) {
+    const int64_t nt = (n + JT - 1) / JT;
+    return nt * (nt + 1) / 2;
+}
+
+}  // namespace kge
+
+using namespace kge;
+
+extern "C" int amdkge_join_nearest(const float* d_x, int64_t n, int32_t d, float* d_dist, int32_t* d_idx, float* d_max, void* d_work, void* stream) {
+    if (n < 0 || n > 0x7FFFFFFFll || d < 1) return set_error(AMDKGE_EINVAL, "join_nearest: bad sizes (0 <= n <= 2^31 - 1, d >= 1)");
+    if (!d_max || (n > 0 && (!d_x || !d_dist || !d_idx || !d_work))) return set_error(AMDKGE_EINVAL, "join_nearest: NULL pointer");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(d_max, 0, sizeof(float), st);
+    if (e != hipSuccess) return set_error_hip(e, "join_nearest: hipMemsetAsync");
+    if (n == 0) return AMDKGE_OK;
+    unsigned long long* keys = (unsigned long long*)d_work;
+    e = hipMemsetAsync(keys, 0xFF, (size_t)n * sizeof(unsigned long long), st);
+    if (e != hipSuccess) return set_error_hip(e, "join_nearest: hipMemsetAsync");
+    const int64_t total = join_tiles(n);
+    const dim3 grid((unsigned)(total < JOIN_MAX_BLOCKS ? total : JOIN_MAX_BLOCKS));
+    if (d % 4 == 0 && ((uintptr_t)d_x & 15u) == 0)
+        hipLaunchKernelGGL(join_nearest_kernel<true>, grid, dim3(256), 0, st, d_x, n, (int)d, total, keys, (unsigned int*)d_max);
+    else
+        hipLaunchKernelGGL(join_nearest_kernel<false>, grid, dim3(256), 0, st, d_x, n, (int)d, total, keys, (unsigned int*)d_max);
+    int rc = check_launch("join_nearest");
+    if (rc != AMDKGE_OK) return rc;
+    hipLaunchKernelGGL(join_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, d_dist, d_idx);
+    return check_launch("join_nearest keys");
+}
+
+extern "C" int amdkge_join_radius(const float* d_x, int64_t n, int32_t d, double thr, int32_t* d_pairs, int64_t cap, int64_t* d_count, void* stream) {
+    if (n < 0 || n > 0x7FFFFFFFll || d < 1 || cap < 0) return set_error(AMDKGE_EINVAL, "join_radius: bad sizes (0 <= n <= 2^31 - 1, d >= 1, cap >= 0)");
+    if (thr != thr) return set_error(AMDKGE_EINVAL, "join_radius: threshold is NaN");
+    if (!d_count || (cap > 0 && !d_pairs) || (n > 0 && !d_x)) return set_error(AMDKGE_EINVAL, "join_radius: NULL pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(d_count, 0, sizeof(int64_t), st);
+    if (e != hipSuccess) return set_error_hip(e, "join_radius: hipMemsetAsync");
+    if (n < 2) return AMDKGE_OK;
+    const int64_t total = join_tiles(n);
+    const dim3 grid((unsigned)(total < JOIN_MAX_BLOCKS ? total : JOIN_MAX_BLOCKS));
+    if (d % 4 == 0 && ((uintptr_t)d_x & 15u) == 0)
+        hipLaunchKernelGGL(join_radius_kernel<true>, grid, dim3(256), 0, st, d_x, n, (int)d, total, thr, d_pairs, cap, (unsigned long long*)d_count);
+    else
+        hipLaunchKernelGGL(join_radius_kernel<false>, grid, dim3(256), 0, st, d_x, n, (int)d, total, thr, d_pairs, cap, (unsigned long long*)d_count);
+    return check_launch("join_radius");
+}

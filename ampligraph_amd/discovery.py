@@ -1,15 +1,22 @@
 """Discovery helpers on the device: query_topn
-(/root/reference/ampligraph/discovery/discovery.py:985-1168) and find_nearest_neighbours (:1171-1244).
+(/root/reference/ampligraph/discovery/discovery.py:985-1168), find_nearest_neighbours (:1171-1244), find_duplicates
+(:714-982) and find_clusters (:546-711).
 
 The reference materialises one STRING triple per candidate, calls model.predict and argsorts on the host; its nearest
 neighbours are sklearn on the host.  Here an entity completion is ONE query through the 1-vs-all corruption-score kernels
 of evaluate() (amdkge_corruption_scores: same prep + tile kernels as the ranks) followed by a streaming top-k selection
 kernel (amdkge_topk_rows); nearest neighbours are dot products on the same tile kernel with the norms folded into the
 selection.  Only top_n ids / scores travel back.  Both work on a row-sharded entity table (per-shard lists, merged).
+find_duplicates is an exact self-join of the embeddings on the device (amdkge_join_nearest / amdkge_join_radius,
+kge_join.hip); its tolerance bisection runs on the host over one nearest distance per row.
 Same arguments, validation and error behaviour as the reference."""
+import logging
+
 import numpy as np
 
 from . import _ffi
+
+logger = logging.getLogger(__name__)
 
 
 def _known(indexer, values, type_of):
@@ -122,3 +129,225 @@ def find_nearest_neighbours(kge_model, entities, n_neighbors=10, entities_subset
     ids, dist = pl.select(lambda ids_, hi, kk: eng.nearest_rows(Q, kk, met, ent_ids=ids_, ent_hi=hi), cand, len(qid), k, largest=False)
     labels = ix.get_indexes(ids.reshape(-1), "e", "ind2raw").reshape(ids.shape)
     return labels, dist.astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------- find_duplicates / clusters
+_MODES = ("t", "e", "r")
+_EUCLIDEAN = ("l2", "euclidean", "minkowski")   # (sklearn's minkowski defaults to p = 2)
+_ZERO_NORM = 10 * np.finfo(np.float32).eps      # sklearn's normalize() leaves rows below this norm as they are
+
+
+def _fail(msg):
+    logger.error(msg)
+    raise ValueError(msg)
+
+
+def _validate(X, model, mode, clustering_algorithm=None):
+    """The reference's checks, messages and order (discovery.py:673-701, :888-912) -> (unwrapped model, X as an array)."""
+    model = getattr(model, "model", model) if getattr(model, "is_backward", False) else model   # 1.x compat wrappers
+    if not model.is_fitted:
+        _fail("Model has not been fitted.")
+    if clustering_algorithm is not None and not hasattr(clustering_algorithm, "fit_predict"):
+        _fail("Clustering algorithm does not have the `fit_predict` method.")
+    if mode not in _MODES:
+        _fail("Argument `mode` must be one of the following: {}.".format(", ".join(_MODES)))
+    X = np.asarray(X)
+    if mode == "t" and (len(X.shape) != 2 or X.shape[1] != 3):
+        _fail("For 't' mode the input X must be a matrix with three columns.")
+    if mode in ("e", "r") and len(X.shape) != 1:
+        _fail("For 'e' or 'r' mode the input X must be an array.")
+    return model, X
+
+
+def _device_embeddings(model, X, mode):
+    """fp32 device matrix of the rows of X: entity / relation embeddings, or [s | p | o] per triple (mode "t").  Entity rows
+    come from placement.entity_table() (a collective on a row-sharded table: every rank calls) + engine.unpack, as in
+    get_embeddings.  Unseen labels raise ValueError naming them (the reference's get_indexes drops them silently, which
+    shifts every later row onto the wrong label); non-finite embeddings raise ValueError, as sklearn does."""
+    import torch
+
+    ix, eng = model.data_indexer, model._engine
+    cols = [(X[:, 0], "e"), (X[:, 1], "r"), (X[:, 2], "e")] if mode == "t" else [(X, mode)]
+    ids = []
+    for labels, kind in cols:
+        got = np.asarray(ix.get_indexes(labels, kind), dtype=np.int64)
+        if len(got) != len(labels):
+            unseen = [u for u in dict.fromkeys(labels.tolist()) if len(ix.get_indexes(np.asarray([u]), kind)) == 0]
+            raise ValueError("{} not seen by the model: {}".format("Entities" if kind == "e" else "Relations", unseen))
+        ids.append(got)
+    parts = []
+    for (labels, kind), idx in zip(cols, ids):
+        tab = model._placement.entity_table() if kind == "e" else eng.rel
+        parts.append(eng.unpack(tab[torch.as_tensor(idx).to(tab.device)]))
+    emb = parts[0] if len(parts) == 1 else torch.cat(parts, 1).contiguous()
+    if not bool(torch.isfinite(emb).all()):
+        raise ValueError("Input contains NaN, infinity or a value too large for dtype('float32').")
+    return emb
+
+
+def _labels(X, mode):
+    return [tuple(r) for r in X.tolist()] if mode == "t" else X.tolist()
+
+
+def duplicate_tolerance(near, labels, to_thr, expected_fraction_duplicates, max_d, verbose=False):
+    """The reference's tolerance bisection (scipy.optimize.bisect on [0, max_d], xtol=1e-3, maxiter=50) over one number per
+    row: near[i] = row i's nearest other row in threshold units (float64).  A row's neighbour set has a partner exactly when
+    near[i] <= to_thr(tol), and every partner has one too, so the reference's len(set().union(*dups)) / n is the number of
+    distinct labels owning such a row over n."""
+    from scipy import optimize
+
+    n = len(near)
+    group = {}
+    inv = np.fromiter((group.setdefault(lab, len(group)) for lab in labels), dtype=np.int64, count=n)
+    per_label = np.full(len(group), np.inf)
+    np.minimum.at(per_label, inv, np.asarray(near, dtype=np.float64))
+    per_label.sort()
+    info = {"Nfeval": 0}
+
+    def f(tol):
+        frac = np.searchsorted(per_label, to_thr(tol), side="right") / n
+        if verbose:
+            info["Nfeval"] += 1
+            logger.info("Eval {}: tol: {}, duplicate fraction: {}".format(info["Nfeval"], tol, frac))
+        return frac - expected_fraction_duplicates
+
+    return optimize.bisect(f, 0.0, max_d, xtol=1e-3, maxiter=50)
+
+
+def duplicate_sets(pairs, labels, n):
+    """Sorted unordered pairs (i < j, int [m, 2]) -> the reference's result: for every row i with at least one partner,
+    frozenset({label(i)} | {label(j) : j partner of i}) -- one element when a repeated label's copies are the only partners."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if len(pairs) == 0:
+        return set()
+    a = np.concatenate([pairs[:, 0], pairs[:, 1]])
+    b = np.concatenate([pairs[:, 1], pairs[:, 0]])
+    order = np.argsort(a, kind="stable")
+    a, b = a[order], b[order]
+    cut = np.flatnonzero(np.diff(a)) + 1
+    out = set()
+    for rows, partners in zip(np.split(a, cut), np.split(b, cut)):
+        out.add(frozenset([labels[rows[0]]] + [labels[j] for j in partners.tolist()]))
+    return out
+
+
+def _join_nearest_units(eng, E, cosine, zero):
+    """Nearest other row of every row in threshold units (float64 numpy), the largest euclidean pair distance of the RAW rows
+    E (the reference's distance_matrix(emb, emb).max(), whatever the metric).  cosine: units of d2 between unit rows
+    (cosine distance = d2 / 2); rows in `zero` (numpy bool) have distance 1 (d2 = 2) to every other row, as in sklearn."""
+    import torch
+
+    d2, _, mx = eng.join_nearest(E)
+    max_d = float(np.sqrt(np.float64(mx.item())))
+    if not cosine:
+        return d2.cpu().numpy().astype(np.float64), max_d
+    n = int(E.shape[0])
+    keep = np.flatnonzero(~zero)
+    near = np.full(n, np.inf)
+    if len(keep):
+        U = _unit_rows(E[torch.as_tensor(keep).to(E.device)])
+        near[keep] = eng.join_nearest(U)[0].cpu().numpy().astype(np.float64)
+    if zero.any() and n > 1:
+        near = np.minimum(near, 2.0)
+    return near, max_d
+
+
+def _unit_rows(E):
+    import torch
+
+    return (E / torch.linalg.vector_norm(E, dim=1, keepdim=True)).contiguous()
+
+
+def _join_radius_pairs(eng, E, cosine, zero, thr):
+    """Sorted unordered pairs within thr (threshold units) -> int64 numpy [m, 2]."""
+    import torch
+
+    if not cosine:
+        return eng.join_radius(E, thr).cpu().numpy().astype(np.int64)
+    n = int(E.shape[0])
+    keep = np.flatnonzero(~zero)
+    pairs = [np.zeros((0, 2), np.int64)]
+    if len(keep) > 1:
+        p = eng.join_radius(_unit_rows(E[torch.as_tensor(keep).to(E.device)]), thr).cpu().numpy().astype(np.int64)
+        pairs.append(keep[p])
+    if zero.any() and 2.0 <= thr:   # a zero row is at cosine distance 1 from every other row
+        z = np.flatnonzero(zero)
+        i, j = np.meshgrid(z, np.arange(n), indexing="ij")
+        zp = np.stack([np.minimum(i, j).ravel(), np.maximum(i, j).ravel()], 1)
+        pairs.append(zp[zp[:, 0] != zp[:, 1]])
+    p = np.unique(np.concatenate(pairs), axis=0)
+    return p
+
+
+def find_duplicates(X, model, mode="e", metric="l2", tolerance="auto", expected_fraction_duplicates=0.1, verbose=False):
+    """Duplicate entities / relations / triples by distance in embedding space (:714-982): returns (set of frozensets of
+    labels, tolerance).  Two rows are duplicates when their distance under `metric` is <= tolerance; tolerance="auto"
+    bisects (scipy.optimize.bisect on [0, largest euclidean pair distance], xtol=1e-3) for the tolerance at which the
+    fraction of distinct labels with a duplicate reaches expected_fraction_duplicates.
+
+    "l2" / "euclidean" / "minkowski" (p = 2) and "cosine" run on the device as an exact self-join of the embeddings
+    (kge_join.hip): one pass gives every row's nearest other row and the bisection runs on the host over those n numbers;
+    one more pass emits the pairs at the chosen tolerance.  Other sklearn metrics fall back to sklearn NearestNeighbors on
+    the downloaded embeddings, as the reference does.  For every row with at least one partner the result holds
+    frozenset({its label} | {its partners' labels}); a label repeated in X whose copies are its only partners gives a
+    one-element set (the reference's code does the same, though its docstring says "at least two").  Differences from the
+    reference: labels the model has not seen raise ValueError naming them (the reference drops them silently and then
+    labels later rows wrongly); cosine rows of (near) zero norm are at distance 1 from every other row, as in sklearn."""
+    import torch
+
+    model, X = _validate(X, model, mode)
+    E = _device_embeddings(model, X, mode)
+    labels = _labels(X, mode)
+    n = int(E.shape[0])
+    eng = model._engine
+    if metric not in _EUCLIDEAN and metric != "cosine":
+        return _find_duplicates_sklearn(eng, E, X, mode, labels, metric, tolerance, expected_fraction_duplicates, verbose)
+    cosine = metric == "cosine"
+    to_thr = (lambda t: 2.0 * float(t)) if cosine else (lambda t: float(t) * float(t))
+    zero = np.zeros(n, dtype=bool)
+    if cosine:
+        zero = (torch.linalg.vector_norm(E, dim=1) < _ZERO_NORM).cpu().numpy()
+    if tolerance == "auto":
+        near, max_d = _join_nearest_units(eng, E, cosine, zero)
+        tolerance = duplicate_tolerance(near, labels, to_thr, expected_fraction_duplicates, max_d, verbose)
+    pairs = _join_radius_pairs(eng, E, cosine, zero, to_thr(tolerance))
+    return duplicate_sets(pairs, labels, n), tolerance
+
+
+def _find_duplicates_sklearn(eng, E, X, mode, labels, metric, tolerance, expected_fraction_duplicates, verbose):
+    """The reference's procedure for metrics the join does not cover (sklearn on the host); the "auto" upper bound (largest
+    euclidean pair distance) still comes from the device join."""
+    from scipy import optimize
+    from sklearn.neighbors import NearestNeighbors
+
+    emb = E.cpu().numpy()
+
+    def get_dups(tol):
+        neighbors = NearestNeighbors(metric=metric, radius=tol).fit(emb).radius_neighbors(emb)[1]
+        return {frozenset(labels[j] for j in row) for row in neighbors if len(row) > 1}
+
+    if tolerance == "auto":
+        info = {"Nfeval": 0}
+
+        def opt(tol):
+            frac = len(set().union(*get_dups(tol))) / len(emb)
+            if verbose:
+                info["Nfeval"] += 1
+                logger.info("Eval {}: tol: {}, duplicate fraction: {}".format(info["Nfeval"], tol, frac))
+            return frac - expected_fraction_duplicates
+
+        max_d = float(np.sqrt(np.float64(eng.join_nearest(E)[2].item())))
+        tolerance = optimize.bisect(opt, 0.0, max_d, xtol=1e-3, maxiter=50)
+    return get_dups(tolerance), tolerance
+
+
+def find_clusters(X, model, clustering_algorithm=None, mode="e"):
+    """Cluster labels of the embeddings of X (:546-711): entities, relations or [s | p | o] per triple, through
+    clustering_algorithm.fit_predict on the host (None: sklearn.cluster.DBSCAN() with its defaults).  Same validation and
+    embedding assembly as find_duplicates."""
+    if clustering_algorithm is None:
+        from sklearn.cluster import DBSCAN
+
+        clustering_algorithm = DBSCAN()
+    model, X = _validate(X, model, mode, clustering_algorithm)
+    return clustering_algorithm.fit_predict(_device_embeddings(model, X, mode).cpu().numpy())

@@ -536,6 +536,38 @@ class KgeEngine:
                                              _ptr(dist), _stream()))
         return self.topk_rows(dist, k, largest=False, payload=out_i)   # final order by the exact distances
 
+    def join_nearest(self, X):
+        """Exact self-join of the fp32 device matrix X [n, d] (amdkge_join_nearest): every row's nearest OTHER row in squared
+        euclidean distance -> (d2 fp32 [n], idx int32 [n] (equal distances: the lower index; n == 1: +inf / -1), largest
+        pair d2 fp32 [1]), all on the device."""
+        X = X.to(self.device, torch.float32).contiguous()
+        n, d = int(X.shape[0]), int(X.shape[1])
+        dist = torch.empty(n, dtype=torch.float32, device=self.device)
+        idx = torch.empty(n, dtype=torch.int32, device=self.device)
+        mx = torch.empty(1, dtype=torch.float32, device=self.device)
+        work = self._buf("join_keys", (max(n, 1),), torch.int64)
+        check(self.lib.amdkge_join_nearest(_ptr(X), n, d, _ptr(dist), _ptr(idx), _ptr(mx), _ptr(work), _stream()))
+        return dist, idx, mx
+
+    def join_radius(self, X, thr):
+        """Every unordered pair i < j of rows of the fp32 device matrix X [n, d] with squared euclidean distance <= thr
+        (amdkge_join_radius) -> int32 device tensor [m, 2], sorted lexicographically.  One synchronisation reads the count;
+        a count beyond the buffer's capacity relaunches with a buffer of that size."""
+        X = X.to(self.device, torch.float32).contiguous()
+        n, d = int(X.shape[0]), int(X.shape[1])
+        count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        cap = max(4 * n, 4096)
+        while True:
+            pairs = torch.empty(cap, 2, dtype=torch.int32, device=self.device)
+            check(self.lib.amdkge_join_radius(_ptr(X), n, d, float(thr), _ptr(pairs), cap, _ptr(count), _stream()))
+            m = int(count.item())
+            if m <= cap:
+                break
+            cap = m
+        key = pairs[:m].to(torch.int64)
+        order = torch.argsort(key[:, 0] * max(n, 1) + key[:, 1])
+        return pairs[:m][order].contiguous()
+
     def platt_step(self, scores_pos, scores_neg, w, b, label_pos, label_neg, weight_pos, weight_neg):
         """(loss, dloss/dw, dloss/db) of the Platt-scaling objective for one batch (amdkge_platt_step)."""
         out = torch.zeros(3, dtype=torch.float64, device=self.device)

@@ -436,6 +436,19 @@ int amdkge_topk_rows(const float* d_vals, int64_t n, int64_t m, int64_t ld, cons
 int amdkge_pair_distances(const float* d_q, int64_t n, const float* d_table, int32_t row_floats, const int32_t* d_ids, int64_t lo,
                           const int32_t* d_pos, int32_t k, int32_t cosine, float* d_out, void* stream);
 
+/* Exact self-join of a row-major fp32 matrix d_x [n, d] (0 <= n <= 2^31 - 1, d >= 1, finite values): find_duplicates
+ * (discovery/discovery.py:714-982).  Squared euclidean distances only, in the direct form: a pair's value is the fp32 fma
+ * chain over the columns, in column order, of (x_i - x_j)^2 -- the same expression in both entry points and in either order
+ * of the pair, so a row's nearest distance and the radius decisions agree bit for bit.  Each unordered pair is computed once.
+ * amdkge_join_nearest: per row i the nearest OTHER row -- d_dist[i] (squared distance) and d_idx[i] (equal distances: the lower
+ *   index; n == 1: +inf and -1) -- and *d_max = the largest squared distance over all pairs (0 when n < 2).  Deterministic.
+ *   d_work: 8 n bytes.
+ * amdkge_join_radius : every unordered pair i < j with d2 <= thr (the fp32 value compared with the double thr as it is) as int32
+ *   (i, j) into d_pairs [cap][2], in no particular order; *d_count = the number of such pairs (int64), also when it exceeds
+ *   cap (the caller then calls again with a larger buffer). */
+int amdkge_join_nearest(const float* d_x, int64_t n, int32_t d, float* d_dist, int32_t* d_idx, float* d_max, void* d_work, void* stream);
+int amdkge_join_radius(const float* d_x, int64_t n, int32_t d, double thr, int32_t* d_pairs, int64_t cap, int64_t* d_count, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU data path (one process per GPU; the host issues the RCCL collectives between these calls -- see
  * ampligraph_amd/sharded.py and trainer.py).  The reference has no multi-device path; what these replace is its
