@@ -1,5 +1,5 @@
 // Discovery helpers on the device: per-row top-k selection and squared row norms.  Together with
-// amdkge_corruption_scores / amdkge_row_dots (kge_rank.hip) they replace the host side of
+// amdkge_corruption_scores (kge_rank_tile.hip) / amdkge_row_dots (kge_rank.hip) they replace the host side of
 // /root/reference/ampligraph/discovery/discovery.py:985-1168 (query_topn: one STRING triple per candidate through
 // model.predict, then np.argsort) and :1171-1244 (find_nearest_neighbours: sklearn NearestNeighbors on the host).
 #include "kge_host.h"

@@ -10,7 +10,7 @@
 //   2. device radix sort of the keys (rocPRIM, only the bits R * N^2 needs)
 //   3. flags "new key" / "new group" per sorted position, one exclusive scan of the packed pair of counters (rocPRIM)
 //   4. scatter: ids[unique position] = key % N; keys[group] = key / N, start[group] = unique position   (filter_emit_kernel)
-// The per-triple lookup into this index is amdkge_filter_ranges (kge_rank.hip).  HBM-bound integer work: 310 k filter
+// The per-triple lookup into this index is amdkge_filter_ranges (kge_rank_filter.hip).  HBM-bound integer work: 310 k filter
 // triples at C2 are 2.5 MB of keys -- microseconds; the point is that evaluate() no longer spends 15 ms in host sorts.
 #include <string.h>
 

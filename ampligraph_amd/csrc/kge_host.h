@@ -4,12 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <exception>
+#include <initializer_list>
 #include <new>
 
 #include "../../include/amdkge.h"
 #include "kge_device.h"
+#include "kge_once.h"
 
 namespace kge {
 
@@ -17,18 +20,22 @@ int set_error(int code, const char* msg);            // stores a thread-local me
 int set_error_hip(hipError_t e, const char* where);  // AMDKGE_EHIP with hipGetErrorString
 int check_launch(const char* kernel_name);           // hipGetLastError() after a launch
 
-// "Once" for hipFuncSetAttribute-style set-up: a function's attributes belong to (function, DEVICE), and a process may drive several
-// devices (session groups: one replica and one host thread per GPU), so a process-wide `static bool` would set up device 0 only.
-// One bit per device ordinal (mod 64); racing threads at worst both do the idempotent set-up.
-struct PerDeviceOnce {
-    unsigned long long mask = 0ull;
-    int dev = 0;
-    bool need() {
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        return !((__atomic_load_n(&mask, __ATOMIC_RELAXED) >> (dev & 63)) & 1ull);
-    }
-    void done() { __atomic_fetch_or(&mask, 1ull << (dev & 63), __ATOMIC_RELAXED); }
-};
+// Raises the dynamic-LDS limit of `kernels` to `bytes` on the calling thread's current device, once per device (kge_once.h).  Every
+// kernel that is launched with more than 64 KB of dynamic LDS goes through this in front of its launch.  The first failure is
+// reported as "hipFuncSetAttribute(<what>): <HIP's message>", and the device stays unmarked.
+inline int ensure_dynamic_lds(PerDeviceOnce& once, std::initializer_list<const void*> kernels, size_t bytes, const char* what) {
+    hipError_t err = hipSuccess;
+    const bool ok = once.run([] { int dev = 0; return hipGetDevice(&dev) == hipSuccess ? dev : 0; },
+                             [&] {
+                                 for (const void* f : kernels)
+                                     if ((err = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) != hipSuccess) return false;
+                                 return true;
+                             });
+    if (ok) return AMDKGE_OK;
+    char where[96];
+    snprintf(where, sizeof(where), "hipFuncSetAttribute(%s)", what);
+    return set_error_hip(err, where);
+}
 
 // The session layers allocate on the host (staging vectors, the per-device threads of a group, the registries): those can throw,
 // the C ABI cannot.  Their entry points are function-try-blocks closed by KGE_CATCH("name").

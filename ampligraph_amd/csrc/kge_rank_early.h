@@ -1,5 +1,7 @@
 // evaluate(), distance models (TransE / RotatE): EXACT early exit of the 1-vs-all count pass.
-// Included by kge_rank.hip (namespace kge) behind the tile kernels and kge_rank_screen.h, whose ScreenBufs it reuses.
+// Included by kge_rank_tile.hip only (it defines kernels); the workspace head it shares with the screening pass (ScreenBufs), the
+// chains (rank_op / rot_exact_op) and the guard protocol come from kge_rank_common.h, and so
+// do the early exit's run-time knobs (EarlyCfg in RankConfig, set by amdkge_set_rank_early).
 //
 // The declared score of a (query i, entity j) pair is  -acc_U,  acc_u = fl(acc_{u-1} + t_u)  in unit order, with  t_u = |q_u +- e_u|
 // (TransE.py:77-83,107-113) or the correctly rounded modulus of RotatE's unit (RotatE.py:151-160,209-214) -- every t_u >= 0, so the
@@ -22,40 +24,12 @@
 //   * RotatE's fast modulus is exact only for x >= 2^-100: a workgroup that has met a smaller x (gmax > 2^50) does not exit
 //     early; its tile is redone with libm's sqrtf as before;
 //   * a full list raises the device flag and the plain kernel, guarded by that flag, redoes the call (no host round trip).
-// Two parts (no include guard): part 1 -- what the tile kernels need, included BEFORE them; part 2 (KGE_RANK_EARLY_PART2) -- the
-// workspace, the row-flag and recheck kernels, included behind kge_rank_screen.h (ScreenBufs) and rot_exact_op.
-#ifndef KGE_RANK_EARLY_PART2
+#pragma once
+#include "kge_rank_common.h"
 
 namespace kge {
 
 constexpr int EARLY_STAGE_PAIRS = 512;   // undecided pairs a tile may hand over (LDS staging)
-
-struct EarlyCfg {
-    int on = 1;
-    int check_l1 = 4, check_rot = 1;   // stages (of KT = 16 units) between two checks.  A check is ~15 % of a TransE stage (1.5 issue slots per
-                                       // pair and unit) and ~2 % of a RotatE stage: measured at the C2 shape on planted tables
-                                       // (profiles/r04d_distance_models_sweep.jsonl) TransE 1.25 ms with 4, 1.56 - 1.96 with 2 or 1;
-                                       // RotatE 6.2 - 6.3 ms with 1, 6.6 - 6.8 with 2
-    int cost = 16;                     // a re-checked pair's chain costs about this many tile-kernel pair chains (measured ~10: one lane
-                                       // per pair against a 4 x 4 register tile; handing over 2 % of the pairs costs what it saves)
-    int probe = 1;                     // 0: the early-exit kernel always does the work (tests)
-};
-static EarlyCfg g_early;
-
-// The PROBE (rank_early_probe_kernel, part 2) samples 4 096 (query, candidate) pairs and counts those already decided at half
-// their units; probe[0] = decided, probe[1] = sampled.  On tables whose positives do not stand out (an untrained model: nothing
-// is decided before the last units) the early-exit kernel would only pay for its checks and its lower occupancy (measured: TransE
-// k = 200, 12 % slower than the plain kernel), so the device decides which of the two kernels of the call does the work -- both
-// are launched, one returns at once, no host round trip.
-__device__ __forceinline__ bool early_probe_says_yes(const int* probe) { return probe[0] * 2 >= probe[1] && probe[1] > 0; }
-enum { GUARD_NONE = 0, GUARD_FLAG = 1 /* run iff *guard != 0 */, GUARD_EARLY = 2 /* run iff the probe says yes */,
-       GUARD_EARLY_FALLBACK = 3 /* run iff the probe says no, or *guard (the list overflowed) != 0 */ };
-__device__ __forceinline__ bool guard_says_run(int mode, const int* guard, const int* probe) {
-    if (mode == GUARD_FLAG) return *guard != 0;
-    if (mode == GUARD_EARLY) return early_probe_says_yes(probe);
-    if (mode == GUARD_EARLY_FALLBACK) return *guard != 0 || !early_probe_says_yes(probe);
-    return true;
-}
 
 // T = the largest fp32 acc >= 0 with quantise(sgn_scale * acc) >= qp; -1 when not even acc = 0 reaches qp (every pair of the
 // query is decided at once), +inf when every acc does (never decided).  quantise(sgn_scale * .) is non-increasing (sgn_scale < 0).
@@ -89,7 +63,6 @@ __device__ __forceinline__ bool early_decide(const EarlyShared& s, int units_don
 }
 
 // hand the undecided pairs of this thread (bit 4 x + y of `und`) to the list; called by every thread of the workgroup
-struct EarlyList { int* counter; int2* pairs; int64_t cap; };   // counter: [0] pairs appended, [1] overflow flag, [2] tiles ended early
 __device__ __forceinline__ void early_spill(EarlyShared& s, const EarlyList& b, uint32_t und, int total, int64_t q_first, int64_t cand_first) {
     const int c = __popc(und);
     if (c) {
@@ -113,19 +86,6 @@ __device__ __forceinline__ void early_spill(EarlyShared& s, const EarlyList& b, 
     if (base >= 0 && base + total <= b.cap)
         for (int i = threadIdx.x; i < total; i += 256) b.pairs[base + i] = s.pairs[i];
     __syncthreads();
-}
-
-
-}  // namespace kge
-
-#else   // ---------------------------------------------------------------- part 2
-
-namespace kge {
-
-
-// fixed part of the early-exit workspace: counters | this call's counts | row flags (queries, candidates)
-static inline size_t early_fixed_bytes(int64_t n, int64_t m) {
-    return 256 + scr_up((size_t)n * 8) + scr_up((size_t)n) + scr_up((size_t)m);
 }
 
 struct EarlyBufs {
@@ -333,5 +293,3 @@ __global__ __launch_bounds__(256) void rank_recheck_dist_kernel(RecheckDistArgs 
 
 
 }  // namespace kge
-
-#endif

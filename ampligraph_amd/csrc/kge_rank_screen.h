@@ -1,5 +1,6 @@
 // evaluate(), contraction models (DistMult / ComplEx / HolE): EXACT ranks from an int8 matrix-core screening pass.
-// Included by kge_rank.hip (namespace kge) behind the fp32 kernels, whose CountArgs / quantise / prep it shares.
+// Included by kge_rank_screen.hip only (it defines kernels); CountArgs / quantise, the workspace layout (ScreenBufs, carve_screen)
+// and RecheckArgs come from kge_rank_common.h.
 //
 // The declared score of a (query i, entity j) pair is the fp32 chain  S_ij = fmaf(q_U e_U, ... fmaf(q_1 e_1, 0))  in table
 // order (rank_op<MODE_DOT>; v_mfma_f32_32x32x2_f32 reproduces it bit for bit at the fp32 VECTOR rate, 157 TFLOP/s).  A rank
@@ -28,59 +29,13 @@
 // If the list overflows its capacity the whole call falls back to the exact fp32 MFMA kernel (device-side flag, no host
 // round trip).  Nothing here approximates a result: the int8 pass only decides which comparisons need the exact chain.
 #pragma once
+#include "kge_rank_common.h"
 
 namespace kge {
 
 typedef int v4i32 __attribute__((ext_vector_type(4)));
 typedef int v16i32 __attribute__((ext_vector_type(16)));
 
-constexpr int SCR_Q = 128, SCR_K = 32;   // queries per workgroup (4 waves x 32), units per stage
-constexpr int SCR_ROW_SLAB = 96;                       // bytes of one row per K slab: 3 limbs x 32 units
-// Limb storage is FRAGMENT-MAJOR: [block of 32 rows][slab][limb][half][row % 32][16 bytes] -- the 64 lanes of a matrix operand
-// fragment (lane = half * 32 + row % 32, 16 units each) read 1 KB of CONSECUTIVE memory, from global memory as from LDS.
-constexpr int SCR_BLK_SLAB = 32 * SCR_ROW_SLAB;        // bytes of one 32-row block per K slab (3 072)
-
-struct ScreenBufs {
-    int* counter;        // [0] undecided pairs appended, [1] overflow flag, [2] candidate rows > 4 bits below their tile's scale (rank_limbs_tile_kernel)
-    int32_t* counts;     // [n][2] this call's (greater, equal) counts (merged into the caller's unless the call fell back)
-    int8_t* qlimbs;      // [ceil(n / 32)][S][3][2][32][16]
-    float4* qm;          // [n] {A = 2^-a, u (1 + 2 U u) |W q|_2, |q|_1 / 2, 0}, all rounded up
-    float2* qt;          // [n] {T_ge, T_gt}
-    int8_t* elimbs;      // [ceil(m / 32)][S][3][2][32][16]
-    float4* em;          // [m] {B, |W e|_2, |e|_1 / 2, 0}
-    float4* tm;          // [ceil(m / 64)] per tile of 64 candidates {B_t, max |W e|_2, max |e|_1 / 2, 1 / B_t}: rank_limbs_tile_kernel (kernel r)
-    int2* pairs;         // [cap] (query, candidate position)
-    int64_t cap;
-    int S;               // K slabs per row
-};
-
-static inline size_t scr_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// fixed part of the workspace (everything but the pair list), for n queries against m candidates of U units
-static inline size_t screen_fixed_bytes(int64_t n, int64_t m, int U) {
-    const size_t S = (size_t)(U + SCR_K - 1) / SCR_K;
-    const size_t nb = (size_t)(n + 31) / 32 + 4, mb = (size_t)(m + 31) / 32 + 4;   // (+ a tile of slack: loaders read whole 128-row tiles)
-    return 256 + scr_up((size_t)n * 8) + scr_up(nb * S * SCR_BLK_SLAB) + scr_up((size_t)n * 16) + scr_up((size_t)n * 8) +
-           scr_up(mb * S * SCR_BLK_SLAB) + scr_up((size_t)m * 16) + scr_up(((size_t)(m + 63) / 64 + 4) * 16);
-}
-
-static inline ScreenBufs carve_screen(void* d_screen, size_t bytes, int64_t n, int64_t m, int U) {
-    ScreenBufs b;
-    b.S = (U + SCR_K - 1) / SCR_K;
-    char* p = (char*)(((uintptr_t)d_screen + 255) & ~(uintptr_t)255);
-    const char* end = (char*)d_screen + bytes;
-    b.counter = (int*)p; p += 256;
-    b.counts = (int32_t*)p; p += scr_up((size_t)n * 8);
-    b.qlimbs = (int8_t*)p; p += scr_up(((size_t)(n + 31) / 32 + 4) * b.S * SCR_BLK_SLAB);
-    b.qm = (float4*)p; p += scr_up((size_t)n * 16);
-    b.qt = (float2*)p; p += scr_up((size_t)n * 8);
-    b.elimbs = (int8_t*)p; p += scr_up(((size_t)(m + 31) / 32 + 4) * b.S * SCR_BLK_SLAB);
-    b.em = (float4*)p; p += scr_up((size_t)m * 16);
-    b.tm = (float4*)p; p += scr_up(((size_t)(m + 63) / 64 + 4) * 16);
-    b.pairs = (int2*)p;
-    b.cap = end > p ? (int64_t)((end - p) / 8) : 0;
-    return b;
-}
 
 // ---- 1. rows -> fixed point limbs + norms: one wave per row --------------------------------------------------------------------
 // src row r: table[ids ? ids[lo + r] : lo + r] (stride K floats), U units walked (whole float4s: U % 4 == 0).
@@ -599,17 +554,6 @@ __global__ __launch_bounds__(SCR_THREADS, 2) void rank_screen_kernel_v1_wild(Scr
 }
 
 // ---- 3. exact recheck of the undecided pairs: one lane per pair, the fp32 chain of rank_op<MODE_DOT> --------------------------
-struct RecheckArgs {
-    const float* ent;
-    const float* Q;
-    const int* qpos;
-    const int32_t* ent_ids;
-    int64_t ent_lo;
-    int U, K, QW;
-    float sgn_scale;
-    ScreenBufs b;
-};
-
 // One lane per pair, 64 pairs per wave -- but the rows are NOT read lane by lane (64 lanes x 16 bytes of 64 different rows per
 // load instruction: the address path, not the bytes, bound the first version at ~2 TB/s for 650 000 pairs).  A wave fetches
 // 32-unit chunks of its 64 query rows and 64 entity rows COALESCED (8 rows x one 128-byte line per instruction), parks them in

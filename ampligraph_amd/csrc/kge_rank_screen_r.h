@@ -1,5 +1,5 @@
 // Round 6: the screening kernel restructured around ONE wave per SIMD with the QUERY operand resident in registers.
-// Included by kge_rank.hip behind kge_rank_screen.h, whose limbs / thresholds / recheck / merge kernels, ScreenArgs and error bound it
+// Included by kge_rank_screen.hip; builds on kge_rank_screen.h, whose limbs / thresholds / recheck / merge kernels, ScreenArgs and error bound it
 // shares: the matrix work is rank_screen_kernel_v1's (six limb products in three exact int32 accumulator levels per output), the
 // decisions are the same ones taken in integer arithmetic against a tile-wide bound -- the counts are the same integers.
 //
@@ -34,6 +34,7 @@
 //     instruction read stale registers -- wrong, run-to-run different ranks in two otherwise correct variants.  The stage-0
 //     statements carry their own s_nop 1, and scripts/check_mfma_hazards.py (tests/test_build_hazards.py) scans the generated code.
 #pragma once
+#include "kge_rank_screen.h"
 
 #ifndef SCRR_ABLATE
 #define SCRR_ABLATE 0   // development (scripts/build_variant.sh with EXTRA=-DSCRR_ABLATE=n): 1 no epilogue slices, 2 no matrix instructions, 4 no stage barrier, 8 no fold of the accumulators, 16 no DMA, 32 no fragment reads, 64 no hand-over of the undecided outputs -- wrong counts, timing only

@@ -369,8 +369,8 @@ int amdkge_session_count_side(amdkge_session* s, const amdkge_model* m, const in
     KGE_RC(scratch(s, 2, n * 3 * (int64_t)sizeof(int32_t), &d_counts));   // counts [n,2] + sub [n]
     int32_t* d_sub = (int32_t*)d_counts + 2 * n;
     KGE_HIP(hipMemsetAsync(d_counts, 0, (size_t)n * 3 * sizeof(int32_t), s->st), "hipMemsetAsync");
-    // DistMult / ComplEx / HolE: the int8 screening pass + exact recheck (kge_rank_screen.h) -- the counts of amdkge_rank_counts,
-    // bit for bit, at about twice its rate; TransE / RotatE: their exact early exit (kge_rank_early.h) through the same workspace.
+    // DistMult / ComplEx / HolE: the int8 screening pass + exact recheck (kge_rank_screen.hip) -- the counts of amdkge_rank_counts,
+    // bit for bit, at about twice its rate; TransE / RotatE: their exact early exit (kge_rank_tile.hip, kge_rank_early.h) through the same workspace.
     // Beyond SCREEN_MAX (huge candidate ranges) or when the library sees nothing to gain (screen_need == 0: tiny problems) the
     // call is the plain amdkge_rank_counts.
     void* d_screen = nullptr;

@@ -1071,11 +1071,8 @@ static int plan_guard(const void* d_work, const TiledPlan& p, char* w, hipStream
 template <int MODEL, int CH, int UNROLL, bool DET = false>
 static int launch_tile(const TileArgs& a, size_t shmem, hipStream_t st) {
     static PerDeviceOnce attr;
-    if (attr.need()) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)tile_backward_kernel<MODEL, CH, UNROLL, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256))   // (the kernel has a few bytes of static LDS)
-            return set_error_hip(e, "hipFuncSetAttribute(tile_backward)");
-        attr.done();
-    }
+    if (int rc = ensure_dynamic_lds(attr, {(const void*)tile_backward_kernel<MODEL, CH, UNROLL, DET>}, 160 * 1024 - 256,   // (the kernel has a few bytes of static LDS)
+                                    "tile_backward")) return rc;
     hipLaunchKernelGGL((tile_backward_kernel<MODEL, CH, UNROLL, DET>), dim3(a.n_tiles + a.rel_blocks), dim3(TILE_THREADS), shmem, st, a);
     return check_launch("tile_backward");
 }
@@ -1090,11 +1087,7 @@ static int launch_forward_v(TrainArgs& f, hipStream_t st) {
     if (W != 1 || CHF != 1) shmem += sign_stash_bytes(MODEL, f.eta, CHF);   // (one wave per positive, one quad per lane: TransE takes the single-pass form, no stash)
     if (shmem > 64 * 1024) {
         static PerDeviceOnce attr;
-        if (attr.need()) {
-            if (hipError_t e = hipFuncSetAttribute((const void*)train_fwdbwd_kernel<MODEL, 4, W, CHF, true, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-                return set_error_hip(e, "hipFuncSetAttribute(train_forward_stage)");
-            attr.done();
-        }
+        if (int rc = ensure_dynamic_lds(attr, {(const void*)train_fwdbwd_kernel<MODEL, 4, W, CHF, true, DET>}, 160 * 1024, "train_forward_stage")) return rc;
     }
     const unsigned grid = KGE_DBG(f, 8192) ? 0u : (unsigned)((f.B + slots - 1) / slots);   // (ablation 8192: no forward launch)
     if (grid) hipLaunchKernelGGL((train_fwdbwd_kernel<MODEL, 4, W, CHF, true, DET>), dim3(grid), dim3(256), shmem, st, f);

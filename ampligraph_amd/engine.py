@@ -453,7 +453,7 @@ class KgeEngine:
                                     _ptr(out), _stream()))
         return out
 
-    # ------------------------------------------------------------------ discovery (kge_discovery.hip, kge_rank.hip)
+    # ------------------------------------------------------------------ discovery (kge_discovery.hip, kge_rank_tile.hip, kge_rank.hip)
     SCORE_CHUNK_BYTES = 256 << 20   # bound of the transient (queries x candidates) score block
 
     def topk_rows(self, vals, k, largest=True, col_scale=None, col_bias=None, payload=None):
@@ -656,7 +656,7 @@ class KgeEngine:
         work = self._workspace(n, lane)
         sfx = f"_lane{lane}" if lane else ""
         counts = torch.zeros(n, 2, dtype=torch.int32, device=self.device)
-        # contraction models: the int8 screening pass + exact recheck (kge_rank_screen.h) -- the same counts, bit for bit, at a
+        # contraction models: the int8 screening pass + exact recheck (kge_rank_screen.hip) -- the same counts, bit for bit, at a
         # multiple of the fp32 matrix rate; its workspace (fixed-point copies of the query vectors and the candidate rows, the
         # recheck list) is kept between calls.  Beyond SCREEN_MAX_BYTES (huge candidate ranges) the exact kernel runs alone.
         screen, sbytes = None, 0

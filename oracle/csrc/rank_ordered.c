@@ -10,7 +10,7 @@
  *     RotatE               acc = acc + sqrtf(re*re + im*im)
  * The reference's own order is whatever Eigen's reduce_sum does on the machine it runs on (it differs between its
  * CPU and GPU kernels); the numpy oracle (oracle/kge_oracle.py) accumulates in fp64, which is order-free.  This file
- * is the second oracle mode: the order the HIP rank kernels declare (ampligraph_amd/csrc/kge_rank.hip, rank_op), so
+ * is the second oracle mode: the order the HIP rank kernels declare (ampligraph_amd/csrc/kge_rank_common.h, rank_op), so
  * that filtered ranks can be compared BIT FOR BIT at full size.  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg may load it.
  *
@@ -22,7 +22,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-enum { MODE_DOT = 0, MODE_L1 = 1, MODE_ROT_O = 2, MODE_ROT_S = 3, MODE_L1_SUB = 4 };   /* same numbering as kge_rank.hip */
+enum { MODE_DOT = 0, MODE_L1 = 1, MODE_ROT_O = 2, MODE_ROT_S = 3, MODE_L1_SUB = 4 };   /* same numbering as kge_rank_common.h */
 
 #define TILE 64
 

@@ -4,7 +4,7 @@
 accumulation: order-free, but neither the reference's fp32 bits nor anybody else's, so ranks on real-valued tables
 could only be compared up to "fragile" comparisons at the int32(score * 1000) truncation boundary
 (AbstractScoringLayer.py:11,201).  The reference's own fp32 order is unspecified (Eigen reductions; its CPU and GPU
-kernels differ).  This module fixes ONE order -- the one the HIP rank kernels declare (ampligraph_amd/csrc/kge_rank.hip)
+kernels differ).  This module fixes ONE order -- the one the HIP rank kernels declare (ampligraph_amd/csrc/kge_rank_common.h: rank_op / rot_exact_op)
 -- and restates it on the CPU, so that filtered ranks are comparable BIT FOR BIT at full size:
 
   * query vectors and the positive's score in fp32 exactly where the reference rounds them (TransE.py:77-83,107-113,
@@ -19,7 +19,7 @@ kernels differ).  This module fixes ONE order -- the one the HIP rank kernels de
     ROUNDED to fp32 (evaluated in fp64, rounded once -- libm here, ocml on the GPU: both well inside the 2^-29 relative
     margin in which one more rounding could differ), the per-unit modulus a correctly rounded fp32 sqrtf of
     fl(fl(re re) + fl(im im)), accumulated over the LIVE units in table order.  That is the kernels' exact mode (the
-    default; kge_rank.hip rank_rot_kernel, kge_device.h sqrt_rn / prep_rel_exact), so RotatE is bit-comparable too.
+    default; kge_rank_tile.hip rank_rot_kernel, kge_device.h sqrt_rn / prep_rel_exact), so RotatE is bit-comparable too.
 """
 import ctypes as C
 import os

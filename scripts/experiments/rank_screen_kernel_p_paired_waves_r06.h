@@ -4,7 +4,7 @@
 // registers: no room to double-buffer the entity fragments, and in-place reloads leave half a stage of LDS latency uncovered.  To build it:
 // include behind kge_rank_screen_r.h and launch with 512 threads, SCRP_LDS_BYTES, on the tile-scale path of run_screen.
 // Round 6: the screening kernel with the six limb products SPLIT BETWEEN TWO WAVES of a SIMD.
-// Included by kge_rank.hip behind kge_rank_screen_r.h, whose tile-wide candidate scales (rank_limbs_tile_kernel), integer thresholds per
+// Included by kge_rank_screen.hip behind kge_rank_screen_r.h, whose tile-wide candidate scales (rank_limbs_tile_kernel), integer thresholds per
 // (query row, tile), sign-bit counting and DMA helper it shares: the counts are the same integers.
 //
 // Why.  rank_screen_kernel_r keeps a wave's query limbs resident (156 registers), which leaves room for ONE wave per SIMD -- and one wave

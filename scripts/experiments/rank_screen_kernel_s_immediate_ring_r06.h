@@ -7,7 +7,7 @@
 // and launch rank_screen_kernel_s<13> with ScrsLds<13>::bytes of dynamic LDS (git show 214863e^ has the wiring).
 //
 // Round 6, second step: rank_screen_kernel_r with its instruction stream cut down to what ONE wave can issue.
-// Included by kge_rank.hip behind kge_rank_screen_r.h (whose static_for and constants it uses).  Same matrix work, same decisions, same
+// Included by kge_rank_screen.hip behind kge_rank_screen_r.h (whose static_for and constants it uses).  Same matrix work, same decisions, same
 // counts as kernels v1 / r.
 //
 // Why.  One wave per SIMD hides about five single-issue instructions in the 32 cycles a v_mfma_i32_32x32x32_i8 occupies the pipe

@@ -1,7 +1,8 @@
 """The hand-written matrix-instruction streams of the screening kernels are inline assembly: the compiler cannot pad the hazards of
 instructions it does not see.  gfx90a+ wants two wait states between a VALU write of a VGPR and a matrix instruction that reads it;
 round 6 met the pattern twice (a register-allocator copy of a parked fragment right in front of its first use: wrong, timing-dependent
-ranks).  scripts/check_mfma_hazards.py compiles kge_rank.hip to device assembly (hipcc cross-compiles without a GPU) and scans it."""
+ranks).  scripts/check_mfma_hazards.py has the library's Makefile compile every ranking unit (ampligraph_amd/csrc/kge_rank*.hip) to
+device assembly (hipcc cross-compiles without a GPU) and scans it."""
 import importlib.util
 import os
 import shutil
@@ -35,8 +36,9 @@ _ZN3kge1kEv:
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
 def test_rank_kernels_have_no_unpadded_valu_write_in_front_of_a_matrix_instruction():
-    text = chk.device_asm(os.path.join(ROOT, "ampligraph_amd", "csrc", "kge_rank.hip"))
-    assert "v_mfma_i32_32x32x32_i8" in text
+    asm = chk.unit_asm()
+    assert "v_mfma_i32_32x32x32_i8" in asm["kge_rank_screen.hip"] and "v_mfma_f32_32x32x2" in asm["kge_rank_mfma.hip"]
+    text = "\n".join(asm.values())
     hits = chk.scan(text)
     assert hits == [], "\n".join("%s: %s -> %s" % (k, w, m) for k, _, w, m in hits[:10])
     # rank_screen_kernel_r<13> fills the register file and parks a few dwords that are live across its tile loop

@@ -324,7 +324,7 @@ def test_table_beyond_2_31_elements(gpu_lib, model, k):
 def test_fullsize_filtered_ranks_bit_identical(gpu_lib, model, k, dataset, n_test):
     """"Identical filtered ranks" (BASELINE.json north_star) at full size on REAL-VALUED tables: the HIP path against the
     oracle's declared-order fp32 mode (oracle/rank_ordered.py: same rounding points, same accumulation order as
-    kge_rank.hip declares) -- every test triple, filter = train + valid + test, three tie strategies, four corrupt_side
+    the ranking kernels declare, kge_rank_common.h) -- every test triple, filter = train + valid + test, three tie strategies, four corrupt_side
     forms, bit for bit.  (The fp64 oracle mode stays as the order-free cross-check in test_fullsize_ranks_against_oracle.)"""
     from oracle import kge_oracle as O
     from oracle import rank_ordered as RO

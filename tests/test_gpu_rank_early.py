@@ -1,4 +1,4 @@
-"""The exact early exit of evaluate()'s count pass for the distance models (kge_rank_early.h): counts bit-identical to the plain
+"""The exact early exit of evaluate()'s count pass for the distance models (kge_rank_tile.hip, kge_rank_early.h): counts bit-identical to the plain
 tile kernels (amdkge_set_rank_kernel(1): rank_count_kernel / rank_rot_kernel, themselves held bit for bit to the declared-order
 oracle in test_gpu_fullsize) -- on untrained tables (nothing is decided early), on tables where the positives score near the
 top (almost everything is), with ties, zeros, denormals, huge / inf / NaN rows, RotatE units of modulus exactly 0, candidate

@@ -1,4 +1,4 @@
-"""The int8 screening pass of evaluate() (kge_rank_screen.h): counts bit-identical to the exact fp32 kernels -- it only decides
+"""The int8 screening pass of evaluate() (kge_rank_screen.hip, kge_rank_screen.h): counts bit-identical to the exact fp32 kernels -- it only decides
 WHICH comparisons need the exact chain.  Against the unscreened pipelined MFMA kernel (amdkge_set_rank_kernel(3)), itself held
 bit for bit to the declared-order oracle in test_gpu_fullsize, on real-valued tables, tables with wild dynamic range, ties,
 inf / NaN rows, candidate subsets and ranges; and the recheck statistics (a fraction of a per cent of the comparisons)."""

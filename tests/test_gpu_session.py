@@ -207,7 +207,7 @@ def test_session_group_of_one_through_rccl(gpu_lib):
 @pytest.mark.parametrize("model,k", [("ComplEx", 100), ("DistMult", 200), ("TransE", 64)])
 def test_session_rank_takes_the_screening_pass(gpu_lib, model, k):
     """amdkge_session_rank counts through amdkge_rank_counts_screened: the contraction models report that the int8
-    screening pass ran (amdkge_session_screen_stats), TransE that its exact early exit did (kge_rank_early.h: on these untrained-looking
+    screening pass ran (amdkge_session_screen_stats), TransE that its exact early exit did (kge_rank_tile.hip, kge_rank_early.h: on these untrained-looking
     tables the device-side probe hands the work to the plain kernel, nothing is re-checked), and the ranks are those of the
     declared-order oracle, bit for bit, either way."""
     from oracle import rank_ordered as RO
