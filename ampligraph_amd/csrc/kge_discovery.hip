@@ -2,39 +2,9 @@
 // amdkge_corruption_scores (kge_rank_tile.hip) / amdkge_row_dots (kge_rank.hip) they replace the host side of
 // /root/reference/ampligraph/discovery/discovery.py:985-1168 (query_topn: one STRING triple per candidate through
 // model.predict, then np.argsort) and :1171-1244 (find_nearest_neighbours: sklearn NearestNeighbors on the host).
-#include "kge_host.h"
+#include "kge_topk.h"
 
 namespace kge {
-
-constexpr int TOPK_MAX = 1024;          // largest k
-constexpr int TOPK_BUF = 2 * TOPK_MAX;  // LDS candidates: the current best TOPK_MAX (sorted) + a staging half
-
-// order-preserving map fp32 -> uint32 (larger float <=> larger key); NaN sorts below everything
-__device__ __forceinline__ uint32_t sortable(float v) {
-    if (v != v) return 0u;
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float unsortable(uint32_t k) {
-    const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-    return __uint_as_float(b);
-}
-
-// bitonic sort of buf[0 .. TOPK_BUF) in DESCENDING order by the 64-bit key (256 threads)
-__device__ __forceinline__ void sort_desc(unsigned long long* buf, int tid) {
-    for (int k = 2; k <= TOPK_BUF; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < TOPK_BUF; i += 256) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const bool desc = (i & k) == 0;
-                    const unsigned long long a = buf[i], b = buf[p];
-                    if (desc ? (a < b) : (a > b)) { buf[i] = b; buf[p] = a; }
-                }
-            }
-            __syncthreads();
-        }
-}
 
 // One workgroup per row: streaming top-k.  key = sortable(value) << 32 | ~column, so equal values are ordered by
 // LOWER column first and the result is deterministic.  Values at or below the current k-th best are dropped as they

@@ -9,6 +9,12 @@ kernel (amdkge_topk_rows); nearest neighbours are dot products on the same tile 
 selection.  Only top_n ids / scores travel back.  Both work on a row-sharded entity table (per-shard lists, merged).
 find_duplicates is an exact self-join of the embeddings on the device (amdkge_join_nearest / amdkge_join_radius,
 kge_join.hip); its tolerance bisection runs on the host over one nearest distance per row.
+discover_facts (:21-271) and generate_candidates (:274-519) are the reference's procedure on the host -- the same legacy
+numpy draws in the same order, so equal inputs and seed give the reference's rows -- ranked by evaluate() on the device.
+discover_facts also runs strategy="exhaustive", which the reference documents and then rejects: every (s, o) pair of a
+relation, decided by two 1-vs-all score passes (amdkge_corruption_scores), a per-row selection of the columns that can
+still rank within the cut-off (amdkge_discover_select, kge_discover.hip), the intersection of the two sides and exact ranks
+of the survivors.
 Same arguments, validation and error behaviour as the reference."""
 import logging
 
@@ -17,6 +23,8 @@ import numpy as np
 from . import _ffi
 
 logger = logging.getLogger(__name__)
+
+__all__ = ["discover_facts", "generate_candidates", "query_topn", "find_nearest_neighbours", "find_duplicates", "find_clusters"]
 
 
 def _known(indexer, values, type_of):
@@ -351,3 +359,223 @@ def find_clusters(X, model, clustering_algorithm=None, mode="e"):
         clustering_algorithm = DBSCAN()
     model, X = _validate(X, model, mode, clustering_algorithm)
     return clustering_algorithm.fit_predict(_device_embeddings(model, X, mode).cpu().numpy())
+
+
+# ---------------------------------------------------------------------------------------------------- discover_facts
+_SAMPLED = ("random_uniform", "entity_frequency", "graph_degree", "cluster_coefficient", "cluster_triangles", "cluster_squares")
+
+
+def _row_keys(A, B):
+    """One int64 key per row of A and of B; two rows get the same key exactly when all their columns are equal."""
+    both = [np.asarray(M).astype(str) if np.asarray(M).dtype == object else np.asarray(M) for M in (A, B)]
+    M = np.concatenate(both, 0)
+    key = np.zeros(M.shape[0], dtype=np.int64)
+    for c in range(M.shape[1]):   # (re-numbered after every column: the keys stay below the row count)
+        uniq, code = np.unique(M[:, c], return_inverse=True)
+        key = np.unique(key * len(uniq) + code.reshape(-1), return_inverse=True)[1].reshape(-1).astype(np.int64)
+    return key[:len(A)], key[len(A):]
+
+
+def _setdiff2d(A, B):
+    """Rows of A that are not in B, in A's order (:522-543) -- with the reference's quirk: only the FIRST copy of a row of A
+    that occurs in B is removed, later copies of the same row survive.  The reference builds an |A| x |B| x columns comparison
+    array for this; here a row key (np.unique per column) and "first occurrence in A" give the same rows in O((|A| + |B|) log)."""
+    A, B = np.asarray(A), np.asarray(B)
+    if len(A.shape) != 2 or len(B.shape) != 2:
+        raise RuntimeError("Input arrays must be 2-dimensional.")
+    if len(A) == 0 or len(B) == 0:
+        return A[np.ones(len(A), dtype=bool)]
+    ka, kb = _row_keys(A, B)
+    first = np.zeros(len(A), dtype=bool)
+    first[np.unique(ka, return_index=True)[1]] = True
+    return A[~(first & np.isin(ka, kb))]
+
+
+def generate_candidates(X, strategy, target_rel, max_candidates, consolidate_sides=False, seed=0):
+    """Candidate statements (n, 3) for `target_rel` from the entities of X under a sampling strategy (:274-519): the grid of
+    sqrt(max_candidates) + 10 sampled subjects x sampled objects, minus the rows of X and the reflexive rows, up to five
+    rounds until max_candidates rows are collected.  "random_uniform" samples without replacement; "entity_frequency",
+    "graph_degree", "cluster_coefficient", "cluster_triangles" and "cluster_squares" (networkx) sample WITH replacement,
+    weighted by that statistic.  The draws are the reference's -- np.random.seed(seed), then np.random.choice for the subjects
+    and the objects of each round -- so equal inputs and seed give its rows, row for row.  That includes what its
+    _setdiff2d does: only the first copy of a row that occurs in X is removed, so the weighted strategies can return
+    duplicate rows and, now and then, a row of X."""
+    if X.shape[1] > 3:   # (weights beside the triples)
+        X = X[:, :3]
+    if strategy not in _SAMPLED:
+        raise ValueError("%s is not a valid candidate generation strategy." % strategy)
+    if not np.isin(target_rel, np.unique(X[:, 1])).all():   # (also for a list of relations, where the reference's `in` depends on numpy's broadcasting)
+        logger.warning("Target relation is not found in triples.")   # (no error: the relation may be absent from X)
+    if not isinstance(max_candidates, (float, int)):
+        raise ValueError("Parameter max_candidates must be a float or int.")
+    if max_candidates <= 0:
+        raise ValueError("Parameter max_candidates must be a positive integer or float in range (0,1].")
+    if isinstance(max_candidates, float):
+        max_candidates = int(max_candidates * len(X))
+
+    np.random.seed(seed)
+    if consolidate_sides:
+        e_s = e_o = np.unique(np.concatenate((X[:, 0], X[:, 2])))
+    else:
+        e_s, e_o = np.unique(X[:, 0]), np.unique(X[:, 2])
+    logger.info("Generating candidates using {} strategy.".format(strategy))
+
+    w_s = w_o = None
+    if strategy == "entity_frequency":
+        if consolidate_sides:
+            n_s = n_o = np.unique(X[:, [0, 2]], return_counts=True)[1].astype(np.float64)
+        else:
+            n_s = np.unique(X[:, 0], return_counts=True)[1].astype(np.float64)
+            n_o = np.unique(X[:, 2], return_counts=True)[1].astype(np.float64)
+        w_s, w_o = n_s / np.sum(n_s), n_o / np.sum(n_o)
+    elif strategy != "random_uniform":
+        import networkx as nx
+
+        G = nx.Graph()
+        for s, p, o in X:
+            G.add_nodes_from([s, o])
+            G.add_edge(s, o, name=p)
+        stat = {"graph_degree": lambda g: dict(g.degree()), "cluster_coefficient": nx.algorithms.cluster.clustering,
+                "cluster_triangles": nx.algorithms.cluster.triangles, "cluster_squares": nx.algorithms.cluster.square_clustering}[strategy](G)
+        w_s = np.array([stat[e] for e in e_s], dtype=np.float64)
+        w_o = np.array([stat[e] for e in e_o], dtype=np.float64)
+        w_s, w_o = w_s / np.sum(w_s), w_o / np.sum(w_o)
+
+    sample_size = int(np.sqrt(max_candidates) + 10)   # (+ 10: the filter below shrinks the grid)
+    out = np.zeros([max_candidates, 3], dtype=object)
+    filled = 0
+    for _ in range(5):
+        if filled > max_candidates - 1:
+            break
+        if w_s is None:
+            pick_s = np.random.choice(e_s, size=sample_size, replace=False)
+            pick_o = np.random.choice(e_o, size=sample_size, replace=False)
+        else:
+            pick_s = np.random.choice(e_s, size=sample_size, replace=True, p=w_s)
+            pick_o = np.random.choice(e_o, size=sample_size, replace=True, p=w_o)
+        grid = np.array(np.meshgrid(pick_s, target_rel, pick_o)).T.reshape(-1, 3)   # [s, rel, o] rows, subjects fastest
+        grid = _setdiff2d(grid, X)
+        grid = grid[grid[:, 0] != grid[:, 2]]
+        take = min(len(grid), max_candidates - filled)
+        out[filled:filled + take] = grid[:take]
+        filled += take
+    return out[:filled]
+
+
+def discover_facts(X, model, top_n=10, strategy="random_uniform", max_candidates=100, target_rel=None, seed=0):
+    """New statements the model ranks highly (:21-271): candidates for `target_rel` (a label, a list of labels, or None for
+    every relation of the model, one after the other) are ranked against their corruptions on both sides by
+    model.evaluate(candidates, use_filter={"test": X}, corrupt_side="s,o"), and those whose mean rank is <= top_n are
+    returned as (triples (n, 3) of labels, mean ranks (n,)).  A candidate is not in the filter, so it counts among its own
+    corruptions: with the default "worst" ties every rank is at least 2.
+
+    The sampled strategies draw the candidates with generate_candidates, as the reference does (a given list of target
+    relations goes there in one call).  strategy="exhaustive" -- documented and then rejected by the reference -- takes
+    every (s, r, o) with s != o that is not in X, for every target relation r and all entities of the model, and returns
+    exactly those whose mean rank is <= top_n, ordered by relation, subject id, object id; max_candidates is ignored.  It
+    runs on the device (two 1-vs-all score passes and a selection per relation, exact ranks of the survivors) and needs
+    the whole entity table on one GPU: row- and column-sharded models raise NotImplementedError.
+
+    Differences from the reference: (1) it returns np.hstack of the per-relation (n, 3) arrays, which is wrong or raises as
+    soon as there are two relations; here the rows are stacked vertically into one (n, 3) array (the same result when the
+    loop runs once).  (2) evaluate() drops candidates with labels the model has not seen, which shifts the ranks against
+    the candidates; here such candidates are dropped before ranking, so rows and ranks stay aligned."""
+    model = getattr(model, "model", model) if getattr(model, "is_backward", False) else model   # 1.x compat wrappers
+    if not model.is_fitted:
+        _fail("Model is not fitted.")
+    if strategy not in _SAMPLED + ("exhaustive",):
+        _fail("%s is not a valid strategy." % strategy)
+    if strategy == "exhaustive":
+        logger.info("Strategy is `exhaustive`, ignoring max_candidates.")
+    X = np.asarray(X)
+    if isinstance(max_candidates, float):
+        logger.debug("Converting max_candidates float value {} to int value {}".format(max_candidates, int(max_candidates * len(X))))
+        max_candidates = int(max_candidates * len(X))
+    if isinstance(target_rel, str):
+        target_rel = [target_rel]
+    ix = model.data_indexer
+    known = ix.get_indexes(np.arange(ix.get_relations_count()), "r", "ind2raw").tolist()
+    if target_rel is None:
+        logger.info("No target relation specified. Using all relations to generate candidate statements.")
+        rel_list = known
+    else:
+        missing = [rel for rel in target_rel if rel not in known]
+        if len(missing) > 0:
+            _fail("Target relation(s) not found in model: {}".format(missing))
+        rel_list = [target_rel]
+    if strategy == "exhaustive":
+        return _discover_exhaustive(X, model, top_n, known if target_rel is None else list(target_rel))
+    np.random.seed(seed)
+    found, found_ranks = [], []
+    for relation in rel_list:
+        logger.info("Generating candidates for relation: %s" % relation)
+        candidates = generate_candidates(X, strategy, relation, max_candidates, seed=seed)
+        logger.debug("Generated %d candidate statements." % len(candidates))
+        if len(candidates):
+            candidates = candidates[ix.valid_row_mask(candidates)]
+        ranks = model.evaluate(candidates, use_filter={"test": X}, corrupt_side="s,o", verbose=False) if len(candidates) else np.zeros((0, 2))
+        mean = np.mean(np.asarray(ranks).reshape(len(candidates), -1), axis=1)
+        keep = mean <= top_n
+        found.append(candidates[keep])
+        found_ranks.append(mean[keep])
+    logger.info("Discovered %d facts" % sum(len(f) for f in found))
+    return np.vstack(found), np.concatenate(found_ranks)
+
+
+def _discover_exhaustive(X, model, top_n, rel_labels, stats=None):
+    """strategy="exhaustive" of discover_facts.  Per relation: R = max(1, floor(2 top_n) - 1) bounds each side's rank (the
+    mean of two ranks >= 1 is <= top_n only if both are <= R); engine.corruption_select emits, for the queries (s, r, .) of
+    every s and (., r, o) of every o, the columns that can rank <= R (a superset: kge_discover.hip); the two lists are
+    intersected on s * N + o; placement.rank gives the survivors' exact ranks and the cut is applied to those, so the
+    result is evaluate()'s by construction.  stats: a dict that receives per-relation counts and (synchronised) phase times."""
+    import time
+
+    import torch
+
+    from .placement import Columns, Rows
+
+    pl = model._placement
+    if isinstance(pl, (Rows, Columns)):
+        raise NotImplementedError("strategy='exhaustive' scores every (s, o) pair against the whole entity table on one GPU: "
+                                  "row- and column-sharded tables (entity_sharding) are out of its scope; the sampled strategies work there")
+    eng, ix = model._engine, model.data_indexer
+    dev, N = eng.device, int(model._n_ents)
+    R = max(1, int(np.floor(2 * top_n)) - 1)
+    fi = model._filter_index({"test": X}, None)
+    ents = torch.arange(N, dtype=torch.int32, device=dev)
+    zero = torch.zeros_like(ents)
+    triples, mean_ranks = [np.zeros((0, 3), dtype=np.int64)], [np.zeros(0, dtype=np.float64)]
+
+    def tick():
+        if stats is not None:
+            torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    for r_id in np.asarray(ix.get_indexes(np.asarray(rel_labels), "r"), dtype=np.int64).tolist():
+        rel = torch.full_like(ents, r_id)
+        t0 = tick()
+        margin_q = eng.select_margin(r_id)
+        lists = {}
+        for side, name, q in ((_ffi.SIDE_O, "o", torch.stack([ents, rel, zero], 1).contiguous()),
+                              (_ffi.SIDE_S, "s", torch.stack([zero, rel, ents], 1).contiguous())):
+            lists[name] = eng.corruption_select(q, side, R, margin_q, fi.device_filter(eng, q, name))[0].to(torch.int64)
+        t1 = tick()
+        k_o = lists["o"][:, 0] * N + lists["o"][:, 1]   # (query s, column o)
+        k_s = lists["s"][:, 1] * N + lists["s"][:, 0]   # (query o, column s)
+        keys = torch.sort(k_o[torch.isin(k_o, k_s)]).values
+        t2 = tick()
+        kept = 0
+        if keys.numel():
+            tri = torch.stack([keys // N, torch.full_like(keys, r_id), keys % N], 1).to(torch.int32).cpu().numpy()
+            mean = pl.rank(tri, ["s", "o"], fi, None, "worst").cpu().numpy().astype(np.float64).mean(1)
+            keep = mean <= top_n
+            kept = int(keep.sum())
+            triples.append(tri[keep].astype(np.int64))
+            mean_ranks.append(mean[keep])
+        t3 = tick()
+        if stats is not None:
+            stats.setdefault("relations", []).append({
+                "relation": int(r_id), "R": R, "margin_q": int(margin_q), "emitted_o": int(k_o.numel()), "emitted_s": int(k_s.numel()),
+                "survivors": int(keys.numel()), "found": kept, "t_score_select": t1 - t0, "t_intersect": t2 - t1, "t_exact_ranks": t3 - t2})
+    logger.info("Discovered %d facts" % (sum(len(t) for t in triples)))
+    return ix.get_indexes(np.concatenate(triples), "t", "ind2raw"), np.concatenate(mean_ranks)

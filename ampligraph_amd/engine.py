@@ -568,6 +568,101 @@ class KgeEngine:
         order = torch.argsort(key[:, 0] * max(n, 1) + key[:, 1])
         return pairs[:m][order].contiguous()
 
+    # ------------------------------------------------------------------ discover_facts(strategy="exhaustive") (kge_discover.hip)
+    _INT32_MIN = -(1 << 31)
+
+    def select_margin(self, rel_id):
+        """margin_q of amdkge_discover_select for relation rel_id: an upper bound, in quanta of 1e-3, on the distance between
+        rank_prep's and the tile chain's fp32 value of one (s, rel_id, o) pair, from the largest entity row norm and the relation
+        row (DESIGN.md section 3 has the derivation): both values evaluate one sum of monomials with at most K + 18 roundings on
+        any path, so each is within gamma(K + 18) * B of the exact score, B = a bound on the sum of the monomials' magnitudes."""
+        col = torch.empty(self.n_ents, dtype=torch.float32, device=self.device)
+        check(self.lib.amdkge_row_sqnorms(_ptr(self.ent), self.Ks, None, 0, self.n_ents, 1.0, 0, _ptr(col), _stream()))
+        p = self.rel[int(rel_id)].to(torch.float64)
+        s2 = float(col.max().item()) * 1.001   # (the fp32 norm itself carries (K + 1) roundings)
+        p_inf, p_2 = float(p.abs().max().item()), float(torch.linalg.vector_norm(p).item())
+        K = float(self.Ks)
+        st = self.scoring_type
+        if st == "TransE":
+            B = np.sqrt(K) * (2.0 * np.sqrt(s2) + p_2)   # sum_c |s_c| + |p_c| + |o_c|, |x|_1 <= sqrt(K) |x|_2
+        elif st == "RotatE":
+            B = 3.0 * np.sqrt(K) * np.sqrt(s2)           # sum_c (|cos| + |sin|)(|s_re| + |s_im|) + |o_re| + |o_im|
+        else:
+            B = p_inf * s2                               # sum_c |s_c p_c o_c| <= |p|_inf |s|_2 |o|_2
+            if st != "DistMult":
+                B *= 2.0                                 # four triple products per complex unit
+            if st == "HolE":
+                B *= 2.0 / self.k_full
+        n_round = K + 18.0
+        u = 2.0 ** -24
+        gamma = n_round * u / (1.0 - n_round * u)
+        mq = 1.0 + np.ceil(1000.0 * 2.0 * gamma * B)
+        return int(mq) if np.isfinite(mq) and mq < 2 ** 30 else 2 ** 30
+
+    def _select_thresholds_sorted(self, vals, flt, R):
+        """T of amdkge_discover_select by a full device sort of the quantised rows: R beyond the streaming selection's 1024."""
+        n, m = int(vals.shape[0]), int(vals.shape[1])
+        v = vals.to(torch.float32)
+        bad = ~torch.isfinite(v).all(1)
+        q = torch.trunc(torch.nan_to_num(v, nan=0.0, posinf=0.0, neginf=0.0) * 1000.0).clamp(-2147483648.0, 2147483520.0).to(torch.int64)
+        gone = -(1 << 40)
+        if flt is not None:
+            lo, hi, ids = flt
+            cnt = (hi - lo).clamp(min=0)
+            rows = torch.repeat_interleave(torch.arange(n, device=self.device), cnt)
+            first = torch.cumsum(cnt, 0) - cnt
+            pos = torch.arange(int(rows.shape[0]), device=self.device) - first[rows] + lo[rows]
+            cols = ids[pos].to(torch.int64)
+            ok = (cols >= 0) & (cols < m)
+            q[rows[ok], cols[ok]] = gone
+        thr = torch.full((n,), self._INT32_MIN, dtype=torch.int64, device=self.device)
+        if m >= R:
+            t = torch.sort(q, dim=1, descending=True).values[:, R - 1]
+            thr = torch.where((t == gone) | bad, thr, t)
+        return thr.to(torch.int32)
+
+    def select_rows(self, vals, queries, side, R, margin_q, flt=None, row_base=0, cap=None):
+        """amdkge_discover_select on the score block vals [n, m] (columns = entity ids) of the query rows `queries` (int32 [n, 3]):
+        -> (pairs int32 [c, 2] of (row_base + row, column), in no particular order; thresholds int32 [n]).  One synchronisation
+        reads the count; a count beyond the buffer's capacity relaunches with a buffer of that size."""
+        n, m = int(vals.shape[0]), int(vals.shape[1])
+        R = int(R)
+        given = 1 if R > 1024 else 0
+        thr = self._select_thresholds_sorted(vals, flt, R) if given else torch.empty(n, dtype=torch.int32, device=self.device)
+        lo, hi, ids = flt if flt is not None else (None, None, None)
+        count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        cap = max(4096, 2 * min(R, m) * n) if cap is None else int(cap)
+        while True:
+            pairs = torch.empty(cap, 2, dtype=torch.int32, device=self.device)
+            check(self.lib.amdkge_discover_select(_ptr(vals), n, m, int(vals.stride(0)) if n else m, _ptr(queries), int(side), _ptr(lo), _ptr(hi),
+                                                  _ptr(ids), R, int(margin_q), _ptr(thr), given, int(row_base), _ptr(pairs), cap, _ptr(count),
+                                                  _stream()))
+            c = int(count.item())
+            if c <= cap:
+                break
+            cap = c
+        return pairs[:c], thr
+
+    def corruption_select(self, triples, side, R, margin_q, flt=None):
+        """select_rows over the 1-vs-all scores of every query triple against ALL entities: queries go through
+        amdkge_corruption_scores in chunks whose score block stays under SCORE_CHUNK_BYTES (as corruption_topk), each chunk
+        straight into the selection.  -> (pairs int32 [c, 2] of (query, entity), thresholds int32 [n])."""
+        n, m = int(triples.shape[0]), self.n_ents
+        rows = max(1, min(n, self.SCORE_CHUNK_BYTES // max(4 * m, 1)))
+        out = [torch.empty(0, 2, dtype=torch.int32, device=self.device)]
+        thr = torch.empty(n, dtype=torch.int32, device=self.device)
+        for c0 in range(0, n, rows):
+            c1 = min(n, c0 + rows)
+            blk = self._buf("disc_scores", (c1 - c0, m), torch.float32)
+            work = self._workspace(c1 - c0)
+            check(self.lib.amdkge_corruption_scores(C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples[c0:c1]), c1 - c0, int(side),
+                                                    None, 0, m, _ptr(blk), m, _ptr(work), _stream()))
+            f = None if flt is None else (flt[0][c0:c1], flt[1][c0:c1], flt[2])
+            p_, t_ = self.select_rows(blk, triples[c0:c1], side, R, margin_q, f, row_base=c0)
+            out.append(p_)
+            thr[c0:c1] = t_
+        return torch.cat(out), thr
+
     def platt_step(self, scores_pos, scores_neg, w, b, label_pos, label_neg, weight_pos, weight_neg):
         """(loss, dloss/dw, dloss/db) of the Platt-scaling objective for one batch (amdkge_platt_step)."""
         out = torch.zeros(3, dtype=torch.float64, device=self.device)

@@ -449,6 +449,25 @@ int amdkge_pair_distances(const float* d_q, int64_t n, const float* d_table, int
 int amdkge_join_nearest(const float* d_x, int64_t n, int32_t d, float* d_dist, int32_t* d_idx, float* d_max, void* d_work, void* stream);
 int amdkge_join_radius(const float* d_x, int64_t n, int32_t d, double thr, int32_t* d_pairs, int64_t cap, int64_t* d_count, void* stream);
 
+/* discover_facts(strategy = "exhaustive") (discovery/discovery.py:21-271 documents the strategy and rejects its name): the selection
+ * behind a 1-vs-all score block.  d_scores [n, m] (leading dimension ld) holds amdkge_corruption_scores' values of the query rows
+ * d_queries [n, 3] for `side` over ALL entities (column j = entity j); d_flt_lo / d_flt_hi / d_flt_ids are the rows' filter ranges
+ * (amdkge_filter_ranges; ids ascending inside a range; three NULLs: unfiltered).  Per row i:
+ *   T_i = the R-th largest QUANTISED score (trunc(score * 1000), as the rank kernels compare) over the columns evaluate() counts as
+ *         corruptions -- every column but the row's filter ids; the reflexive column and a candidate's own column are counted --,
+ *         with multiplicity; INT32_MIN when fewer than R such columns exist or the row holds a non-finite score.  Written to
+ *         d_thr[i]; with thr_given != 0 it is READ from there instead (R > 1024: the caller sorts) and R is only validated.
+ *   every column j that is not a filter id, not the row's own entity (subject for AMDKGE_SIDE_O, object for AMDKGE_SIDE_S) and has
+ *         quantise(score) >= T_i - margin_q is emitted as the int32 pair (row_base + i, j) into d_pairs [cap][2], in no
+ *         particular order; *d_count = the number of such pairs (int64), also when it exceeds cap (the caller then calls again
+ *         with a larger buffer): the protocol of amdkge_join_radius.
+ * A triple ranks <= R on this side only if its column is emitted, provided margin_q bounds the distance in quanta between
+ * rank_prep's value of a pair and the tile chain's (DESIGN.md section 3 derives the bound). */
+int amdkge_discover_select(const float* d_scores, int64_t n, int64_t m, int64_t ld, const int32_t* d_queries, int32_t side,
+                           const int64_t* d_flt_lo, const int64_t* d_flt_hi, const int32_t* d_flt_ids, int32_t R, int32_t margin_q,
+                           int32_t* d_thr, int32_t thr_given, int64_t row_base, int32_t* d_pairs, int64_t cap, int64_t* d_count,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU data path (one process per GPU; the host issues the RCCL collectives between these calls -- see
  * ampligraph_amd/sharded.py and trainer.py).  The reference has no multi-device path; what these replace is its
