@@ -123,6 +123,8 @@ SIGNATURES = {
     "amdkge_discover_select": (C.c_int, [P, I64, I64, I64, P, I32, P, P, P, I32, I32, P, I32, I64, P, I64, P, P]),
     "amdkge_join_nearest": (C.c_int, [P, I64, I32, P, P, P, P, P]),
     "amdkge_join_radius": (C.c_int, [P, I64, I32, C.c_double, P, I64, P, P]),
+    "amdkge_join_dbscan_workspace_bytes": (I64, [I64]),
+    "amdkge_join_dbscan": (C.c_int, [P, I64, I32, C.c_double, I32, P, P, P, P, P]),
     "amdkge_shard_route_workspace_bytes": (I64, [I64, I64]),
     "amdkge_shard_route": (C.c_int, [I64, I32, I32, P, I64, P, I64, I32, P, P, P, P, P, P]),
     "amdkge_gather_rows": (C.c_int, [P, I32, P, I64, P, P]),

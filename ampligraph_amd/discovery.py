@@ -8,7 +8,9 @@ of evaluate() (amdkge_corruption_scores: same prep + tile kernels as the ranks) 
 kernel (amdkge_topk_rows); nearest neighbours are dot products on the same tile kernel with the norms folded into the
 selection.  Only top_n ids / scores travel back.  Both work on a row-sharded entity table (per-shard lists, merged).
 find_duplicates is an exact self-join of the embeddings on the device (amdkge_join_nearest / amdkge_join_radius,
-kge_join.hip); its tolerance bisection runs on the host over one nearest distance per row.
+kge_join.hip); its tolerance bisection runs on the host over one nearest distance per row.  find_clusters runs DBSCAN -- its
+default, and the reference's documented use -- on the same join (amdkge_join_dbscan: neighbour count, union-find over the core
+rows, border pass; no pair list) and returns sklearn's labels; other clustering objects get the downloaded embeddings.
 discover_facts (:21-271) and generate_candidates (:274-519) are the reference's procedure on the host -- the same legacy
 numpy draws in the same order, so equal inputs and seed give the reference's rows -- ranked by evaluate() on the device.
 discover_facts also runs strategy="exhaustive", which the reference documents and then rejects: every (s, o) pair of a
@@ -349,16 +351,80 @@ def _find_duplicates_sklearn(eng, E, X, mode, labels, metric, tolerance, expecte
     return get_dups(tolerance), tolerance
 
 
+def _device_dbscan_params(algo):
+    """(eps, min_samples, cosine) when `algo` is an sklearn.cluster.DBSCAN whose result the device join computes exactly, else
+    None.  Covered: metric euclidean / l2 / minkowski with p in (None, 2) / cosine, no metric_params, and eps / min_samples that
+    sklearn's own parameter check accepts (anything else goes to sklearn, whose error then surfaces).  algorithm, leaf_size and
+    n_jobs choose how sklearn finds the neighbours, not which rows they are."""
+    import numbers
+
+    from sklearn.cluster import DBSCAN
+
+    if type(algo) is not DBSCAN or algo.metric_params is not None:
+        return None
+    if not (isinstance(algo.metric, str) and (algo.metric in _EUCLIDEAN or algo.metric == "cosine")):
+        return None
+    if algo.metric == "minkowski" and algo.p not in (None, 2):
+        return None
+    if algo.metric == "cosine" and algo.algorithm not in ("auto", "brute"):   # (sklearn's trees refuse the metric)
+        return None
+    eps, ms = algo.eps, algo.min_samples
+    if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not (0.0 < float(eps) < np.inf):
+        return None
+    if isinstance(ms, bool) or not isinstance(ms, numbers.Integral) or not (1 <= int(ms) <= 0x7FFFFFFF):
+        return None
+    return float(eps), int(ms), algo.metric == "cosine"
+
+
+def dbscan_labels(core, parent, border):
+    """sklearn.cluster.DBSCAN's labels_ from the three per-row results of the device passes (torch tensors on any one device;
+    the restatement of join_rank_kernel / join_labels_kernel in kge_join.hip, which the tests hold the kernels to).  core: bool [n];
+    parent: int [n], for a core row the lowest core row of its component; border: int [n], for a non-core row the lowest such root
+    among the core rows within its radius, or INT32_MAX.  Clusters are numbered by their lowest core row; a border row takes the
+    lowest-numbered cluster it touches; noise is -1.  -> int64 [n]."""
+    import torch
+
+    n = int(core.shape[0])
+    idx = torch.arange(n, device=core.device)
+    parent, border = parent.to(torch.int64), border.to(torch.int64)
+    root = core & (parent == idx)
+    rank = torch.cumsum(root.to(torch.int64), 0) - root.to(torch.int64)   # exclusive: the number of roots below each row
+    target = torch.where(core, parent, border)
+    noise = target == 0x7FFFFFFF
+    return torch.where(noise, torch.full_like(target, -1), rank[torch.where(noise, torch.zeros_like(target), target)])
+
+
 def find_clusters(X, model, clustering_algorithm=None, mode="e"):
-    """Cluster labels of the embeddings of X (:546-711): entities, relations or [s | p | o] per triple, through
-    clustering_algorithm.fit_predict on the host (None: sklearn.cluster.DBSCAN() with its defaults).  Same validation and
-    embedding assembly as find_duplicates."""
+    """Cluster labels of the embeddings of X (:546-711): entities, relations or [s | p | o] per triple.  Same validation and
+    embedding assembly as find_duplicates.
+
+    clustering_algorithm=None (sklearn.cluster.DBSCAN() with its defaults) or a DBSCAN instance with metric "euclidean" / "l2" /
+    "minkowski" (p = 2) / "cosine" and no metric_params runs on the device (engine.dbscan, kge_join.hip): a neighbour count, a
+    lock-free union-find over the core rows and a border pass on the exact self-join of find_duplicates, O(n) memory and no
+    pair list; the thresholds are eps^2, or 2 eps between unit rows for cosine.  The labels are sklearn's, numbering included,
+    and labels_, core_sample_indices_, components_ and n_features_in_ are set on the object as its fit_predict sets them.
+    Any other object, other DBSCAN parameters, an empty X or a cosine call with a row of (near) zero norm go through
+    clustering_algorithm.fit_predict on the downloaded embeddings, as in the reference."""
+    import torch
+
     if clustering_algorithm is None:
         from sklearn.cluster import DBSCAN
 
         clustering_algorithm = DBSCAN()
     model, X = _validate(X, model, mode, clustering_algorithm)
-    return clustering_algorithm.fit_predict(_device_embeddings(model, X, mode).cpu().numpy())
+    E = _device_embeddings(model, X, mode)
+    params = _device_dbscan_params(clustering_algorithm)
+    if params is not None and int(E.shape[0]) > 0:
+        eps, min_samples, cosine = params
+        if not cosine or not bool((torch.linalg.vector_norm(E, dim=1) < _ZERO_NORM).any()):
+            labels, core, _ = model._engine.dbscan(_unit_rows(E) if cosine else E, 2.0 * eps if cosine else eps * eps, min_samples)
+            algo = clustering_algorithm
+            algo.core_sample_indices_ = torch.nonzero(core).reshape(-1).cpu().numpy()
+            algo.components_ = E[core].cpu().numpy()
+            algo.labels_ = labels.cpu().numpy().astype(np.int64)
+            algo.n_features_in_ = int(E.shape[1])
+            return algo.labels_
+    return clustering_algorithm.fit_predict(E.cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------- discover_facts

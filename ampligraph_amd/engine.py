@@ -568,6 +568,21 @@ class KgeEngine:
         order = torch.argsort(key[:, 0] * max(n, 1) + key[:, 1])
         return pairs[:m][order].contiguous()
 
+    def dbscan(self, X, thr, min_samples):
+        """DBSCAN over the rows of the fp32 device matrix X [n, d] on the self-join (amdkge_join_dbscan): row j is a neighbour of
+        row i when their squared euclidean distance is <= thr (i is its own neighbour), a row with at least min_samples neighbours
+        is a core row -> (labels int32 [n] in sklearn's numbering, -1 = noise; core bool [n]; n_clusters int32 [1]), all on the
+        device, no synchronisation.  Three passes over the pairs and 12 n bytes of scratch: no pair list."""
+        X = X.to(self.device, torch.float32).contiguous()
+        n, d = int(X.shape[0]), int(X.shape[1])
+        labels = torch.empty(n, dtype=torch.int32, device=self.device)
+        core = torch.empty(n, dtype=torch.uint8, device=self.device)
+        n_clusters = torch.empty(1, dtype=torch.int32, device=self.device)
+        work = self._buf("join_dbscan", (max(int(self.lib.amdkge_join_dbscan_workspace_bytes(n)) // 4, 1),), torch.int32)
+        check(self.lib.amdkge_join_dbscan(_ptr(X), n, d, float(thr), int(min_samples), _ptr(labels), _ptr(core), _ptr(n_clusters), _ptr(work),
+                                          _stream()))
+        return labels, core.view(torch.bool), n_clusters
+
     # ------------------------------------------------------------------ discover_facts(strategy="exhaustive") (kge_discover.hip)
     _INT32_MIN = -(1 << 31)
 

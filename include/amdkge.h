@@ -449,6 +449,22 @@ int amdkge_pair_distances(const float* d_q, int64_t n, const float* d_table, int
 int amdkge_join_nearest(const float* d_x, int64_t n, int32_t d, float* d_dist, int32_t* d_idx, float* d_max, void* d_work, void* stream);
 int amdkge_join_radius(const float* d_x, int64_t n, int32_t d, double thr, int32_t* d_pairs, int64_t cap, int64_t* d_count, void* stream);
 
+/* DBSCAN over the rows of d_x [n, d] on the self-join above: find_clusters (discovery/discovery.py:546-711) with its default
+ * algorithm.  Row j is a neighbour of row i when the join's fp32 d2(i, j) <= thr (compared with the double as it is; i is its own
+ * neighbour); a row with at least min_samples neighbours is a core row; clusters are the connected components of the core rows
+ * under that relation.  Output, exactly sklearn.cluster.DBSCAN's for the same neighbour relation:
+ *   d_core[i]     1 for a core row, else 0;
+ *   d_labels[i]   clusters are numbered 0, 1, ... by their lowest core row; a core row has its cluster's number, a non-core row the
+ *                 lowest number among the clusters that have a core row among its neighbours, or -1 (noise);
+ *   *d_n_clusters the number of clusters (int32, device memory).
+ * Three passes over the pairs (count, union, border), no pair list: d_work holds amdkge_join_dbscan_workspace_bytes(n) = 12 n bytes
+ * (-1 for an n outside 0 .. 2^31 - 1), three int32 arrays of n: [the roots' ranks | every core row's root = the lowest core row of
+ * its cluster | per non-core row the lowest such root among its neighbours, or INT32_MAX] on return.  The result is a function of
+ * the neighbour relation alone: two calls give identical arrays.  Asynchronous on `stream`.  n == 0 writes *d_n_clusters = 0. */
+int64_t amdkge_join_dbscan_workspace_bytes(int64_t n);
+int amdkge_join_dbscan(const float* d_x, int64_t n, int32_t d, double thr, int32_t min_samples, int32_t* d_labels, uint8_t* d_core,
+                       int32_t* d_n_clusters, void* d_work, void* stream);
+
 /* discover_facts(strategy = "exhaustive") (discovery/discovery.py:21-271 documents the strategy and rejects its name): the selection
  * behind a 1-vs-all score block.  d_scores [n, m] (leading dimension ld) holds amdkge_corruption_scores' values of the query rows
  * d_queries [n, 3] for `side` over ALL entities (column j = entity j); d_flt_lo / d_flt_hi / d_flt_ids are the rows' filter ranges
