@@ -125,6 +125,9 @@ SIGNATURES = {
     "amdkge_join_radius": (C.c_int, [P, I64, I32, C.c_double, P, I64, P, P]),
     "amdkge_join_dbscan_workspace_bytes": (I64, [I64]),
     "amdkge_join_dbscan": (C.c_int, [P, I64, I32, C.c_double, I32, P, P, P, P, P]),
+    "amdkge_kmeans_workspace_bytes": (I64, [I64, I32, I32, I32]),
+    "amdkge_kmeans_assign": (C.c_int, [P, I64, I32, P, I32, I32, P, P, P]),
+    "amdkge_kmeans_lloyd": (C.c_int, [P, I64, I32, P, I32, I32, I32, C.c_double, P, P, P, P, P, P]),
     "amdkge_shard_route_workspace_bytes": (I64, [I64, I64]),
     "amdkge_shard_route": (C.c_int, [I64, I32, I32, P, I64, P, I64, I32, P, P, P, P, P, P]),
     "amdkge_gather_rows": (C.c_int, [P, I32, P, I64, P, P]),

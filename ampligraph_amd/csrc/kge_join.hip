@@ -13,16 +13,12 @@
 //
 // find_clusters' DBSCAN (the reference's discovery/discovery.py:546-711 hands the embeddings to sklearn on the host) runs on the
 // same tile routine: amdkge_join_dbscan, three passes over the pairs and O(n) state, below the two duplicate kernels.
-#include "kge_host.h"
+#include "kge_join_tile.h"
 
 namespace kge {
 
-constexpr int JT = 128;           // rows per tile side
-constexpr int JKT = 16;           // columns per LDS stage
-constexpr int JLD = JT + 4;       // LDS row pitch (floats)
+// (the tile routine -- join_stage, join_tile, join_row, join_val, join_key, umin64 -- lives in kge_join_tile.h)
 constexpr int64_t JOIN_MAX_BLOCKS = 65536;   // persistent grid: every block walks tiles blockIdx.x, + gridDim.x, ...
-
-typedef float jf2 __attribute__((ext_vector_type(2)));
 
 // Tile t of the upper triangle (diagonal included), enumerated column by column: t = tb (tb + 1) / 2 + ta, ta <= tb.
 // (t < 2^47 for n = 2^31 - 1: 8 t + 1 is exact in a double; the two loops correct the square root's rounding.)
@@ -33,75 +29,6 @@ __device__ __forceinline__ void join_tile_of(int64_t t, int64_t& ta, int64_t& tb
     tb = b;
     ta = t - b * (b + 1) / 2;
 }
-
-// columns k0 .. k0 + JKT of rows r0 .. r0 + JT -> S[column][row] (rows beyond n repeat row n - 1, columns beyond d are 0 on
-// both sides: fma(0, 0, acc) == acc, so the padding leaves every sum as it is)
-template <bool V4>
-__device__ __forceinline__ void join_stage(const float* __restrict__ X, int64_t n, int d, int64_t r0, int k0, float (*S)[JLD], int tid) {
-    const int lrow = tid >> 1, lc = (tid & 1) * 8;
-    const int64_t r = r0 + lrow < n ? r0 + lrow : n - 1;
-    const float* row = X + r * (int64_t)d;
-    float v[8];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int c = k0 + lc + 4 * h;
-        if (V4) {   // d % 4 == 0: a group is either wholly inside the row or wholly beyond it
-            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < d) t = *reinterpret_cast<const float4*>(row + c);
-            v[4 * h] = t.x; v[4 * h + 1] = t.y; v[4 * h + 2] = t.z; v[4 * h + 3] = t.w;
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[4 * h + u] = (c + u < d) ? row[c + u] : 0.f;
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) S[lc + u][lrow] = v[u];
-}
-
-// Squared distances of the thread's 8 x 8 pairs of tile (ta, tb).  Thread (tq, te) = (tid / 16, tid % 16) owns A rows
-// ra0 + arow(x) and B rows rb0 + arow(y), arow(v) = v < 4 ? 4 t + v : 64 + 4 t + v - 4 (contiguous 16-byte LDS reads).
-// The inner step is the VALU tile of rank_count_kernel<MODE_L1>: a packed subtract forms a - b for two B rows at once (a
-// broadcast), and a packed FMA accumulates d * d -- strictly in column order for every pair.
-template <bool V4>
-__device__ __forceinline__ void join_tile(const float* __restrict__ X, int64_t n, int d, int64_t ra0, int64_t rb0, float (*As)[JLD], float (*Bs)[JLD],
-                                          jf2 (&acc)[8][4], int tid) {
-    const int tq = tid >> 4, te = tid & 15;
-    const bool diag = ra0 == rb0;
-    float (*B)[JLD] = diag ? As : Bs;
-#pragma unroll
-    for (int x = 0; x < 8; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) acc[x][y] = jf2{0.f, 0.f};
-    for (int k0 = 0; k0 < d; k0 += JKT) {
-        __syncthreads();   // the previous stage (or tile) is no longer read
-        join_stage<V4>(X, n, d, ra0, k0, As, tid);
-        if (!diag) join_stage<V4>(X, n, d, rb0, k0, Bs, tid);
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < JKT; ++kk) {
-            const float4 a0 = *reinterpret_cast<const float4*>(&As[kk][tq * 4]), a1 = *reinterpret_cast<const float4*>(&As[kk][64 + tq * 4]);
-            const float4 b0 = *reinterpret_cast<const float4*>(&B[kk][te * 4]), b1 = *reinterpret_cast<const float4*>(&B[kk][64 + te * 4]);
-            const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-            const jf2 bv[4] = {{b0.x, b0.y}, {b0.z, b0.w}, {b1.x, b1.y}, {b1.z, b1.w}};
-#pragma unroll
-            for (int x = 0; x < 8; ++x)
-#pragma unroll
-                for (int y = 0; y < 4; ++y) {
-                    const jf2 dd = jf2{av[x], av[x]} - bv[y];
-                    acc[x][y] = __builtin_elementwise_fma(dd, dd, acc[x][y]);
-                }
-        }
-    }
-}
-
-__device__ __forceinline__ int join_row(int t, int v) { return v < 4 ? 4 * t + v : 64 + 4 * t + v - 4; }
-__device__ __forceinline__ float join_val(const jf2 (&acc)[8][4], int x, int v) { return (v & 1) ? acc[x][v >> 1].y : acc[x][v >> 1].x; }
-// nearest-row key: non-negative floats order like their bit patterns, so the 64-bit minimum is the smallest distance and,
-// among equal distances, the lowest index -- whatever order the atomics arrive in
-__device__ __forceinline__ unsigned long long join_key(float v, int64_t idx) {
-    return ((unsigned long long)__float_as_uint(v) << 32) | (unsigned long long)(uint32_t)idx;
-}
-__device__ __forceinline__ unsigned long long umin64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 
 template <bool V4>
 __global__ __launch_bounds__(256) void join_nearest_kernel(const float* __restrict__ X, int64_t n, int d, int64_t total,
@@ -116,7 +43,7 @@ __global__ __launch_bounds__(256) void join_nearest_kernel(const float* __restri
         join_tile_of(t, ta, tb);
         const int64_t ra0 = ta * JT, rb0 = tb * JT;
         jf2 acc[8][4];
-        join_tile<V4>(X, n, d, ra0, rb0, As, Bs, acc, tid);
+        join_tile<V4>(X, n, X, n, d, ra0, rb0, As, Bs, acc, tid);
         const bool diag = ta == tb;
         // A side: the nearest B row of each A row (a diagonal tile holds both orders of its pairs: this side alone covers it)
 #pragma unroll
@@ -183,7 +110,7 @@ __global__ __launch_bounds__(256) void join_radius_kernel(const float* __restric
         join_tile_of(t, ta, tb);
         const int64_t ra0 = ta * JT, rb0 = tb * JT;
         jf2 acc[8][4];
-        join_tile<V4>(X, n, d, ra0, rb0, As, Bs, acc, tid);
+        join_tile<V4>(X, n, X, n, d, ra0, rb0, As, Bs, acc, tid);
         // every unordered pair once: i < j (off the diagonal every A row is below every B row); the fp32 value is compared
         // with the double threshold as it is
         uint64_t hit = 0ull;
@@ -245,7 +172,7 @@ __global__ __launch_bounds__(256) void join_count_kernel(const float* __restrict
         join_tile_of(t, ta, tb);
         const int64_t ra0 = ta * JT, rb0 = tb * JT;
         jf2 acc[8][4];
-        join_tile<V4>(X, n, d, ra0, rb0, As, Bs, acc, tid);
+        join_tile<V4>(X, n, X, n, d, ra0, rb0, As, Bs, acc, tid);
         const bool diag = ta == tb;
         const uint64_t hit = join_hits(acc, ra0, rb0, n, thr, tq, te, false);
 #pragma unroll
@@ -331,7 +258,7 @@ __global__ __launch_bounds__(256) void join_union_kernel(const float* __restrict
         join_tile_of(t, ta, tb);
         const int64_t ra0 = ta * JT, rb0 = tb * JT;
         jf2 acc[8][4];
-        join_tile<V4>(X, n, d, ra0, rb0, As, Bs, acc, tid);
+        join_tile<V4>(X, n, X, n, d, ra0, rb0, As, Bs, acc, tid);
         uint64_t hit = join_hits(acc, ra0, rb0, n, thr, tq, te, true);
         if (!__syncthreads_or(hit != 0ull)) continue;   // most tiles of a sparse matrix: nothing to look up (the barrier also ends the previous tile's reads of rt)
         const bool diag = ta == tb;
@@ -371,7 +298,7 @@ __global__ __launch_bounds__(256) void join_border_kernel(const float* __restric
         join_tile_of(t, ta, tb);
         const int64_t ra0 = ta * JT, rb0 = tb * JT;
         jf2 acc[8][4];
-        join_tile<V4>(X, n, d, ra0, rb0, As, Bs, acc, tid);
+        join_tile<V4>(X, n, X, n, d, ra0, rb0, As, Bs, acc, tid);
         uint64_t hit = join_hits(acc, ra0, rb0, n, thr, tq, te, true);
         if (!__syncthreads_or(hit != 0ull)) continue;
         const bool diag = ta == tb;

@@ -10,7 +10,9 @@ selection.  Only top_n ids / scores travel back.  Both work on a row-sharded ent
 find_duplicates is an exact self-join of the embeddings on the device (amdkge_join_nearest / amdkge_join_radius,
 kge_join.hip); its tolerance bisection runs on the host over one nearest distance per row.  find_clusters runs DBSCAN -- its
 default, and the reference's documented use -- on the same join (amdkge_join_dbscan: neighbour count, union-find over the core
-rows, border pass; no pair list) and returns sklearn's labels; other clustering objects get the downloaded embeddings.
+rows, border pass; no pair list) and returns sklearn's labels; a KMeans of this module -- the estimator of the reference's
+documented find_clusters use, Lloyd's iterations with every restart batched into the same launches (amdkge_kmeans_lloyd,
+kge_kmeans.hip) -- gets the device matrix; other clustering objects get the downloaded embeddings.
 discover_facts (:21-271) and generate_candidates (:274-519) are the reference's procedure on the host -- the same legacy
 numpy draws in the same order, so equal inputs and seed give the reference's rows -- ranked by evaluate() on the device.
 discover_facts also runs strategy="exhaustive", which the reference documents and then rejects: every (s, o) pair of a
@@ -26,7 +28,7 @@ from . import _ffi
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["discover_facts", "generate_candidates", "query_topn", "find_nearest_neighbours", "find_duplicates", "find_clusters"]
+__all__ = ["discover_facts", "generate_candidates", "query_topn", "find_nearest_neighbours", "find_duplicates", "find_clusters", "KMeans"]
 
 
 def _known(indexer, values, type_of):
@@ -394,6 +396,195 @@ def dbscan_labels(core, parent, border):
     return torch.where(noise, torch.full_like(target, -1), rank[torch.where(noise, torch.zeros_like(target), target)])
 
 
+# ---------------------------------------------------------------------------------------------------- KMeans
+_STANDALONE = {}
+
+
+def _standalone_engine():
+    """The engine a KMeans uses outside find_clusters: a minimal KgeEngine on the current GPU, one per device (raises without one)."""
+    import torch
+
+    from .engine import KgeEngine
+
+    dev = torch.cuda.current_device() if torch.cuda.is_available() else -1
+    if dev not in _STANDALONE:
+        _STANDALONE[dev] = KgeEngine("DistMult", 4, 4, 2)   # (the tables are not used)
+    return _STANDALONE[dev]
+
+
+def _run_rng(seed, run):
+    """Run `run`'s generator: a function of (seed, run) alone, so a run does not depend on n_init."""
+    return np.random.default_rng(np.random.SeedSequence(seed, spawn_key=(run,)))
+
+
+class KMeans:
+    """Lloyd's k-means on the device, with sklearn.cluster.KMeans' interface: pass it to find_clusters in sklearn's place (the
+    reference's documented use is KMeans(n_clusters=6, n_init=100, max_iter=500)), or call fit / fit_predict / predict on a numpy
+    array or a device tensor anywhere -- a standalone call runs on the current GPU.  A sklearn.cluster.KMeans object given to
+    find_clusters still runs on the host; KMeans.from_sklearn(km) copies its parameters into one of these.
+
+    All n_init restarts advance in lock-step in the same kernel launches (engine.kmeans, kge_kmeans.hip): an assignment pass on the
+    self-join's distance tile, per-block sums of the rows by label in row order and a fixed-order reduction -- no floating-point
+    atomics, so equal inputs and seed give equal bits, whatever n_init.  Stop rules and `tol` (tol x the mean of the column
+    variances, computed on the device) are sklearn's: no label changed, or the centres moved by no more than the tolerance, or
+    max_iter.  cluster_centers_ (float32), labels_ (int32), inertia_, n_iter_ and n_features_in_ describe the restart of least
+    inertia (ties: the lowest restart).
+
+    init: "k-means++" (run r draws u = default_rng(SeedSequence(seed, spawn_key=(r,))).random(k); its first centre is row
+    floor(u_0 n), centre j the first row whose fp64 cumulative squared distance to the chosen centres exceeds u_j x the total, or row
+    floor(u_j n) when that total is 0), "random" (k distinct rows) or an array [k, d] (one run: n_init must be 1).
+
+    Differences from sklearn: a cluster that loses all its rows keeps its centre (sklearn moves it to a far row); k-means++ is the
+    plain D^2 sampling with one trial per step, not the greedy variant; Lloyd only (no elkan), no sample_weight.  With a different
+    seeding the restarts differ from sklearn's; from equal initial centres, and where no row lies within fp32 rounding of a tie
+    between two centres, labels and iteration counts are sklearn's."""
+
+    def __init__(self, n_clusters=8, *, init="k-means++", n_init=10, max_iter=300, tol=1e-4, random_state=None):
+        self.n_clusters = n_clusters
+        self.init = init
+        self.n_init = n_init
+        self.max_iter = max_iter
+        self.tol = tol
+        self.random_state = random_state
+
+    @classmethod
+    def from_sklearn(cls, km):
+        """A device KMeans with the six parameters of the sklearn.cluster.KMeans object km (algorithm="elkan", a callable init and
+        a RandomState object are refused; n_init="auto" becomes sklearn's value for it: 1 for k-means++ or an array, 10 for random)."""
+        if getattr(km, "algorithm", "lloyd") not in ("lloyd", "auto", "full"):
+            raise ValueError("KMeans.from_sklearn: algorithm=%r is not supported (Lloyd only)" % (km.algorithm,))
+        if callable(km.init):
+            raise ValueError("KMeans.from_sklearn: a callable init is not supported")
+        n_init = km.n_init
+        if isinstance(n_init, str):
+            if n_init != "auto":
+                raise ValueError("KMeans.from_sklearn: n_init=%r" % (n_init,))
+            n_init = 10 if isinstance(km.init, str) and km.init == "random" else 1
+        return cls(km.n_clusters, init=km.init, n_init=n_init, max_iter=km.max_iter, tol=km.tol, random_state=km.random_state)
+
+    # ------------------------------------------------------------------ parameters
+    def _check_params(self):
+        for name in ("n_clusters", "n_init", "max_iter"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError("KMeans: %s must be a positive integer, got %r" % (name, v))
+        if isinstance(self.tol, bool) or not isinstance(self.tol, (int, float, np.integer, np.floating)) or not self.tol >= 0:
+            raise ValueError("KMeans: tol must be a non-negative number, got %r" % (self.tol,))
+        if isinstance(self.init, str):
+            if self.init not in ("k-means++", "random"):
+                raise ValueError("KMeans: init must be 'k-means++', 'random' or an array [n_clusters, n_features], got %r" % (self.init,))
+        elif callable(self.init) or self.init is None:
+            raise ValueError("KMeans: init must be 'k-means++', 'random' or an array [n_clusters, n_features]")
+        elif self.n_init != 1:
+            raise ValueError("KMeans: an explicit init array is one run: n_init must be 1, got %r" % (self.n_init,))
+        rs = self.random_state
+        if rs is not None and (isinstance(rs, bool) or not isinstance(rs, (int, np.integer)) or rs < 0):
+            raise ValueError("KMeans: random_state must be None or a non-negative integer, got %r" % (rs,))
+
+    def _seed(self):
+        return int(self.random_state) if self.random_state is not None else int(np.random.SeedSequence().entropy)
+
+    @staticmethod
+    def _matrix(X, eng):
+        """X as an fp32 matrix on the engine's device (numpy arrays are uploaded, device tensors are used where they are)."""
+        import torch
+
+        t = X if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X))
+        if t.dim() != 2:
+            raise ValueError("KMeans: X must be a matrix [n_samples, n_features], got shape %s" % (tuple(t.shape),))
+        if not (t.is_floating_point() or t.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)):
+            raise ValueError("KMeans: X must be numeric, got %s" % (t.dtype,))
+        if int(t.shape[0]) == 0 or int(t.shape[1]) == 0:
+            raise ValueError("KMeans: X is empty (shape %s)" % (tuple(t.shape),))
+        t = t.to(getattr(eng, "device", t.device), torch.float32).contiguous()
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("KMeans: X contains NaN or infinity")
+        return t
+
+    # ------------------------------------------------------------------ initial centres
+    def _initial_centres(self, eng, X, seed):
+        """centres0 [runs, k, d] on X's device."""
+        import torch
+
+        n, d = int(X.shape[0]), int(X.shape[1])
+        k = int(self.n_clusters)
+        if not isinstance(self.init, str):
+            c = self.init if isinstance(self.init, torch.Tensor) else torch.as_tensor(np.asarray(self.init))
+            if tuple(c.shape) != (k, d):
+                raise ValueError("KMeans: init has shape %s, expected (%d, %d)" % (tuple(c.shape), k, d))
+            c = c.to(X.device, torch.float32)
+            if not bool(torch.isfinite(c).all()):
+                raise ValueError("KMeans: init contains NaN or infinity")
+            return c[None].contiguous()
+        runs = int(self.n_init)
+        if self.init == "random":
+            rows = np.stack([_run_rng(seed, r).choice(n, size=k, replace=False) for r in range(runs)])
+            return X[torch.as_tensor(rows, device=X.device)].contiguous()
+        return _kmeans_plusplus(eng, X, k, runs, seed)
+
+    # ------------------------------------------------------------------ sklearn's methods
+    def fit(self, X, y=None, engine=None):
+        """Fit on the rows of X (numpy array or device tensor).  engine: the KgeEngine to run on (find_clusters passes the model's)."""
+        import torch
+
+        self._check_params()
+        eng = engine if engine is not None else _standalone_engine()
+        Xd = self._matrix(X, eng)
+        n, d = int(Xd.shape[0]), int(Xd.shape[1])
+        if self.n_clusters > n:
+            raise ValueError("KMeans: n_samples=%d should be >= n_clusters=%d" % (n, self.n_clusters))
+        tol_abs = float(self.tol) * float(Xd.to(torch.float64).var(dim=0, unbiased=False).mean().item())
+        centres0 = self._initial_centres(eng, Xd, self._seed())
+        centres, labels, inertia, n_iter, _ = eng.kmeans(Xd, centres0, int(self.max_iter), tol_abs)
+        best = int(np.argmin(inertia.cpu().numpy()))   # (ties: the lowest run)
+        self.cluster_centers_ = centres[best].cpu().numpy().astype(np.float32)
+        self.labels_ = labels[best].cpu().numpy().astype(np.int32)
+        self.inertia_ = float(inertia[best].item())
+        self.n_iter_ = int(n_iter[best].item())
+        self.n_features_in_ = d
+        self._engine = eng
+        return self
+
+    def fit_predict(self, X, y=None):
+        return self.fit(X).labels_
+
+    def predict(self, X):
+        """The nearest of cluster_centers_ for every row of X (int32 numpy; equal distances: the lowest centre)."""
+        import torch
+
+        if not hasattr(self, "cluster_centers_"):
+            raise ValueError("KMeans: this instance is not fitted yet")
+        eng = getattr(self, "_engine", None) or _standalone_engine()
+        Xd = self._matrix(X, eng)
+        if int(Xd.shape[1]) != self.n_features_in_:
+            raise ValueError("KMeans: X has %d features, the fit had %d" % (int(Xd.shape[1]), self.n_features_in_))
+        labels, _ = eng.kmeans_assign(Xd, torch.as_tensor(self.cluster_centers_))
+        return labels.cpu().numpy().astype(np.int32)
+
+
+def _kmeans_plusplus(eng, X, k, runs, seed):
+    """k-means++ seeding of `runs` restarts at once -> centres [runs, k, d], every one a row of X.  Plain D^2 sampling, one trial per
+    step; the distance pass is engine.kmeans_assign on the newest centre of every run, the draw a cumulative sum and a search."""
+    import torch
+
+    n = int(X.shape[0])
+    u = np.stack([_run_rng(seed, r).random(k) for r in range(runs)])                      # [runs, k], host
+    pick = lambda col: np.minimum((u[:, col] * n).astype(np.int64), n - 1)                 # noqa: E731   row floor(u n)
+    rows = torch.as_tensor(pick(0), device=X.device)
+    chosen = [rows]
+    mind2 = None
+    for j in range(1, k):
+        _, m2 = eng.kmeans_assign(X, X[rows][:, None, :])
+        mind2 = m2 if mind2 is None else torch.minimum(mind2, m2)
+        cum = torch.cumsum(mind2.to(torch.float64), dim=1)
+        total = cum[:, -1]
+        target = torch.as_tensor(u[:, j], device=X.device) * total
+        rows = torch.searchsorted(cum, target[:, None], right=True).reshape(-1).clamp_(max=n - 1)   # the first row with cum > target
+        rows = torch.where(total > 0, rows, torch.as_tensor(pick(j), device=X.device))
+        chosen.append(rows)
+    return X[torch.stack(chosen, 1)].contiguous()
+
+
 def find_clusters(X, model, clustering_algorithm=None, mode="e"):
     """Cluster labels of the embeddings of X (:546-711): entities, relations or [s | p | o] per triple.  Same validation and
     embedding assembly as find_duplicates.
@@ -403,7 +594,10 @@ def find_clusters(X, model, clustering_algorithm=None, mode="e"):
     lock-free union-find over the core rows and a border pass on the exact self-join of find_duplicates, O(n) memory and no
     pair list; the thresholds are eps^2, or 2 eps between unit rows for cosine.  The labels are sklearn's, numbering included,
     and labels_, core_sample_indices_, components_ and n_features_in_ are set on the object as its fit_predict sets them.
-    Any other object, other DBSCAN parameters, an empty X or a cosine call with a row of (near) zero norm go through
+    A KMeans of this module (the reference's documented use of find_clusters clusters with KMeans) is fitted on the device matrix,
+    with no download: clustering_algorithm.fit(E, engine=model._engine); its labels_ come back as int64.  An empty X is a ValueError.
+    Any other object -- sklearn.cluster.KMeans objects among them: they run on the host with sklearn's exact labels; see
+    KMeans.from_sklearn --, other DBSCAN parameters, an empty X or a cosine call with a row of (near) zero norm go through
     clustering_algorithm.fit_predict on the downloaded embeddings, as in the reference."""
     import torch
 
@@ -413,6 +607,10 @@ def find_clusters(X, model, clustering_algorithm=None, mode="e"):
         clustering_algorithm = DBSCAN()
     model, X = _validate(X, model, mode, clustering_algorithm)
     E = _device_embeddings(model, X, mode)
+    if isinstance(clustering_algorithm, KMeans):
+        if int(E.shape[0]) == 0:
+            raise ValueError("find_clusters: X is empty")
+        return clustering_algorithm.fit(E, engine=model._engine).labels_.astype(np.int64)
     params = _device_dbscan_params(clustering_algorithm)
     if params is not None and int(E.shape[0]) > 0:
         eps, min_samples, cosine = params

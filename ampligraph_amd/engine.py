@@ -583,6 +583,69 @@ class KgeEngine:
                                           _stream()))
         return labels, core.view(torch.bool), n_clusters
 
+    # ------------------------------------------------------------------ discovery.KMeans (kge_kmeans.hip)
+    KMEANS_WORK_BYTES = 1 << 30   # bound of the Lloyd workspace (the per-block partial sums): more runs than fit go in groups
+
+    def kmeans_assign(self, X, centres):
+        """Nearest centre of every row of the fp32 device matrix X [n, d] (amdkge_kmeans_assign): centres [runs, k, d] ->
+        (labels int32 [runs, n], mind2 fp32 [runs, n]); centres [k, d] -> ([n], [n]).  The distance is the self-join's fp32 value,
+        equal distances go to the lowest centre.  On the device, no synchronisation."""
+        X = X.to(self.device, torch.float32).contiguous()
+        C3 = centres.to(self.device, torch.float32).contiguous()
+        single = C3.dim() == 2
+        if single:
+            C3 = C3[None]
+        n, d = int(X.shape[0]), int(X.shape[1])
+        runs, k = int(C3.shape[0]), int(C3.shape[1])
+        if int(C3.shape[2]) != d:
+            raise ValueError("centres have %d columns, X has %d" % (int(C3.shape[2]), d))
+        labels = torch.empty(runs, n, dtype=torch.int32, device=self.device)
+        mind2 = torch.empty(runs, n, dtype=torch.float32, device=self.device)
+        check(self.lib.amdkge_kmeans_assign(_ptr(X), n, d, _ptr(C3), k, runs, _ptr(labels), _ptr(mind2), _stream()))
+        return (labels[0], mind2[0]) if single else (labels, mind2)
+
+    def kmeans(self, X, centres0, max_iter, tol_abs, check_every=8):
+        """Lloyd's iterations of `runs` independent restarts over the rows of the fp32 device matrix X [n, d], from centres0 [runs, k, d]
+        (amdkge_kmeans_lloyd; the stop rules and the empty-cluster rule are stated in include/amdkge.h) -> (centres fp32 [runs, k, d],
+        labels int32 [runs, n], inertia fp64 [runs], n_iter int32 [runs], done int32 [runs]: 1 = no label changed, 2 = the centres
+        moved by no more than tol_abs, 0 = max_iter reached), all on the device.  The iterations are enqueued check_every at a time
+        (the last chunk shortened to max_iter); between chunks one read of the runs' state is the only synchronisation.  Runs go in
+        groups whose workspace stays under KMEANS_WORK_BYTES.  A run's result does not depend on runs, the grouping or check_every."""
+        X = X.to(self.device, torch.float32).contiguous()
+        C = centres0.to(self.device, torch.float32).clone().contiguous()
+        n, d = int(X.shape[0]), int(X.shape[1])
+        runs, k = int(C.shape[0]), int(C.shape[1])
+        if C.dim() != 3 or int(C.shape[2]) != d:
+            raise ValueError("centres0 must be [runs, k, %d]" % d)
+        max_iter, check_every = int(max_iter), max(int(check_every), 1)
+        labels = torch.full((runs, n), -1, dtype=torch.int32, device=self.device)
+        mind2 = torch.empty(runs, n, dtype=torch.float32, device=self.device)
+        state = torch.zeros(runs, 4, dtype=torch.int32, device=self.device)
+        inertia = torch.zeros(runs, dtype=torch.float64, device=self.device)
+        one = int(self.lib.amdkge_kmeans_workspace_bytes(n, d, k, 1))
+        if one < 0:
+            raise ValueError("kmeans: sizes out of range (n %d, d %d, k %d)" % (n, d, k))
+        group = max(1, min(runs, self.KMEANS_WORK_BYTES // max(one, 1)))
+        for r0 in range(0, runs, group):
+            g = min(group, runs - r0)
+            work = self._buf("kmeans_work", (max(int(self.lib.amdkge_kmeans_workspace_bytes(n, d, k, g)) // 8, 1),), torch.int64)
+            args = (_ptr(labels[r0:r0 + g]), _ptr(mind2[r0:r0 + g]), _ptr(state[r0:r0 + g]), _ptr(inertia[r0:r0 + g]), _ptr(work), _stream())
+
+            def lloyd(iters):
+                check(self.lib.amdkge_kmeans_lloyd(_ptr(X), n, d, _ptr(C[r0:r0 + g]), k, g, iters, float(tol_abs), *args))
+
+            it, done = 0, torch.zeros(g, dtype=torch.int32)
+            while it < max_iter:
+                step = min(check_every, max_iter - it)
+                lloyd(step)
+                it += step
+                done = state[r0:r0 + g, 1].cpu()
+                if bool((done != 0).all()):
+                    break
+            if n > 0 and bool((done != 1).any()):
+                lloyd(0)   # labels and inertia of the final centres (a strict stop has them already)
+        return C, labels, inertia, state[:, 0].contiguous(), state[:, 1].contiguous()
+
     # ------------------------------------------------------------------ discover_facts(strategy="exhaustive") (kge_discover.hip)
     _INT32_MIN = -(1 << 31)
 

@@ -465,6 +465,35 @@ int64_t amdkge_join_dbscan_workspace_bytes(int64_t n);
 int amdkge_join_dbscan(const float* d_x, int64_t n, int32_t d, double thr, int32_t min_samples, int32_t* d_labels, uint8_t* d_core,
                        int32_t* d_n_clusters, void* d_work, void* stream);
 
+/* Lloyd's k-means over the rows of d_x [n, d] (0 <= n <= 2^31 - 1, d >= 1, finite values): discovery.KMeans, the estimator of
+ * find_clusters' documented use (discovery/discovery.py:614-651: KMeans(n_clusters=6, n_init=100, max_iter=500)).  `runs` independent
+ * restarts share every launch: d_centres is [runs, k, d], d_labels (int32) and d_mind2 (fp32) are [runs, n].  A row's distance to a
+ * centre is the join's fp32 value above -- the fma chain over the columns, in column order, of (x - c)^2 --, the same bits for every
+ * tile width the centre count selects (8, 32 or 128 centres per tile).
+ * amdkge_kmeans_assign: d_labels[r][i] = argmin over c of d2(x_i, centre[r][c]) (equal distances: the lowest c) and, unless d_mind2 is
+ *   NULL, d_mind2[r][i] = that distance.  Stateless; also the distance pass of the k-means++ seeding and of predict().
+ * amdkge_kmeans_lloyd : enqueues `iters` iterations of every run whose done is 0.  One iteration: assign as above against the centres
+ *   as they are; centre[c] = the mean of its rows -- per block of rows_per_block(n) rows the fp32 sum in row order, the blocks' sums
+ *   added in block order, one IEEE divide by the count; a centre WITHOUT rows keeps its value (sklearn moves it to a far row) --; then
+ *   d_state [runs][4] int32 = {n_iter, done, changed, reserved}: n_iter += 1, changed = the rows whose label differs from the one
+ *   stored before (exact), done = 1 when n_iter > 1 and changed == 0, else done = 2 when shift2 = the fp64 sum of (new - old)^2 over
+ *   the centres <= tol_abs; d_inertia[r] (fp64) = the fixed-order fp64 sum of the iteration's mind2.  That is sklearn's Lloyd loop.
+ *   After done == 1 labels, mind2 and inertia belong to the final centres (equal labels give bit-equal centres).  After done == 2,
+ *   or with done == 0 at the caller's iteration limit, they belong to the centres BEFORE the last update: a call with iters == 0
+ *   refreshes labels, mind2 and inertia of every run whose done != 1 from the centres as they are and changes nothing else.
+ *   The caller zeroes d_state and sets d_labels to -1 before the first call.  No floating-point atomics and no order that depends on
+ *   `runs`, on timing or on how the iterations are spread over calls: run r of any call sequence gives the bits of run r alone.
+ *   d_work holds amdkge_kmeans_workspace_bytes(n, d, k, runs) bytes (-1 for bad sizes or an overflow, 0 for n == 0): O(runs n / 128)
+ *   plus the partial sums [runs][blocks <= 256][k][d] fp32, every part on an 8-byte boundary: [count accumulators int32 runs k |
+ *   change accumulators int32 runs | the last iteration's counts int32 [runs][k] | ...].  Asynchronous on `stream`.
+ * Both fail with AMDKGE_EINVAL before touching the device for NULL pointers, n outside 0 .. 2^31 - 1, d, k or runs < 1, iters < 0 and
+ * a NaN or negative tol_abs; n == 0 is a no-op. */
+int64_t amdkge_kmeans_workspace_bytes(int64_t n, int32_t d, int32_t k, int32_t runs);
+int amdkge_kmeans_assign(const float* d_x, int64_t n, int32_t d, const float* d_centres, int32_t k, int32_t runs, int32_t* d_labels,
+                         float* d_mind2, void* stream);
+int amdkge_kmeans_lloyd(const float* d_x, int64_t n, int32_t d, float* d_centres, int32_t k, int32_t runs, int32_t iters, double tol_abs,
+                        int32_t* d_labels, float* d_mind2, int32_t* d_state, double* d_inertia, void* d_work, void* stream);
+
 /* discover_facts(strategy = "exhaustive") (discovery/discovery.py:21-271 documents the strategy and rejects its name): the selection
  * behind a 1-vs-all score block.  d_scores [n, m] (leading dimension ld) holds amdkge_corruption_scores' values of the query rows
  * d_queries [n, 3] for `side` over ALL entities (column j = entity j); d_flt_lo / d_flt_hi / d_flt_ids are the rows' filter ranges
