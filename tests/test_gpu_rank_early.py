@@ -1,6 +1,8 @@
 """The exact early exit of evaluate()'s count pass for the distance models (kge_rank_tile.hip, kge_rank_early.h): counts bit-identical to the plain
-tile kernels (amdkge_set_rank_kernel(1): rank_count_kernel / rank_rot_kernel, themselves held bit for bit to the declared-order
-oracle in test_gpu_fullsize) -- on untrained tables (nothing is decided early), on tables where the positives score near the
+tile kernels (amdkge_set_rank_kernel(1): rank_count_kernel / rank_rot_kernel; they and the early exit are held bit for bit to the
+declared-order oracle in test_gpu_rank_widths_oracle -- TransE k = 37, 50, 60, 64, 101, 200 and RotatE k = 50, 63, 64, 101, 200: below, at
+and above the exit's 64 units, padded and odd widths, on this file's "gaussian", "trained" and "ties" tables -- and at full size in
+test_gpu_fullsize) -- on untrained tables (nothing is decided early), on tables where the positives score near the
 top (almost everything is), with ties, zeros, denormals, huge / inf / NaN rows, RotatE units of modulus exactly 0, candidate
 subsets and ranges, and an overflowing hand-over list."""
 import ctypes as C

@@ -1,7 +1,11 @@
 """The int8 screening pass of evaluate() (kge_rank_screen.hip, kge_rank_screen.h): counts bit-identical to the exact fp32 kernels -- it only decides
-WHICH comparisons need the exact chain.  Against the unscreened pipelined MFMA kernel (amdkge_set_rank_kernel(3)), itself held
-bit for bit to the declared-order oracle in test_gpu_fullsize, on real-valued tables, tables with wild dynamic range, ties,
-inf / NaN rows, candidate subsets and ranges; and the recheck statistics (a fraction of a per cent of the comparisons)."""
+WHICH comparisons need the exact chain.  Against the unscreened pipelined MFMA kernel (amdkge_set_rank_kernel(3)), on real-valued
+tables, tables with wild dynamic range, ties, inf / NaN rows, candidate subsets and ranges; and the recheck statistics (a fraction
+of a per cent of the comparisons).  That anchor, and the screened pass itself, are held bit for bit to the declared-order oracle
+in test_gpu_rank_widths_oracle -- every slab count 1 .. 14, 19, 22 and 64 (all ten rank_screen_kernel_r instantiations, from a
+one-plane and a two-halves model; rank_screen_kernel_v1 elsewhere), padded halves, unit counts that are no multiple of 4, kernel
+r's 16-tile hand-over boundary, on the "gaussian" and "ties" families -- and at full size in test_gpu_fullsize (13- and 22-slab
+rows).  The wild and non-finite families stay here: the oracle's semantics on inf / NaN are pinned by nothing."""
 import numpy as np
 import pytest
 import torch

@@ -24,13 +24,15 @@ def test_wave_sum_is_the_documented_tree():
         assert got[r] == want
 
 
-@pytest.mark.parametrize("mode,planes", [(RO.MODE_DOT, 1), (RO.MODE_L1, 1), (RO.MODE_L1_SUB, 1), (RO.MODE_ROT_O, 2), (RO.MODE_ROT_S, 2)])
-def test_c_chain_equals_numpy_chain(mode, planes):
+CHAIN_MODES = [(RO.MODE_DOT, 1), (RO.MODE_L1, 1), (RO.MODE_L1_SUB, 1), (RO.MODE_ROT_O, 2), (RO.MODE_ROT_S, 2)]
+
+
+def _c_chain_equals_numpy_chain(mode, planes, scale):
     rng = np.random.default_rng(mode)
     n, m, U = 7, 150, 37                      # ragged entity tile (150 = 2 * 64 + 22)
     qplanes = 4 if mode == RO.MODE_ROT_S else planes
-    Q = (rng.normal(size=(n, qplanes * U)) * 0.7).astype(np.float32)
-    E = (rng.normal(size=(m, planes * U)) * 0.7).astype(np.float32)
+    Q = (rng.normal(size=(n, qplanes * U)) * scale).astype(np.float32)
+    E = (rng.normal(size=(m, planes * U)) * scale).astype(np.float32)
     plane = U if planes == 2 else 0
     ref = O.quantise(RO.chain_scores_numpy(mode, Q, E, U, plane, -1.0 if mode != RO.MODE_DOT else 1.0))
     qpos = np.sort(ref, axis=1)[:, m // 2].astype(np.int32)   # a threshold in the middle of each query's scores
@@ -47,6 +49,22 @@ def test_c_chain_equals_numpy_chain(mode, planes):
     RO.lib().ro_pair_qscores(mode, RO._ptr(Q), Q.shape[1], plane, RO._ptr(E), E.shape[1], plane, U, RO._ptr(pq), RO._ptr(pe), 40,
                              -1.0 if mode != RO.MODE_DOT else 1.0, RO._ptr(out))
     assert np.array_equal(out, ref[pq, pe])
+    return ref
+
+
+@pytest.mark.parametrize("mode,planes", CHAIN_MODES)
+def test_c_chain_equals_numpy_chain(mode, planes):
+    _c_chain_equals_numpy_chain(mode, planes, 0.7)
+
+
+@pytest.mark.parametrize("mode,planes", CHAIN_MODES)
+def test_c_chain_equals_numpy_chain_where_every_ulp_shows(mode, planes):
+    """At scores of a few units int32(score * 1000) moves only when a score crosses a multiple of 0.001: a chain walked in another
+    order, or with a rounding point more, differs by an ulp or two (~1e-7) and passes the comparison above in most modes.  Inputs
+    100 x larger put the quantised scores at 2^21 and beyond (and well inside int32), where an ulp of a score is an eighth of a
+    quantisation step or more: over the 1 050 scores of a case a chain that differs anywhere shows, in every mode."""
+    ref = _c_chain_equals_numpy_chain(mode, planes, 100.0)
+    assert np.median(np.abs(ref.astype(np.int64))) > 2 ** 21 and np.abs(ref.astype(np.int64)).max() < 2 ** 30
 
 
 def test_fma_emulation_catches_double_rounding():
