@@ -7,7 +7,7 @@ so the tables can instead be cut by COLUMNS: rank r holds units [r k / W, (r + 1
 and im slices of the same units for the complex models) with the optimizer state of those columns, EVERY rank processes the WHOLE
 global batch on its slice, and the one exchange of a step is the all-reduce of the B (1 + eta) partial score sums -- 6.7 MB at
 B = 80 000, eta = 20, whatever the table size.  Loss, backward, gradient merge, regulariser and optimizer are element-wise in the
-columns and stay local (kge_train_cols.h).  What a step replaces is ScoringBasedEmbeddingModel.train_step
+columns and stay local (kge_train_cols.hip).  What a step replaces is ScoringBasedEmbeddingModel.train_step
 (ScoringBasedEmbeddingModel.py:370-429) on one global batch; the reference has no multi-device path.  W ranks compute one GPU's
 step up to fp32 summation order: every rank draws the same Philox corruptions for the whole batch.
 """

@@ -225,12 +225,16 @@ __device__ __forceinline__ float sqrt_rn(float x) {
     return fmaf(r, h, y);
 }
 
+// (ROTATE_FAST_FORMS records which variant this unit compiled: kge_train_common.h, the one place that defines KGE_FAST_ROTATE, asserts
+// on it, so a training unit that included this header too early does not compile)
 #ifdef KGE_FAST_ROTATE
 #define KGE_SQRT(x) __builtin_amdgcn_sqrtf(x)
 #define KGE_DIV(a, b) ((a) * __builtin_amdgcn_rcpf(b))
+constexpr bool ROTATE_FAST_FORMS = true;
 #else
 #define KGE_SQRT(x) sqrtf(x)
 #define KGE_DIV(a, b) ((a) / (b))
+constexpr bool ROTATE_FAST_FORMS = false;
 #endif
 
 // EXACT (the deterministic train mode): IEEE square root and division -- correctly rounded, the same bits as numpy's -- instead

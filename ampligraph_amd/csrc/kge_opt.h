@@ -1,5 +1,5 @@
 // Element-wise optimizer + regulariser arithmetic shared by the dense sweep (kge_opt.hip) and the
-// owner-computes backward (kge_train_tiled.hip).  Keras *legacy* update rules, see kge_opt.hip.
+// owner-computes backward (kge_train_tile.hip, kge_train_direct.hip).  Keras *legacy* update rules, see kge_opt.hip.
 #pragma once
 #include "kge_host.h"
 

@@ -898,7 +898,7 @@ extern "C" int amdkge_session_group_rank(amdkge_session_group* g, const int32_t*
 
 
 // =====================================================================================================================================
-// AMDKGE_GROUP_COLS -- every table COLUMN-sharded over the replicas of a group (kge_train_cols.h).
+// AMDKGE_GROUP_COLS -- every table COLUMN-sharded over the replicas of a group (kge_train_cols.hip).
 // Replica d holds units [d k / W, (d + 1) k / W) of EVERY entity and relation row (the re and im slices of the same units for the
 // complex models) with the optimizer state of those columns, and processes the WHOLE batch on its slice: the scores are sums over
 // units, so the one exchange of a step is the all-reduce of B (1 + eta) partial sums -- 6.7 MB at B = 80 000, eta = 20, whatever

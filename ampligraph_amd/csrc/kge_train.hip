@@ -15,13 +15,6 @@
 #include <mutex>
 #include <unordered_map>
 
-// RotatE's modulus and its reciprocal in the TRAINING kernels use the hardware v_sqrt_f32 / v_rcp_f32 (1 ulp) instead of the
-// correctly rounded libm sequences: the fused kernels are bound by exactly these on RotatE (measured 1.26x on the step);
-// loss and gradients stay far inside the 1e-5 relative tolerance of the parity tests.  predict() (kge_score.hip) keeps the
-// exact forms; the rank kernels have their own rank_sqrt.  Device functions are inlined per kernel, so the two variants of
-// score_unit / grad_unit never meet at link time.
-#define KGE_FAST_ROTATE 1
-
 #include "kge_train_kernel.h"
 
 namespace kge {
@@ -113,8 +106,8 @@ static int launch_train_w(TrainArgs& a, int CH, hipStream_t st) {
     const unsigned grid = (unsigned)((a.B + slots - 1) / slots);
 #define KGE_LAUNCH(CC) do { \
         if (shmem > 64 * 1024) { \
-            if (hipError_t e = hipFuncSetAttribute((const void*)train_fwdbwd_kernel<MODEL, VEC, W, CC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) \
-                return set_error_hip(e, "hipFuncSetAttribute(train_fwdbwd)"); \
+            static PerDeviceOnce attr;   /* one per instantiation */ \
+            if (int rc = ensure_dynamic_lds(attr, {(const void*)train_fwdbwd_kernel<MODEL, VEC, W, CC>}, 160 * 1024, "train_fwdbwd")) return rc; \
         } \
         hipLaunchKernelGGL((train_fwdbwd_kernel<MODEL, VEC, W, CC>), dim3(grid), dim3(256), shmem, st, a); } while (0)
     switch (CH) {
@@ -207,13 +200,9 @@ extern "C" int amdkge_train_fwdbwd(const amdkge_model* m, const amdkge_loss* los
     a.loss_parts = loss_parts_for(d_loss_sum);
     if (!a.loss_parts) return set_error(AMDKGE_ENOMEM, "train: cannot allocate the loss scratch (or 1 024 distinct loss accumulators are already registered: amdkge_release_scratch() frees the library's scratch of finished jobs)");
     int rc;
-    switch (m->scoring_type) {
-        case AMDKGE_TRANSE: rc = launch_train_m<AMDKGE_TRANSE>(a, st); break;
-        case AMDKGE_DISTMULT: rc = launch_train_m<AMDKGE_DISTMULT>(a, st); break;
-        case AMDKGE_COMPLEX: rc = launch_train_m<AMDKGE_COMPLEX>(a, st); break;
-        case AMDKGE_HOLE: rc = launch_train_m<AMDKGE_COMPLEX>(a, st); break;  // HolE = ComplEx * fp32(2/k), via ModelConst
-        default: rc = launch_train_m<AMDKGE_ROTATE>(a, st); break;
-    }
+#define KGE_RUN(MODEL) rc = launch_train_m<MODEL>(a, st)
+    KGE_MODEL_DISPATCH(m->scoring_type, KGE_RUN)
+#undef KGE_RUN
     if (rc) return rc;
     hipLaunchKernelGGL(loss_fold_kernel, dim3(1), dim3(64), 0, st, a.loss_parts, d_loss_sum);
     return check_launch("loss_fold");

@@ -16,8 +16,9 @@
 // half), so a positive is handled by a GROUP of G = 16 / 32 / 64 lanes (one quad of each half per lane), four / two / one positives
 // per wave -- a whole wave per 13-quad row would idle 80 % of its lanes.  The slice table (C2 at W = 8: 14 505 x 416 B = 6 MB) is
 // L2-resident on every XCD, which is where the design gets its speed from (scripts/xcd_slice_bench.hip: 15.1 TB/s of gathers).
-// Included by kge_train_tiled.hip (shares TrainArgs / StageEntry / tile_of_row with the forward kernel).
-#pragma once
+// Shares TrainArgs / StageEntry / tile_of_row with the forward kernel (kge_train_common.h); kge_train_tiled.hip launches C through
+// run_cols_stage (kge_train_tiled.h), A and B have their own entry points below.
+#include "kge_train_tiled.h"
 
 namespace kge {
 
@@ -35,7 +36,7 @@ __device__ __forceinline__ void wave_lds_sync() {   // LDS operations of one wav
 }
 
 struct ColsArgs {
-    TrainArgs t;          // tables, triples, sampling, geometry, staging outputs (see kge_train_kernel.h)
+    TrainArgs t;          // tables, triples, sampling, geometry, staging outputs (see kge_train_common.h)
     float* scores;        // A: out, partial sums [B] positives then [eta][B] corruptions; C: in, dL/dscore in the same layout
 };
 
@@ -381,4 +382,75 @@ __global__ __launch_bounds__(256) void cols_stage_kernel(ColsArgs ca) {
 __host__ inline size_t cols_scores_lds(int G, int eta) { return (size_t)(256 / G) * 2 * eta * 4; }
 __host__ inline size_t cols_stage_lds(int G, int eta, int K) { return (size_t)(256 / G) * (2 * (size_t)eta * 4 + (size_t)K * 4 + 4); }
 
+// C: the coefficients are given, the staging protocol is the forward kernel's
+template <int MODEL, int G>
+static int launch_cols_stage(const TrainArgs& f, float* given, hipStream_t st) {
+    ColsArgs ca{f, given};
+    const size_t sh = cols_stage_lds(G, f.eta, f.K);
+    if (sh > 64 * 1024) return set_error(AMDKGE_EUNSUPPORTED, "train_step_tiled(GIVEN_COEFFS): eta too large for the column-sharded stage kernel");
+    const unsigned grid = (unsigned)((f.B + 256 / G - 1) / (256 / G));
+    if (grid) hipLaunchKernelGGL((cols_stage_kernel<MODEL, G>), dim3(grid), dim3(256), sh, st, ca);
+    return check_launch("cols_stage");
+}
+
+int run_cols_stage(int model, const TrainArgs& f, float* given, hipStream_t st) {
+#define KGE_RUN(MODEL) return f.nq <= 16 ? launch_cols_stage<MODEL, 16>(f, given, st) : (f.nq <= 32 ? launch_cols_stage<MODEL, 32>(f, given, st) : launch_cols_stage<MODEL, 64>(f, given, st))
+    KGE_MODEL_DISPATCH(model, KGE_RUN)
+#undef KGE_RUN
+}
+
+// ---- phases A and B ------------------------------------------------------------------------------------------------------------------
+template <int MODEL>
+static int launch_cols_scores(const ColsArgs& ca, hipStream_t st) {
+    const TrainArgs& f = ca.t;
+    const int G = f.nq <= 16 ? 16 : (f.nq <= 32 ? 32 : 64);
+    const size_t sh = cols_scores_lds(G, f.eta);
+    if (sh > 64 * 1024) return set_error(AMDKGE_EUNSUPPORTED, "cols_partial_scores: eta too large");
+    const unsigned grid = (unsigned)((f.B + 256 / G - 1) / (256 / G));
+    if (G == 16) hipLaunchKernelGGL((cols_scores_kernel<MODEL, 16>), dim3(grid), dim3(256), sh, st, ca);
+    else if (G == 32) hipLaunchKernelGGL((cols_scores_kernel<MODEL, 32>), dim3(grid), dim3(256), sh, st, ca);
+    else hipLaunchKernelGGL((cols_scores_kernel<MODEL, 64>), dim3(grid), dim3(256), sh, st, ca);
+    return check_launch("cols_scores");
+}
+
 }  // namespace kge
+
+using namespace kge;
+
+extern "C" int amdkge_cols_partial_scores(const amdkge_model* m, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int32_t eta,
+                                          int64_t sample_base, int64_t sample_range, uint64_t seed, uint64_t step, int64_t row_offset, int64_t b_global,
+                                          const int32_t* d_neg_override, float* d_scores, void* stream) {
+    if (int rc = validate_model(m)) return rc;
+    if (B < 0 || B >= (1ll << 30) || eta < 1) return set_error(AMDKGE_EINVAL, "cols_partial_scores: B must be in [0, 2^30) and eta >= 1");
+    if (B == 0) return AMDKGE_OK;
+    if (!d_ent || !d_rel || !d_triples || !d_scores) return set_error(AMDKGE_EINVAL, "cols_partial_scores: NULL pointer");
+    const int ks = stored_k(m), K = row_floats(m);
+    if (ks % 4 != 0 || ks > 256) return set_error(AMDKGE_EUNSUPPORTED, "cols_partial_scores: column slices are stored padded (k_pad = amdkge_padded_k(k)) and hold up to 256 units per half");
+    if (!d_neg_override && (sample_range <= 0 || sample_range > 0xFFFFFFFFll || sample_base < 0 || sample_base + sample_range > m->n_ents))
+        return set_error(AMDKGE_EINVAL, "cols_partial_scores: sampling range outside the entity table");
+    ColsArgs ca{};
+    TrainArgs& f = ca.t;
+    f.ent = d_ent; f.rel = d_rel; f.triples = d_triples; f.neg_override = d_neg_override;
+    f.B = B; f.eta = eta; f.k = ks; f.K = K; f.k_live = m->k; f.nq = ks / 4;
+    f.sc = SampleCfg{sample_base, (uint32_t)sample_range, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, (uint32_t)(step >> 32), row_offset,
+                     b_global > 0 ? b_global : B};
+    f.mc = model_const(m);
+    ca.scores = d_scores;
+    // (HolE: the scale is applied to the complete sum, in amdkge_cols_loss)
+#define KGE_RUN(MODEL) return launch_cols_scores<MODEL>(ca, (hipStream_t)stream)
+    KGE_MODEL_DISPATCH(m->scoring_type, KGE_RUN)
+#undef KGE_RUN
+}
+
+extern "C" int amdkge_cols_loss(const amdkge_model* m, const amdkge_loss* loss, float* d_scores, int64_t B, int32_t eta, double* d_loss_sum, void* stream) {
+    if (int rc = validate_model(m)) return rc;
+    if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "cols_loss: unknown loss kind");
+    if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "cols_loss: FocusE is not offered in the column-sharded step");
+    if (B < 0 || eta < 1) return set_error(AMDKGE_EINVAL, "cols_loss: bad sizes");
+    if (B == 0) return AMDKGE_OK;
+    if (!d_scores) return set_error(AMDKGE_EINVAL, "cols_loss: NULL pointer");
+    const ModelConst mc = model_const(m);
+    const unsigned grid = (unsigned)((B + 255) / 256 < 1024 ? (B + 255) / 256 : 1024);
+    hipLaunchKernelGGL(cols_loss_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_scores, B, (int)eta, *loss, mc.score_sign * mc.score_scale, d_loss_sum);
+    return check_launch("cols_loss");
+}

@@ -1,5 +1,6 @@
 // Owner-computes tile pass for LONG rows (more than 128 quads per half: K > 2 KB, the C5 row width), "row direct" form.
-// Included by kge_train_tiled.hip behind tile_backward_kernel, whose arguments (TileArgs), bucket layout and bookkeeping it shares.
+// A unit of the owner-computes step (kge_train_tiled.hip); it shares tile_backward_kernel's arguments (TileArgs, kge_train_tiled.h),
+// bucket layout and bookkeeping (kge_train_tile.hip).
 //
 // Why a second form.  tile_backward_kernel keeps a tile's gradient rows in LDS, adds every bucket entry to them and then
 // flushes the rows through the optimizer.  With 8 KB rows a tile holds 18 rows, a CU runs ONE tile at a time (150 KB of LDS),
@@ -23,7 +24,7 @@
 // Same arithmetic per entry and per element as tile_backward_kernel (add_entry / opt_elem): the sums differ only in the order
 // in which a row's entries are added (sorted by local row, bucket order within a row), i.e. by fp32 summation order.
 // Not used in deterministic mode (that one sorts by content in tile_backward_kernel) or when a bucket could outgrow the LDS list.
-#pragma once
+#include "kge_train_tiled.h"
 
 namespace kge {
 
@@ -329,6 +330,21 @@ __global__ __launch_bounds__(GW * 64) void tile_direct_kernel(TileArgs a) {
     }
     __syncthreads();
     if (s_last && wg == 0 && a.apply_update && a.reg_loss && a.opt.lam != 0.f) fold_loss_parts(a.loss_parts, a.reg_loss, lane, 1);
+}
+
+template <int MODEL>
+static int launch_direct(const TileArgs& te, hipStream_t st) {
+    const size_t sh = direct_lds_bytes(te.cap, te.tile_rows);
+    if (te.nq <= 128) return set_error(AMDKGE_EUNSUPPORTED, "tile_direct: rows of up to 128 quads per half take the LDS-accumulator tiles");
+    if (te.gw == 4) hipLaunchKernelGGL((tile_direct_kernel<MODEL, 4>), dim3(te.n_tiles + te.rel_blocks), dim3(256), sh, st, te);
+    else hipLaunchKernelGGL((tile_direct_kernel<MODEL, 8>), dim3(te.n_tiles + te.rel_blocks), dim3(512), sh, st, te);
+    return check_launch("tile_direct");
+}
+
+int run_tile_direct(int model, const TileArgs& te, hipStream_t st) {
+#define KGE_RUN(MODEL) return launch_direct<MODEL>(te, st)
+    KGE_MODEL_DISPATCH(model, KGE_RUN)
+#undef KGE_RUN
 }
 
 }  // namespace kge

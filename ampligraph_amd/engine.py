@@ -240,7 +240,7 @@ class KgeEngine:
         finally:
             opt_desc.reg_p = p0
 
-    # ------------------------------------------------------------------ column-sharded step (amdkge_cols_*, kge_train_cols.h)
+    # ------------------------------------------------------------------ column-sharded step (amdkge_cols_*, kge_train_cols.hip)
     def cols_partial_scores(self, triples, eta, seed, step, sample_base=0, sample_range=None, row_offset=0, b_global=0,
                             neg_override=None, out=None):
         """Phase A: this slice's partial score sums of B positives and their eta corruptions -> float32 [B (1 + eta)] (positives,

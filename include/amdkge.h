@@ -250,7 +250,7 @@ int amdkge_opt_step(const amdkge_opt* opt, float* d_x, float* d_grad, float* d_s
 #define AMDKGE_TILED_HOT_ROWS 4
 /* AMDKGE_TILED_GIVEN_COEFFS (ABI 5): phase C of the COLUMN-SHARDED step (amdkge_cols_* below).  d_pos_scores / d_neg_scores are
  * INPUTS: dL/dscore of the positives [B] and of the corruptions [eta][B] in ONE buffer (d_neg_scores == d_pos_scores + B), as
- * amdkge_cols_loss left them; the forward kernel is replaced by the stage kernel of kge_train_cols.h (gradient rows of the slice
+ * amdkge_cols_loss left them; the forward kernel is replaced by the stage kernel of kge_train_cols.hip (gradient rows of the slice
  * from the given coefficients, same staging protocol), the tile pass and the optimizer run unchanged on the slice.  d_loss_sum
  * receives nothing from this call (the data loss is amdkge_cols_loss's), d_reg_loss the slice's regulariser terms.  Excludes
  * DETERMINISTIC / POS_ATOMIC / HOT_ROWS and FocusE; stored slices of up to 256 units per half. */
@@ -265,7 +265,7 @@ int amdkge_opt_step(const amdkge_opt* opt, float* d_x, float* d_grad, float* d_s
  * replayed on a workspace no step of another geometry (other B / eta / flags) has used since the capture. */
 int64_t amdkge_train_tiled_workspace_bytes(const amdkge_model* m, int64_t B, int32_t eta);
 /* Long rows (stored half width > 512 units, i.e. rows beyond 2 KB: the C5 row width) take the ROW-DIRECT form of the tile pass by
- * default (kge_tile_direct.h: one wave group per tile, its bucket sorted in LDS, every row folded in registers and updated in
+ * default (kge_train_direct.hip: one wave group per tile, its bucket sorted in LDS, every row folded in registers and updated in
  * one go -- x read once, several tiles resident per CU).  0 keeps them on the LDS-accumulator kernel (A/B measurements, tests);
  * process-wide, both forms compute the same step up to fp32 summation order.  A tile whose entries outgrow the direct form's LDS
  * list rescans the spill in memory (slower, complete): no status is raised for it.  (Any non-zero value means 1: round 5's value 2,
@@ -287,7 +287,7 @@ int amdkge_train_step_tiled(const amdkge_model* m, const amdkge_loss* loss, cons
                             double* d_loss_sum, double* d_reg_loss,
                             float* d_pos_scores, float* d_neg_scores, void* d_work, void* stream);
 
-/* COLUMN-SHARDED train step (ABI 5; kge_train_cols.h): every GPU holds k / W units of every row (m->k = k / W,
+/* COLUMN-SHARDED train step (ABI 5; kge_train_cols.hip): every GPU holds k / W units of every row (m->k = k / W,
  * m->k_full = k) and processes ALL positives of the global batch on its slice -- what replaces
  * ScoringBasedEmbeddingModel.train_step (ScoringBasedEmbeddingModel.py:370-429) when the tables are sharded by COLUMNS.  All five
  * scores are sums over units, so one exchange completes them:
@@ -654,7 +654,7 @@ int amdkge_session_group_info(const amdkge_session_group* g, int32_t* uses_rccl,
  * AMDKGE_TILED_DETERMINISTIC is not offered for row-sharded groups (AMDKGE_EUNSUPPORTED). */
 int amdkge_session_group_create_rows(const amdkge_session_config* cfg, const int32_t* devices, int32_t n_gpus, int32_t flags,
                                      int64_t max_batch, amdkge_session_group** out);
-/* COLUMN-SHARDED group (ABI 5; kge_train_cols.h): for tables that FIT every GPU (BASELINE configs[1] - [3]) and
+/* COLUMN-SHARDED group (ABI 5; kge_train_cols.hip): for tables that FIT every GPU (BASELINE configs[1] - [3]) and
  * whose merge bounds data-parallel scaling.  cfg->model is the WHOLE model; replica d holds units [d k / W, (d + 1) k / W) of every
  * entity and relation row (k % n_gpus == 0; the re and im slices of the same units) with the optimizer state of those columns, and
  * every replica processes the WHOLE batch of a step on its slice.  amdkge_session_group_train_step: partial score sums

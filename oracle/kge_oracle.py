@@ -599,7 +599,7 @@ def touched_rows(n_ents, pos, negs, dN, scale=1.0, nonfinite=None):
     the difference VERDICT r4 #9 asked about: RotatE k = 1000 under rules without damping reaches that regime at the third step
     (profiles/r05a_diag_rotate_rules2.jsonl: the 12 rows the fp64 mask moved and the engine did not all had |g| < 4e-39).
     Round 6: a NaN coefficient is an entry (the kernel's test is `!(|g| < tiny)`), and so is the masked zero of a corruption whose
-    score -- or the hinge argument it enters -- is not finite (`nonfinite`, (B*eta,) bool; kge_train_kernel.h masked_zero): the
+    score -- or the hinge argument it enters -- is not finite (`nonfinite`, (B*eta,) bool; kge_train_common.h masked_zero): the
     reference multiplies that zero by the score's Jacobian, 0 * NaN = NaN."""
     pos, negs = np.asarray(pos, dtype=np.int64), np.asarray(negs, dtype=np.int64)
     mask = np.zeros(n_ents, dtype=bool)

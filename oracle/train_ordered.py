@@ -6,7 +6,7 @@ accumulation.  For the models that are smooth in their parameters that is enough
 discontinuity): a score that differs in its last bit flips a hinge term, an embedding that differs in its last bit flips a sign,
 and two fp32 evaluations of one schedule in different summation orders part (tests/test_gpu_learning.py measures it).  As for
 the ranks (oracle/rank_ordered.py) ONE order has to be fixed for "identical" to be testable -- the one the train kernels declare
-(ampligraph_amd/csrc/kge_train_kernel.h, kge_train_tiled.hip, kge_opt.h):
+(ampligraph_amd/csrc/kge_train_kernel.h, kge_train_tile.hip, kge_train_tiled.hip, kge_opt.h):
 
   * d = fl(fl(s + p) - o) per unit (TransE.py:51-53), for a corruption fl(fl(s + p) - e) (object replaced) or
     fl(fl(e + p) - o) (subject replaced), rounded where the reference rounds;
@@ -534,7 +534,7 @@ def fmaf32(a, b, c):
 def _pf_of(model, nq):
     """Rows in flight per group of the forward kernel (kge_train_kernel.h: PF) for a row of nq quads per component: the launch
     geometry is one wave per positive with 1 (nq <= 64) or 2 (<= 128) quads per component and lane, or four waves per positive
-    with 1 (<= 256) or 2 quads (kge_train_tiled.hip run_tiled)."""
+    with 1 (<= 256) or 2 quads (kge_train_stage.hip forward_by_width)."""
     ch = 1 if nq <= 64 else (2 if nq <= 128 else (1 if nq <= 256 else 2))
     nc = 1 if model in ("DistMult", "TransE") else 2
     return (3 if model == "RotatE" else 6) if ch * nc * 4 <= 8 else 2

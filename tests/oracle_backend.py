@@ -215,7 +215,7 @@ class OracleEngine:
         self.g_rel += torch.as_tensor(Gr.astype(np.float32))
         self.loss_acc[0] += float(total)
 
-    # ---- column-sharded step (kge_train_cols.h): the slice embedded in zero columns of the whole width scores and differentiates
+    # ---- column-sharded step (kge_train_cols.hip): the slice embedded in zero columns of the whole width scores and differentiates
     #      like the slice of the whole model (every score is a sum over units; HolE's 2 / k and RotatE's phase normaliser are the
     #      whole model's) ----
     def _embed(self, a):

@@ -1,4 +1,4 @@
-"""The COLUMN-SHARDED train step (amdkge_cols_*, AMDKGE_TILED_GIVEN_COEFFS, amdkge_session_group_create_cols; kge_train_cols.h):
+"""The COLUMN-SHARDED train step (amdkge_cols_*, AMDKGE_TILED_GIVEN_COEFFS, amdkge_session_group_create_cols; kge_train_cols.hip):
 every slice holds k / W units of every row and processes the whole batch; the partial score sums of the slices add up to the
 reference's scores (TransE.py:51-53, DistMult.py:48, ComplEx.py:58-62, HolE.py:45, RotatE.py:100-104 are sums over units), the loss
 on the complete scores is Loss.__call__ (loss_functions.py:185-225), and the backward / optimizer on a slice is the column slice of the

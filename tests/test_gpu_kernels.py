@@ -176,6 +176,29 @@ def test_train_fwdbwd_geometries(gpu_lib, model, k, pad):
     assert_grads_close(Gr, Tr)
 
 
+@pytest.mark.parametrize("k,eta", [(132, 200), (8, 700)])
+def test_train_fwdbwd_large_lds(gpu_lib, k, eta):
+    """The dense step above 64 KB of dynamic LDS: launch_train_w (kge_train.hip) has to raise the kernel's limit first, once per
+    device.  TransE, one wave per positive, LDS = 4 slot_lds_bytes(eta, 1) + 32 [+ 16 K + 256 eta in the 16-byte layout]:
+    k = 132 (the 16-byte layout starts above 128 units), eta = 200: 72 672 B; k = 8 (one unit per lane), eta = 700: 67 360 B.
+    Two steps on one device -- the second finds the limit already raised -- each against the oracle."""
+    slot = ((eta + 1) * 6 * 4 + 8 + 7) & ~7   # slot_lds_bytes(eta, 1), kge_train_common.h
+    assert 64 * 1024 < 4 * slot + 32 + (16 * k + 256 * eta if k > 128 else 0) <= 150 * 1024
+    N, R, B = 300, 4, 8
+    eng, ent, rel = make_engine("TransE", k, N, R, scale=0.3 if k < 100 else 0.08)
+    rng = np.random.default_rng(6)
+    X = rand_triples(rng, B, N, R)
+    for step in (0, 1):
+        L, Ge, Gr, ps, ns = run_fwdbwd(eng, X, eta, "self_adversarial", "sum", seed=2, step=step)
+        negs = O.generate_corruptions(X, N, eta, 2, step)
+        total, Te, Tr, (sp, sn, per) = O.dense_gradients("TransE", ent, rel, X, negs, eta, "self_adversarial", None, "sum", R)
+        assert np.allclose(ps, sp, rtol=1e-5, atol=1e-5 * np.abs(sp).max())
+        assert np.allclose(ns, sn, rtol=1e-5, atol=1e-5 * np.abs(sn).max())
+        assert abs(L - float(total)) <= 2e-5 * max(1.0, abs(L))
+        assert_grads_close(Ge, Te)
+        assert_grads_close(Gr, Tr)
+
+
 def test_train_neg_override_and_duplicates(gpu_lib):
     """Identity corruptions, s == o triples and heavy row duplication (gradient dedup = sum)."""
     N, R, k, eta = 5, 2, 8, 4

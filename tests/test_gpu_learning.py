@@ -110,7 +110,7 @@ def test_mean_mrr_over_seeds_matches_oracle(gpu_lib, model, loss):
     # -- the sampler redrew the entity that is already on the other side, one corruption in N -- whose relation has a unit with a phase
     # so close to 0 that cos rounds to 1 and e sin(phi) falls under the ulp of e evaluates to z = (0, 0) EXACTLY in fp32, sqrt(0) = 0,
     # and the gradient is 0 / 0: NaN in the tables from that step on -- in the reference's own arithmetic as here (tf.sqrt's gradient at
-    # 0 is inf, times 2 z = 0).  The loss kernels now report it as the NaN it is (clip_exp, kge_train_kernel.h) instead of 375 per
+    # 0 is inf, times 2 z = 0).  The loss kernels now report it as the NaN it is (clip_exp, kge_train_common.h) instead of 375 per
     # positive.  The oracle replays in fp64 and never meets the exact zero, so a fit that does is re-drawn here (the default mode's
     # arrival-order rounding differs from run to run: the same seed does not meet it twice) and COUNTED: more than two per case would
     # be another mechanism.

@@ -148,7 +148,7 @@ def test_nonfinite_rows_after_whole_steps(gpu_lib, model, loss, path, kind):
 @pytest.mark.parametrize("loss", ["nll", "multiclass_nll", "self_adversarial", "pairwise"])
 @pytest.mark.parametrize("model,k,W", [("ComplEx", 64, 4), ("TransE", 64, 2), ("RotatE", 48, 2), ("DistMult", 96, 2)])
 def test_nonfinite_rows_column_sharded(gpu_lib, model, k, W, loss, kind):
-    """The column-sharded step (kge_train_cols.h): cols_loss_kernel on the summed partial scores gives the oracle's loss (NaN where it
+    """The column-sharded step (kge_train_cols.hip): cols_loss_kernel on the summed partial scores gives the oracle's loss (NaN where it
     is NaN), and every slice's gradient holds non-finite rows exactly where the column slice of the oracle's gradient does."""
     from test_gpu_cols import col_slice
 

@@ -1,4 +1,4 @@
-"""The row-direct tile pass for long rows (kge_tile_direct.h; rows beyond 2 KB: the C5 row width) -- whole steps against the
+"""The row-direct tile pass for long rows (kge_train_direct.hip; rows beyond 2 KB: the C5 row width) -- whole steps against the
 oracle and against the LDS-accumulator kernel it replaces there (amdkge_set_tile_direct(0)), in every mode the tile pass has:
 in place / gradient only, touched-rows optimizer, atomic positives, hot-row replicas, overflowing buckets, every update rule."""
 import numpy as np

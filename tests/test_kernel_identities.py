@@ -5,7 +5,7 @@ derivations, the GPU parity tests pin the kernels.
 * RotatE, forward kernel (kge_train_kernel.h, single pass): with z_j = s o r - o of corruption j and Z_side = sum_j g_j z_j / |z_j|
   over the corruptions of one side, the row gradients of the positive are LINEAR in Z:
   d/ds = -conj(r) o Z_obj, d/do = +Z_subj, d/dphase = -Im(conj(A) Z_obj) - Im(conj(o) Z_subj) with A = s o r.
-* RotatE, tile pass (kge_train_tiled.hip): d|e o r - o| / de = (e - B) / |e - B| with B = o o conj(r), and
+* RotatE, tile pass (kge_train_tile.hip): d|e o r - o| / de = (e - B) / |e - B| with B = o o conj(r), and
   d|A - e| / de = (e - A) / |A - e|.
 * TransE: d(-|d|)/d(s, p, o) = (-sign d, -sign d, +sign d) with sign(0) = 0, i.e. a coefficient with the sign bit of d flipped in
   wherever d != 0."""
