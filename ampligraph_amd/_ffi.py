@@ -120,6 +120,7 @@ SIGNATURES = {
     "amdkge_row_sqnorms": (C.c_int, [P, I32, P, I64, I64, C.c_float, I32, P, P]),
     "amdkge_pair_distances": (C.c_int, [P, I64, P, I32, P, I64, P, I32, I32, P, P]),
     "amdkge_topk_rows": (C.c_int, [P, I64, I64, I64, P, P, P, I32, I32, P, P, P]),
+    "amdkge_topk_rows_excluding": (C.c_int, [P, I64, I64, I64, P, I64, P, P, P, P, I32, P, P, P]),
     "amdkge_discover_select": (C.c_int, [P, I64, I64, I64, P, I32, P, P, P, I32, I32, P, I32, I64, P, I64, P, P]),
     "amdkge_join_nearest": (C.c_int, [P, I64, I32, P, P, P, P, P]),
     "amdkge_join_radius": (C.c_int, [P, I64, I32, C.c_double, P, I64, P, P]),

@@ -7,6 +7,11 @@ neighbours are sklearn on the host.  Here an entity completion is ONE query thro
 of evaluate() (amdkge_corruption_scores: same prep + tile kernels as the ranks) followed by a streaming top-k selection
 kernel (amdkge_topk_rows); nearest neighbours are dot products on the same tile kernel with the norms folded into the
 selection.  Only top_n ids / scores travel back.  Both work on a row-sharded entity table (per-shard lists, merged).
+query_topn_batch (no counterpart in the reference) completes MANY (s, p, ?) or (?, p, o) queries in one call and leaves out the
+statements already known to be true: the queries are the rows of chunked amdkge_corruption_scores calls, and each chunk's
+selection (amdkge_topk_rows_excluding, kge_complete.hip) looks a column up in the query's range of the evaluate() filter index
+before it may enter the list -- an exclusion inside the selection, so a known column is never a filler and -inf / NaN scores
+stay scores.  Replicated placement only.
 find_duplicates is an exact self-join of the embeddings on the device (amdkge_join_nearest / amdkge_join_radius,
 kge_join.hip); its tolerance bisection runs on the host over one nearest distance per row.  find_clusters runs DBSCAN -- its
 default, and the reference's documented use -- on the same join (amdkge_join_dbscan: neighbour count, union-find over the core
@@ -28,7 +33,7 @@ from . import _ffi
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["discover_facts", "generate_candidates", "query_topn", "find_nearest_neighbours", "find_duplicates", "find_clusters", "KMeans"]
+__all__ = ["discover_facts", "generate_candidates", "query_topn", "query_topn_batch", "find_nearest_neighbours", "find_duplicates", "find_clusters", "KMeans"]
 
 
 def _known(indexer, values, type_of):
@@ -100,6 +105,106 @@ def query_topn(model, top_n=10, head=None, relation=None, tail=None, ents_to_con
     fix_col = np.full(n, fixed, dtype=np.int64)
     out = np.stack([fix_col, rel_col, ents], 1) if tail is None else np.stack([ents, rel_col, fix_col], 1)
     return ix.get_indexes(out, "t", "ind2raw"), val.astype(np.float32)
+
+
+TOPN_BATCH_MAX = 1024   # amdkge_topk_rows_excluding's largest k
+
+
+def _ids_or_fail(ix, labels, kind):
+    """ids of `labels` (a 1-d array), or ValueError naming the ones the model has not seen (get_indexes drops them silently)."""
+    got = np.asarray(ix.get_indexes(labels, kind), dtype=np.int64)
+    if len(got) != len(labels):
+        unseen = [u for u in dict.fromkeys(labels.tolist()) if len(ix.get_indexes(np.asarray([u]), kind)) == 0]
+        raise ValueError("{} not seen by the model: {}".format("Entities" if kind == "e" else "Relations", unseen))
+    return got
+
+
+def query_topn_batch(model, queries, top_n=10, corrupt_side="o", use_filter=False, ents_to_consider=None, exclude_reflexive=False):
+    """The top_n best completions of MANY incomplete statements, without the ones already known to be true: what a trained
+    link predictor is asked for most (recommendations for every head), and what query_topn -- one query per call, true
+    statements on top of every list -- does not give.  (The reference has no counterpart.)
+
+    queries: (n, 2) labels, the triple without its missing column in s, p, o order -- [subject, predicate] for
+    corrupt_side="o", [predicate, object] for "s".  use_filter: False, or a dict of datasets as evaluate() takes (their
+    union; a bare (m, 3) array stands for {"known": array}): a completion whose statement is in one of them is left out --
+    exactly the ids evaluate() would subtract for a test triple with the same two fixed elements.  ents_to_consider: as in
+    query_topn (None or empty: every entity).  exclude_reflexive: also leave out the query's own entity.
+
+    Returns (entities (n, top_n) object array of labels, scores (n, top_n) float32), best first, equal scores by increasing
+    position in the candidate list; where fewer than top_n candidates remain the tail holds None / -inf.  top_n <= 1024.
+    Labels the model has not seen raise ValueError naming them.
+
+    All queries are scored on the device in chunks (amdkge_corruption_scores) and each chunk goes straight into a per-row
+    selection that skips the known ids (amdkge_topk_rows_excluding, kge_complete.hip): a known completion never enters the
+    selection, so it cannot reappear as a filler, and -inf / NaN scores stay what they are.  Needs the whole entity table on
+    one GPU: row- and column-sharded models raise NotImplementedError."""
+    import torch
+
+    from .placement import Columns, Rows
+
+    model = getattr(model, "model", model) if getattr(model, "is_backward", False) else model   # 1.x compat wrappers
+    if not model.is_fitted:
+        raise ValueError("Model is not fitted.")
+    if corrupt_side not in ("s", "o"):
+        raise ValueError("`corrupt_side` must be 's' or 'o', got {!r}.".format(corrupt_side))
+    Q = np.asarray(queries)
+    if Q.ndim != 2 or Q.shape[1] != 2:
+        raise ValueError("`queries` must have shape (n, 2): [subject, predicate] for corrupt_side='o', [predicate, object] for 's'; "
+                         "got {}.".format(Q.shape))
+    top_n = int(top_n)
+    if top_n < 1 or top_n > TOPN_BATCH_MAX:
+        raise ValueError("`top_n` must be between 1 and {} (the device selection's limit); query_topn takes any top_n for a single "
+                         "query. Got {}.".format(TOPN_BATCH_MAX, top_n))
+    if use_filter is True:
+        raise ValueError("`use_filter=True` has no meaning here (there is no evaluated set that could filter itself): pass a dict of "
+                         "datasets or an (m, 3) array of known statements.")
+    if use_filter is None or use_filter is False:
+        use_filter = None
+    elif not isinstance(use_filter, dict):
+        known = np.asarray(use_filter)
+        if known.ndim != 2 or known.shape[1] < 3:
+            raise ValueError("`use_filter` must be False, a dict of datasets or an (m, 3) array of known statements.")
+        use_filter = {"known": known}
+    ix = model.data_indexer
+    cand_ids = None
+    if ents_to_consider is not None:
+        if not isinstance(ents_to_consider, (list, np.ndarray)):
+            raise ValueError("`ents_to_consider` must be a list or numpy array.")
+        if not _known(ix, ents_to_consider, "e"):
+            raise ValueError("Entities in `ents_to_consider` have not been seen by the model.")
+        if len(ents_to_consider) > 0:
+            cand_ids = np.asarray(ix.get_indexes(np.asarray(ents_to_consider), "e"), dtype=np.int64)
+    ent_col, rel_col = (0, 1) if corrupt_side == "o" else (1, 0)
+    fixed = _ids_or_fail(ix, Q[:, ent_col], "e")
+    r_id = _ids_or_fail(ix, Q[:, rel_col], "r")
+    pl = model._placement
+    if isinstance(pl, (Rows, Columns)):
+        raise NotImplementedError("query_topn_batch selects against the whole entity table on one GPU: row- and column-sharded tables "
+                                  "(entity_sharding) are out of its scope; query_topn works there")
+    n = int(Q.shape[0])
+    if n == 0:
+        return np.empty((0, top_n), dtype=object), np.empty((0, top_n), dtype=np.float32)
+    eng = model._engine
+    dev = eng.device
+    side = _ffi.SIDE_O if corrupt_side == "o" else _ffi.SIDE_S
+    q = torch.as_tensor(np.stack([fixed, r_id, fixed], 1).astype(np.int32)).to(dev)   # the replaced column is ignored by the scores and the filter
+    flt = None
+    if use_filter is not None:
+        flt = model._filter_index(use_filter, None).device_filter(eng, q, corrupt_side)
+    own = q[:, 0].contiguous() if exclude_reflexive else None
+    ql = pl.localise(q)
+    missing = []
+
+    def pick(ids, hi, kk):
+        pos, val = eng.corruption_topk(ql, side, kk, ent_ids=ids, ent_hi=hi, flt=flt, own=own)
+        missing.append(pos < 0)
+        return pos, val
+
+    ents, val = pl.select(pick, cand_ids, n, top_n)
+    gone = missing[0].cpu().numpy()
+    labels = np.empty((n, top_n), dtype=object)
+    labels[~gone] = ix.get_indexes(ents[~gone], "e", "ind2raw")
+    return labels, val.astype(np.float32)
 
 
 def find_nearest_neighbours(kge_model, entities, n_neighbors=10, entities_subset=None, metric="euclidean"):

@@ -484,10 +484,24 @@ class KgeEngine:
                                         _ptr(idx), _ptr(val), _stream()))
         return idx, val
 
-    def corruption_topk(self, triples, side, k, ent_ids=None, ent_lo=0, ent_hi=None):
+    def topk_rows_excluding(self, vals, k, col_ids=None, id_base=0, flt=None, own=None):
+        """(idx int32 [n,k], val fp32 [n,k]) of the k largest entries per row of vals [n,m] among the columns whose entity id
+        (col_ids[j], or id_base + j) is neither in the row's range of flt = (lo, hi, ids) nor equal to own[row]
+        (amdkge_topk_rows_excluding; 1 <= k <= 1024).  Same order and missing-entry convention as topk_rows."""
+        n, m = int(vals.shape[0]), int(vals.shape[1])
+        lo, hi, ids = flt if flt is not None else (None, None, None)
+        idx = torch.empty(n, int(k), dtype=torch.int32, device=self.device)
+        val = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
+        check(self.lib.amdkge_topk_rows_excluding(_ptr(vals), n, m, int(vals.stride(0)) if n else m, _ptr(col_ids), int(id_base), _ptr(lo), _ptr(hi),
+                                                  _ptr(ids), _ptr(own), int(k), _ptr(idx), _ptr(val), _stream()))
+        return idx, val
+
+    def corruption_topk(self, triples, side, k, ent_ids=None, ent_lo=0, ent_hi=None, flt=None, own=None):
         """Top-k scoring corruptions of one side for every query triple: (positions int32 [n,k] into the candidate list /
         row range, scores fp32 [n,k]).  Queries go through amdkge_corruption_scores in chunks whose score block stays under
-        SCORE_CHUNK_BYTES, each chunk straight into amdkge_topk_rows."""
+        SCORE_CHUNK_BYTES, each chunk straight into amdkge_topk_rows.  With flt = (lo, hi, ids) (FilterIndex.device_filter of
+        the queries) and / or own (int32 [n] entity ids) the chunk goes to amdkge_topk_rows_excluding instead: a candidate
+        whose entity id is in the query's range, or equals own[query], takes no part in the selection."""
         n = int(triples.shape[0])
         if ent_hi is None:
             ent_hi = self.n_ents if ent_ids is None else int(ent_ids.shape[0])
@@ -495,13 +509,19 @@ class KgeEngine:
         rows = max(1, min(n, self.SCORE_CHUNK_BYTES // max(4 * m, 1)))
         out_i = torch.empty(n, int(k), dtype=torch.int32, device=self.device)
         out_v = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
+        excluding = flt is not None or own is not None
+        col_ids = None if ent_ids is None else ent_ids[int(ent_lo):int(ent_hi)]
         for c0 in range(0, n, rows):
             c1 = min(n, c0 + rows)
             blk = self._buf("disc_scores", (c1 - c0, m), torch.float32)
             work = self._workspace(c1 - c0)
             check(self.lib.amdkge_corruption_scores(C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples[c0:c1]), c1 - c0, int(side),
                                                     _ptr(ent_ids), int(ent_lo), int(ent_hi), _ptr(blk), m, _ptr(work), _stream()))
-            i_, v_ = self.topk_rows(blk, k)
+            if excluding:
+                f = None if flt is None else (flt[0][c0:c1], flt[1][c0:c1], flt[2])
+                i_, v_ = self.topk_rows_excluding(blk, k, col_ids, int(ent_lo), f, None if own is None else own[c0:c1])
+            else:
+                i_, v_ = self.topk_rows(blk, k)
             out_i[c0:c1], out_v[c0:c1] = i_, v_
         return out_i, out_v
 

@@ -431,6 +431,18 @@ int amdkge_row_sqnorms(const float* d_table, int32_t row_floats, const int32_t* 
                        float* d_out, void* stream);
 int amdkge_topk_rows(const float* d_vals, int64_t n, int64_t m, int64_t ld, const float* d_col_scale, const float* d_col_bias,
                      const int32_t* d_payload, int32_t k, int32_t largest, int32_t* d_out_idx, float* d_out_val, void* stream);
+/* amdkge_topk_rows(largest = 1) without the columns a row already knows (kge_complete.hip; discovery.query_topn_batch): per row i of
+ * d_vals [n, m] (leading dimension ld) the k (1 <= k <= 1024) largest entries among the columns that TAKE PART, best first, as column
+ * indices d_out_idx [n, k] and values d_out_val [n, k]; equal values in order of increasing column, a NaN below everything, missing
+ * entries (fewer than k columns take part) -1 / -inf.  Column j stands for the entity id d_col_ids[j], or id_base + j when d_col_ids
+ * is NULL.  It does not take part when that id is among d_ex_ids[d_ex_lo[i] .. d_ex_hi[i]) -- the ranges of amdkge_filter_ranges,
+ * ids ascending inside a range (amdkge_filter_build's order); three NULLs: nothing excluded -- or equals d_own[i] (d_own may be
+ * NULL).  An excluded column never reaches the output, not even as a filler: it is left out of the selection, the score block is
+ * read only (-inf and NaN are scores like any other).  With three NULLs and d_own NULL the output is amdkge_topk_rows', bit for bit.
+ * Bad sizes, and a range array without its two siblings, fail with AMDKGE_EINVAL before any launch; n == 0 is a no-op. */
+int amdkge_topk_rows_excluding(const float* d_vals, int64_t n, int64_t m, int64_t ld, const int32_t* d_col_ids, int64_t id_base,
+                               const int64_t* d_ex_lo, const int64_t* d_ex_hi, const int32_t* d_ex_ids, const int32_t* d_own,
+                               int32_t k, int32_t* d_out_idx, float* d_out_val, void* stream);
 /* exact distances of explicit pairs: d_out[i*k + j] = |d_q[i] - row(d_pos[i*k + j])| (cosine != 0: 1 - cos), rows addressed like
  * amdkge_row_sqnorms (lo + pos, or d_ids[lo + pos]); pos < 0 -> +inf.  Re-measures the neighbours the GEMM-form selection kept. */
 int amdkge_pair_distances(const float* d_q, int64_t n, const float* d_table, int32_t row_floats, const int32_t* d_ids, int64_t lo,
