@@ -121,6 +121,11 @@ SIGNATURES = {
     "amdkge_pair_distances": (C.c_int, [P, I64, P, I32, P, I64, P, I32, I32, P, P]),
     "amdkge_topk_rows": (C.c_int, [P, I64, I64, I64, P, P, P, I32, I32, P, P, P]),
     "amdkge_topk_rows_excluding": (C.c_int, [P, I64, I64, I64, P, I64, P, P, P, P, I32, P, P, P]),
+    "amdkge_relation_workspace_bytes": (I64, [C.POINTER(Model), I64]),
+    "amdkge_relation_scores": (C.c_int, [C.POINTER(Model), P, P, P, I64, P, I64, I64, P, I64, P, P]),
+    "amdkge_relation_rank_counts": (C.c_int, [P, I64, I64, I64, P, P, I64, P, P, P, P, P, P, P]),
+    "amdkge_pair_filter_build": (C.c_int, [P, I64, I64, I64, P, P, P, P, P, P]),
+    "amdkge_pair_filter_ranges": (C.c_int, [P, P, I64, P, I64, I64, P, P, P]),
     "amdkge_discover_select": (C.c_int, [P, I64, I64, I64, P, I32, P, P, P, I32, I32, P, I32, I64, P, I64, P, P]),
     "amdkge_join_nearest": (C.c_int, [P, I64, I32, P, P, P, P, P]),
     "amdkge_join_radius": (C.c_int, [P, I64, I32, C.c_double, P, I64, P, P]),

@@ -21,11 +21,15 @@
 
 namespace kge {
 
+// third key form (relation prediction, amdkge_pair_filter_build): group key (s * N + o), values p -- the divisor that separates
+// group and value is then R instead of N
+constexpr int FILTER_KEY_PAIR = 4;
+
 __global__ void filter_keys_kernel(const int32_t* __restrict__ tri, int64_t m, int side, uint64_t N, uint64_t R, uint64_t* __restrict__ keys) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const uint64_t s = (uint64_t)tri[3 * i], p = (uint64_t)tri[3 * i + 1], o = (uint64_t)tri[3 * i + 2];
-    keys[i] = (side == AMDKGE_SIDE_S) ? (p * N + o) * N + s : (s * R + p) * N + o;
+    keys[i] = (side == FILTER_KEY_PAIR) ? (s * N + o) * R + p : (side == AMDKGE_SIDE_S) ? (p * N + o) * N + s : (s * R + p) * N + o;
 }
 
 // low 32 bits: 1 where a NEW KEY starts (duplicates of a triple across the filter datasets collapse), high 32 bits: 1 where a
@@ -61,7 +65,7 @@ struct FilterPlan {
 };
 
 static int key_bits_of(int64_t n_ents, int64_t n_rels) {
-    // keys < R * N^2 (subject side: (p N + o) N + s; object side: (s R + p) N + o)
+    // keys < R * N^2 (subject side: (p N + o) N + s; object side: (s R + p) N + o; pairs: (s N + o) R + p)
     long double top = (long double)n_rels * (long double)n_ents * (long double)n_ents;
     int b = 1;
     while (b < 64 && ldexpl(1.0L, b) < top) ++b;
@@ -96,14 +100,9 @@ extern "C" int64_t amdkge_filter_build_workspace_bytes(int64_t m, int64_t n_ents
     return (int64_t)p.total;
 }
 
-extern "C" int amdkge_filter_build(const int32_t* d_triples, int64_t m, int32_t side, int64_t n_ents, int64_t n_rels,
-                                   int64_t* d_keys, int64_t* d_start, int32_t* d_ids, int64_t* d_counts, void* d_work, void* stream) {
-    if (side != AMDKGE_SIDE_S && side != AMDKGE_SIDE_O) return set_error(AMDKGE_EINVAL, "filter_build: side must be AMDKGE_SIDE_S or AMDKGE_SIDE_O");
-    if (m < 0 || n_ents <= 0 || n_rels <= 0 || m > 0xFFFFFFFFll) return set_error(AMDKGE_EINVAL, "filter_build: bad sizes (at most 2^32 - 1 filter triples)");
-    if ((long double)n_rels * (long double)n_ents * (long double)n_ents >= 9.2e18L)
-        return set_error(AMDKGE_EUNSUPPORTED, "filter_build: n_rels * n_ents^2 does not fit the packed 64-bit sort keys");
-    if (!d_start || !d_counts) return set_error(AMDKGE_EINVAL, "filter_build: NULL pointer");
-    hipStream_t st = (hipStream_t)stream;
+// the build behind both entry points; form: AMDKGE_SIDE_S / AMDKGE_SIDE_O / FILTER_KEY_PAIR (arguments already validated)
+static int filter_build_run(const int32_t* d_triples, int64_t m, int form, int64_t n_ents, int64_t n_rels, int64_t* d_keys, int64_t* d_start,
+                            int32_t* d_ids, int64_t* d_counts, void* d_work, hipStream_t st) {
     if (m == 0) {
         if (hipError_t e = hipMemsetAsync(d_start, 0, 8, st)) return set_error_hip(e, "hipMemsetAsync(filter start)");
         if (hipError_t e = hipMemsetAsync(d_counts, 0, 16, st)) return set_error_hip(e, "hipMemsetAsync(filter counts)");
@@ -112,20 +111,68 @@ extern "C" int amdkge_filter_build(const int32_t* d_triples, int64_t m, int32_t 
     if (!d_triples || !d_keys || !d_ids || !d_work) return set_error(AMDKGE_EINVAL, "filter_build: NULL pointer");
     FilterPlan p;
     if (make_filter_plan(m, n_ents, n_rels, p)) return set_error(AMDKGE_EHIP, "filter_build: rocPRIM size query failed");
+    const uint64_t div = form == FILTER_KEY_PAIR ? (uint64_t)n_rels : (uint64_t)n_ents;   // key = group * div + value
     char* w = (char*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
     uint64_t* a = (uint64_t*)(w + p.off_a);
     uint64_t* b = (uint64_t*)(w + p.off_b);
     void* tmp = w + p.off_tmp;
     uint64_t* pos = (uint64_t*)(w + p.off_tmp + ((p.tmp_bytes + 255) & ~(size_t)255));
     const unsigned grid = (unsigned)((m + 255) / 256);
-    hipLaunchKernelGGL(filter_keys_kernel, dim3(grid), dim3(256), 0, st, d_triples, m, (int)side, (uint64_t)n_ents, (uint64_t)n_rels, a);
+    hipLaunchKernelGGL(filter_keys_kernel, dim3(grid), dim3(256), 0, st, d_triples, m, form, (uint64_t)n_ents, (uint64_t)n_rels, a);
     if (int rc = check_launch("filter_keys")) return rc;
     size_t tb = p.tmp_bytes;
     if (hipError_t e = rocprim::radix_sort_keys(tmp, tb, a, b, (size_t)m, 0u, (unsigned)p.key_bits, st)) return set_error_hip(e, "rocprim::radix_sort_keys");
-    hipLaunchKernelGGL(filter_flags_kernel, dim3(grid), dim3(256), 0, st, b, m, (uint64_t)n_ents, a);
+    hipLaunchKernelGGL(filter_flags_kernel, dim3(grid), dim3(256), 0, st, b, m, div, a);
     if (int rc = check_launch("filter_flags")) return rc;
     tb = p.tmp_bytes;
     if (hipError_t e = rocprim::exclusive_scan(tmp, tb, a, pos, (uint64_t)0, (size_t)m, rocprim::plus<uint64_t>(), st)) return set_error_hip(e, "rocprim::exclusive_scan");
-    hipLaunchKernelGGL(filter_emit_kernel, dim3(grid), dim3(256), 0, st, b, a, pos, m, (uint64_t)n_ents, d_keys, d_start, d_ids, d_counts);
+    hipLaunchKernelGGL(filter_emit_kernel, dim3(grid), dim3(256), 0, st, b, a, pos, m, div, d_keys, d_start, d_ids, d_counts);
     return check_launch("filter_emit");
+}
+
+extern "C" int amdkge_filter_build(const int32_t* d_triples, int64_t m, int32_t side, int64_t n_ents, int64_t n_rels,
+                                   int64_t* d_keys, int64_t* d_start, int32_t* d_ids, int64_t* d_counts, void* d_work, void* stream) {
+    if (side != AMDKGE_SIDE_S && side != AMDKGE_SIDE_O) return set_error(AMDKGE_EINVAL, "filter_build: side must be AMDKGE_SIDE_S or AMDKGE_SIDE_O");
+    if (m < 0 || n_ents <= 0 || n_rels <= 0 || m > 0xFFFFFFFFll) return set_error(AMDKGE_EINVAL, "filter_build: bad sizes (at most 2^32 - 1 filter triples)");
+    if ((long double)n_rels * (long double)n_ents * (long double)n_ents >= 9.2e18L)
+        return set_error(AMDKGE_EUNSUPPORTED, "filter_build: n_rels * n_ents^2 does not fit the packed 64-bit sort keys");
+    if (!d_start || !d_counts) return set_error(AMDKGE_EINVAL, "filter_build: NULL pointer");
+    return filter_build_run(d_triples, m, (int)side, n_ents, n_rels, d_keys, d_start, d_ids, d_counts, d_work, (hipStream_t)stream);
+}
+
+// Relation prediction's filter: the same CSR keyed by the PAIR, group key (s * n_ents + o) with the SET of relations seen between
+// the two (workspace: amdkge_filter_build_workspace_bytes, the plan is the same)
+extern "C" int amdkge_pair_filter_build(const int32_t* d_triples, int64_t m, int64_t n_ents, int64_t n_rels, int64_t* d_keys, int64_t* d_start,
+                                        int32_t* d_ids, int64_t* d_counts, void* d_work, void* stream) {
+    if (m < 0 || n_ents <= 0 || n_rels <= 0 || m > 0xFFFFFFFFll) return set_error(AMDKGE_EINVAL, "pair_filter_build: bad sizes (at most 2^32 - 1 filter triples)");
+    if ((long double)n_rels * (long double)n_ents * (long double)n_ents >= 9.2e18L)
+        return set_error(AMDKGE_EUNSUPPORTED, "pair_filter_build: n_rels * n_ents^2 does not fit the packed 64-bit sort keys");
+    if (!d_start || !d_counts) return set_error(AMDKGE_EINVAL, "pair_filter_build: NULL pointer");
+    return filter_build_run(d_triples, m, FILTER_KEY_PAIR, n_ents, n_rels, d_keys, d_start, d_ids, d_counts, d_work, (hipStream_t)stream);
+}
+
+// pair lookup: one thread per query, lower_bound in the sorted (s, o) keys
+__global__ void pair_filter_ranges_kernel(const int64_t* keys, const int64_t* start, int64_t n_keys, const int32_t* triples, int64_t n, int64_t n_ents,
+                                          int64_t* lo_out, int64_t* hi_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t q = (int64_t)triples[3 * i] * n_ents + (int64_t)triples[3 * i + 2];
+    int64_t a = 0, b = n_keys;
+    while (a < b) {
+        const int64_t m = (a + b) >> 1;
+        if (keys[m] < q) a = m + 1; else b = m;
+    }
+    const bool hit = a < n_keys && keys[a] == q;
+    lo_out[i] = hit ? start[a] : 0;
+    hi_out[i] = hit ? start[a + 1] : 0;
+}
+
+extern "C" int amdkge_pair_filter_ranges(const int64_t* d_keys, const int64_t* d_start, int64_t n_keys, const int32_t* d_triples, int64_t n,
+                                         int64_t n_ents, int64_t* d_lo, int64_t* d_hi, void* stream) {
+    if (n < 0 || n_keys < 0 || n_ents <= 0) return set_error(AMDKGE_EINVAL, "pair_filter_ranges: bad sizes");
+    if (n == 0) return AMDKGE_OK;
+    if (!d_triples || !d_lo || !d_hi || (n_keys > 0 && (!d_keys || !d_start))) return set_error(AMDKGE_EINVAL, "pair_filter_ranges: NULL pointer");
+    hipLaunchKernelGGL(pair_filter_ranges_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_keys, d_start, n_keys,
+                       d_triples, n, n_ents, d_lo, d_hi);
+    return check_launch("pair_filter_ranges");
 }

@@ -121,3 +121,81 @@ class FilterIndex:
         slo, shi = self.subject_ranges(triples)
         olo, ohi = self.object_ranges(triples)
         return ([self.s_ids[a:b] for a, b in zip(slo, shi)], [self.o_ids[a:b] for a, b in zip(olo, ohi)])
+
+
+class PairFilterIndex:
+    """The known relations of every (s, o) pair, for relation prediction (evaluate_relations(use_filter=...),
+    discovery.query_topn_relations): for a query (s, ?, o) the filter is the SET {p : (s, p, o) in any filter dataset}, as a CSR
+    over the sorted pair keys s * n_ents + o with the relation ids ascending inside a group -- FilterIndex's layout with a third
+    key form.  engine=None builds it on the host (numpy; the checker of the device build and what GPU-less callers get); with a
+    KgeEngine the id triples are uploaded once and amdkge_pair_filter_build builds it on the device (kge_filter.hip), the host
+    arrays (so_keys, so_start, r_ids) being downloaded only if somebody asks for them."""
+
+    _NAMES = ("so_keys", "so_start", "r_ids")
+
+    def __init__(self, datasets, n_ents, n_rels, engine=None):
+        self.n_ents, self.n_rels = int(n_ents), int(n_rels)
+        N, R = self.n_ents, self.n_rels
+        if R * N * N >= 2 ** 63:   # (python ints: no wrap)
+            raise ValueError(f"PairFilterIndex: n_rels * n_ents^2 = {R * N * N} does not fit the packed int64 keys")
+        if engine is not None:
+            self._init_device(datasets, engine)
+            return
+        X = np.concatenate([np.asarray(d)[:, :3].astype(np.int64) for d in datasets], 0) if len(datasets) else \
+            np.zeros((0, 3), dtype=np.int64)
+        s, p, o = X[:, 0], X[:, 1], X[:, 2]
+        k = np.unique((s * N + o) * R + p)
+        self.so_keys, self.so_start = np.unique(k // R, return_index=True)
+        self.so_start = np.append(self.so_start, k.size).astype(np.int64)
+        self.r_ids = (k % R).astype(np.int32)
+
+    def _init_device(self, datasets, engine):
+        import torch
+
+        dev = engine.device
+        parts = []
+        for d in datasets:
+            if isinstance(d, torch.Tensor):
+                parts.append(d[:, :3].to(device=dev, dtype=torch.int32))
+            else:
+                parts.append(torch.as_tensor(np.ascontiguousarray(np.asarray(d)[:, :3], dtype=np.int32)).to(dev))
+        X = torch.cat(parts, 0).contiguous() if parts else torch.zeros(0, 3, dtype=torch.int32, device=dev)
+        keys, start, ids = engine.pair_filter_build(X, self.n_ents, self.n_rels)
+        self._dev = {"device": str(dev), "so_keys": keys, "so_start": start,
+                     "r_ids": ids if ids.numel() else torch.zeros(1, dtype=torch.int32, device=dev)}
+        self._n_ids = int(ids.numel())
+
+    def __getattr__(self, name):
+        # host views of a device-built index, on demand
+        if name in PairFilterIndex._NAMES and "_dev" in self.__dict__:
+            t = self.__dict__["_dev"][name]
+            if name == "r_ids":
+                t = t[:self.__dict__["_n_ids"]]
+            a = t.cpu().numpy()
+            self.__dict__[name] = a
+            return a
+        raise AttributeError(name)
+
+    def relation_ranges(self, triples):
+        """(lo, hi) int64: the range of each triple's (s, o) pair in r_ids ((0, 0) for a pair no dataset holds)."""
+        t = np.asarray(triples)[:, :3].astype(np.int64)
+        return FilterIndex._ranges(self.so_keys, self.so_start, t[:, 0] * self.n_ents + t[:, 2])
+
+    def device_filter(self, engine, triples_dev):
+        """(lo, hi, ids) device tensors for relation_rank / relation_topk: relation_ranges done on the engine's device by
+        amdkge_pair_filter_ranges (keys, starts and ids are uploaded once per index and kept).  triples_dev: (n,3) int32 device
+        tensor of GLOBAL entity ids."""
+        import torch
+
+        device = engine.device
+        cache = self.__dict__.setdefault("_dev", {})
+        if cache.get("device") != str(device):
+            host = {nm: getattr(self, nm) for nm in PairFilterIndex._NAMES}   # (first: __getattr__ reads the cache replaced here)
+            fresh = {"device": str(device), "so_keys": torch.as_tensor(host["so_keys"]).to(device),
+                     "so_start": torch.as_tensor(host["so_start"]).to(device),
+                     "r_ids": torch.as_tensor(host["r_ids"] if host["r_ids"].size else np.zeros(1, np.int32)).to(device)}
+            cache.clear()
+            cache.update(fresh)
+            self.__dict__["_n_ids"] = int(host["r_ids"].size)
+        lo, hi = engine.pair_filter_ranges(cache["so_keys"], cache["so_start"], triples_dev, self.n_ents)
+        return lo, hi, cache["r_ids"]

@@ -12,6 +12,11 @@ statements already known to be true: the queries are the rows of chunked amdkge_
 selection (amdkge_topk_rows_excluding, kge_complete.hip) looks a column up in the query's range of the evaluate() filter index
 before it may enter the list -- an exclusion inside the selection, so a known column is never a filler and -inf / NaN scores
 stay scores.  Replicated placement only.
+query_topn_relations (no counterpart either) answers "which relation holds between these two entities?" for MANY (s, o) pairs:
+a 1-vs-all pass over the relation table that keeps the pairs' rows in registers (amdkge_relation_scores, kge_relation.hip: the
+bits of predict on the materialised triples, nothing materialised), the same excluding selection with the relations already
+known between a pair left out (PairFilterIndex, amdkge_pair_filter_build).  The relation table is whole on every rank, so it
+works on every placement; ScoringBasedEmbeddingModel.evaluate_relations ranks the true relation with the same kernels.
 find_duplicates is an exact self-join of the embeddings on the device (amdkge_join_nearest / amdkge_join_radius,
 kge_join.hip); its tolerance bisection runs on the host over one nearest distance per row.  find_clusters runs DBSCAN -- its
 default, and the reference's documented use -- on the same join (amdkge_join_dbscan: neighbour count, union-find over the core
@@ -33,7 +38,7 @@ from . import _ffi
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["discover_facts", "generate_candidates", "query_topn", "query_topn_batch", "find_nearest_neighbours", "find_duplicates", "find_clusters", "KMeans"]
+__all__ = ["discover_facts", "generate_candidates", "query_topn", "query_topn_batch", "query_topn_relations", "find_nearest_neighbours", "find_duplicates", "find_clusters", "KMeans"]
 
 
 def _known(indexer, values, type_of):
@@ -204,6 +209,69 @@ def query_topn_batch(model, queries, top_n=10, corrupt_side="o", use_filter=Fals
     gone = missing[0].cpu().numpy()
     labels = np.empty((n, top_n), dtype=object)
     labels[~gone] = ix.get_indexes(ents[~gone], "e", "ind2raw")
+    return labels, val.astype(np.float32)
+
+
+def query_topn_relations(model, pairs, top_n=10, use_filter=False, rels_to_consider=None):
+    """The top_n most plausible relations between MANY pairs of entities, without the ones already known to hold: the batched,
+    filtered form of query_topn(head=..., tail=...).  (The reference has no counterpart.)
+
+    pairs: (n, 2) labels [subject, object].  use_filter: False, or a dict of datasets as evaluate() takes (their union; a bare
+    (m, 3) array stands for {"known": array}): a relation p with (s, p, o) in one of them is left out of the pair's list.
+    rels_to_consider: as in query_topn (None or empty: every relation).
+
+    Returns (relations (n, top_n) object array of labels, scores (n, top_n) float32), best first, equal scores by increasing
+    position in the candidate list; where fewer than top_n candidates remain the tail holds None / -inf.  1 <= top_n <= 1024.
+    Labels the model has not seen raise ValueError naming them.
+
+    Every score has the bits predict() gives the materialised triple (amdkge_relation_scores: the pairs' rows stay in registers,
+    a relation row is read once per group of queries); the selection is amdkge_topk_rows_excluding with the pair's known
+    relations as the excluded ids.  Works on replicated, row- and column-sharded models (the relation table is whole on every
+    rank; on a row-sharded model it is a collective: call it on every rank)."""
+    import torch
+
+    model = getattr(model, "model", model) if getattr(model, "is_backward", False) else model   # 1.x compat wrappers
+    if not model.is_fitted:
+        raise ValueError("Model is not fitted.")
+    Q = np.asarray(pairs)
+    if Q.ndim != 2 or Q.shape[1] != 2:
+        raise ValueError("`pairs` must have shape (n, 2): [subject, object]; got {}.".format(Q.shape))
+    top_n = int(top_n)
+    if top_n < 1 or top_n > TOPN_BATCH_MAX:
+        raise ValueError("`top_n` must be between 1 and {} (the device selection's limit); query_topn takes any top_n for a single "
+                         "query. Got {}.".format(TOPN_BATCH_MAX, top_n))
+    if use_filter is True:
+        raise ValueError("`use_filter=True` has no meaning here (there is no evaluated set that could filter itself): pass a dict of "
+                         "datasets or an (m, 3) array of known statements.")
+    if use_filter is None or use_filter is False:
+        use_filter = None
+    elif not isinstance(use_filter, dict):
+        known = np.asarray(use_filter)
+        if known.ndim != 2 or known.shape[1] < 3:
+            raise ValueError("`use_filter` must be False, a dict of datasets or an (m, 3) array of known statements.")
+        use_filter = {"known": known}
+    ix = model.data_indexer
+    cand = None
+    if rels_to_consider is not None:
+        if not isinstance(rels_to_consider, (list, np.ndarray)):
+            raise ValueError("`rels_to_consider` must be a list or numpy array.")
+        if not _known(ix, rels_to_consider, "r"):
+            raise ValueError("Relations in `rels_to_consider` have not been seen by the model.")
+        if len(rels_to_consider) > 0:
+            cand = np.asarray(ix.get_indexes(np.asarray(rels_to_consider), "r"), dtype=np.int64)
+    s_id = _ids_or_fail(ix, Q[:, 0], "e")
+    o_id = _ids_or_fail(ix, Q[:, 1], "e")
+    n = int(Q.shape[0])
+    if n == 0:
+        return np.empty((0, top_n), dtype=object), np.empty((0, top_n), dtype=np.float32)
+    dev = model._engine.device
+    q = torch.as_tensor(np.stack([s_id, np.zeros_like(s_id), o_id], 1).astype(np.int32)).to(dev)   # the predicate column is ignored
+    pfi = model._pair_filter_index(use_filter, None) if use_filter is not None else None
+    pos, val = model._placement.select_relations(q, top_n, cand, pfi)
+    have = pos >= 0
+    rel = pos if cand is None else cand[np.maximum(pos, 0)]
+    labels = np.empty((n, top_n), dtype=object)
+    labels[have] = ix.get_indexes(rel[have], "r", "ind2raw")
     return labels, val.astype(np.float32)
 
 

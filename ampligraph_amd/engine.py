@@ -525,6 +525,103 @@ class KgeEngine:
             out_i[c0:c1], out_v[c0:c1] = i_, v_
         return out_i, out_v
 
+    # ------------------------------------------------------------------ relation prediction (kge_relation.hip, kge_filter.hip)
+    def pair_filter_build(self, triples, n_ents, n_rels):
+        """amdkge_pair_filter_build: the CSR of the relations known between every (s, o) pair of the id triples (int32 [m,3] device
+        tensor) -> (keys int64 [n_groups], start int64 [n_groups + 1], ids int32 [n_unique]) device tensors, as filter_build."""
+        m = int(triples.shape[0])
+        keys = torch.empty(max(m, 1), dtype=torch.int64, device=self.device)
+        start = torch.empty(m + 1, dtype=torch.int64, device=self.device)
+        ids = torch.empty(max(m, 1), dtype=torch.int32, device=self.device)
+        counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        need = int(self.lib.amdkge_filter_build_workspace_bytes(m, int(n_ents), int(n_rels)))
+        if need < 0:
+            raise ValueError("pair_filter_build: bad sizes")
+        work = self._buf("filter_build_work", (need,), torch.uint8)
+        check(self.lib.amdkge_pair_filter_build(_ptr(triples), m, int(n_ents), int(n_rels), _ptr(keys), _ptr(start), _ptr(ids), _ptr(counts),
+                                                _ptr(work), _stream()))
+        ng, nu = (int(c) for c in counts.tolist())
+        return keys[:ng], start[:ng + 1], ids[:nu]
+
+    def pair_filter_ranges(self, keys, start, triples, n_ents):
+        """(lo, hi) int64 device tensors: each triple's (s, o) range in a PairFilterIndex id array (amdkge_pair_filter_ranges)."""
+        n = int(triples.shape[0])
+        lo = torch.empty(n, dtype=torch.int64, device=self.device)
+        hi = torch.empty(n, dtype=torch.int64, device=self.device)
+        check(self.lib.amdkge_pair_filter_ranges(_ptr(keys), _ptr(start), int(keys.shape[0]), _ptr(triples), n, int(n_ents), _ptr(lo), _ptr(hi),
+                                                 _stream()))
+        return lo, hi
+
+    def _relation_block(self, triples, rel_ids, lo, hi, out, ld):
+        work = None
+        need = int(self.lib.amdkge_relation_workspace_bytes(C.byref(self.model), hi - lo))
+        if need > 0:
+            work = self._buf("relation_work", (need,), torch.uint8)
+        check(self.lib.amdkge_relation_scores(C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples), int(triples.shape[0]),
+                                              _ptr(rel_ids), int(lo), int(hi), _ptr(out), int(ld), _ptr(work), _stream()))
+
+    def _relation_chunks(self, n, m):
+        """Query ranges whose (queries x candidates) score block stays under SCORE_CHUNK_BYTES, as corruption_topk chunks them."""
+        rows = max(1, min(max(n, 1), self.SCORE_CHUNK_BYTES // max(4 * m, 1)))
+        return [(c0, min(n, c0 + rows)) for c0 in range(0, n, rows)]
+
+    def relation_scores(self, triples, rel_ids=None, out=None, rel_lo=0, rel_hi=None):
+        """Scores fp32 [n, m] of (s_i, r_j, o_i) for every query row of `triples` (int32 [n,3] device tensor; the predicate column is
+        ignored) and every candidate relation -- rows [rel_lo, rel_hi) of the relation table, or of the list rel_ids (int32 device
+        tensor) --, each with the bits score() gives the materialised triple (amdkge_relation_scores).  out: an fp32 [n, >= m]
+        device tensor whose rows may be strided; its columns beyond m are left untouched."""
+        n = int(triples.shape[0])
+        if rel_hi is None:
+            rel_hi = self.n_rels if rel_ids is None else int(rel_ids.shape[0])
+        m = int(rel_hi) - int(rel_lo)
+        if out is None:
+            out = torch.empty(n, m, dtype=torch.float32, device=self.device)
+        if out.ndim != 2 or out.dtype != torch.float32 or int(out.shape[0]) != n or int(out.shape[1]) < m or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise ValueError("relation_scores: `out` must be an fp32 [n, >= m] tensor with unit column stride")
+        self._relation_block(triples, rel_ids, rel_lo, rel_hi, out, int(out.stride(0)) if n > 1 else max(int(out.shape[1]), m))
+        return out[:, :m]
+
+    def relation_rank(self, triples, strategy="worst", flt=None, rel_ids=None, subset_pos=None):
+        """1-based ranks (int32 [n]) of each triple's OWN relation among the candidate relations (all, or rel_ids), with the tie
+        and filter conventions of the entity sides: the positive's score (score()) against the 1-vs-all block of relation_scores
+        in quantised comparisons (amdkge_relation_rank_counts), composed by amdkge_rank_compose.  flt = (lo, hi, ids) of
+        PairFilterIndex.device_filter; subset_pos (int32 [n_rels], -1 = not a candidate) maps a relation to its column of rel_ids
+        and is derived from rel_ids when not given.  -> (ranks, counts, sub)."""
+        n = int(triples.shape[0])
+        m = self.n_rels if rel_ids is None else int(rel_ids.shape[0])
+        if rel_ids is not None and subset_pos is None:
+            at = np.full(self.n_rels, -1, dtype=np.int32)   # (on the host: a repeated id keeps its LAST column, as Replicated._rank)
+            at[rel_ids.cpu().numpy()] = np.arange(m, dtype=np.int32)
+            subset_pos = torch.as_tensor(at).to(self.device)
+        pos = self.score(triples)
+        counts = torch.zeros(n, 2, dtype=torch.int32, device=self.device)
+        sub = torch.zeros(n, dtype=torch.int32, device=self.device) if flt is not None else None
+        lo, hi, ids = flt if flt is not None else (None, None, None)
+        for c0, c1 in self._relation_chunks(n, m):
+            blk = self._buf("rel_scores", (c1 - c0, m), torch.float32)
+            self._relation_block(triples[c0:c1], rel_ids, 0, m, blk, m)
+            check(self.lib.amdkge_relation_rank_counts(_ptr(blk), c1 - c0, m, m, _ptr(pos[c0:c1]), _ptr(rel_ids), 0,
+                                                       _ptr(lo[c0:c1]) if flt is not None else _ptr(None),
+                                                       _ptr(hi[c0:c1]) if flt is not None else _ptr(None), _ptr(ids), _ptr(subset_pos),
+                                                       _ptr(counts[c0:c1]), _ptr(sub[c0:c1]) if sub is not None else _ptr(None), _stream()))
+        return self.compose_ranks(counts, sub, strategy), counts, sub
+
+    def relation_topk(self, triples, k, rel_ids=None, flt=None):
+        """The k (<= 1024) best candidate relations of every query pair: (positions int32 [n,k] into the candidate list / the
+        relation table, scores fp32 [n,k]), best first, equal scores by increasing position, missing entries -1 / -inf.  With
+        flt = (lo, hi, ids) (PairFilterIndex.device_filter of the queries) a relation already known between the pair takes no
+        part in the selection (amdkge_topk_rows_excluding over each chunk's relation_scores block)."""
+        n = int(triples.shape[0])
+        m = self.n_rels if rel_ids is None else int(rel_ids.shape[0])
+        out_i = torch.empty(n, int(k), dtype=torch.int32, device=self.device)
+        out_v = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
+        for c0, c1 in self._relation_chunks(n, m):
+            blk = self._buf("rel_scores", (c1 - c0, m), torch.float32)
+            self._relation_block(triples[c0:c1], rel_ids, 0, m, blk, m)
+            f = None if flt is None else (flt[0][c0:c1], flt[1][c0:c1], flt[2])
+            out_i[c0:c1], out_v[c0:c1] = self.topk_rows_excluding(blk, k, rel_ids, 0, f, None)
+        return out_i, out_v
+
     def nearest_rows(self, q_rows, k, metric="euclidean", ent_ids=None, ent_lo=0, ent_hi=None, table=None):
         """k nearest table rows of every query row (stored layout, [n, Ks]), nearest first: (positions int32 [n,k],
         distances fp32 [n,k]).  Selection in GEMM form on the tile kernel (amdkge_row_dots) with the norms folded into

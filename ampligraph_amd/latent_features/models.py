@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from .. import _ffi
-from ..datasets.filters import FilterIndex
+from ..datasets.filters import FilterIndex, PairFilterIndex
 from ..datasets.indexer import DataIndexer
 from ..evaluation.metrics import hits_at_n_score, mr_score, mrr_score
 from . import loss_functions, optimizers, regularizers
@@ -355,6 +355,35 @@ class ScoringBasedEmbeddingModel:
             return FilterIndex([Xi], self._n_ents, self._n_rels, engine=self._engine)
         return None
 
+    def _pair_filter_index(self, use_filter, Xi):
+        """PairFilterIndex for evaluate_relations() / query_topn_relations(): _filter_index's dict / True semantics with the
+        (s, o) pair as the key (the SET of relations known between the two), built on the device (amdkge_pair_filter_build);
+        a cache of its own holds the last dict's index by content checksum."""
+        try:
+            from xxhash import xxh3_64_intdigest as _digest
+        except Exception:   # pragma: no cover
+            from zlib import crc32 as _digest
+
+        if isinstance(use_filter, dict):
+            arrays = [_load_triples(v)[:, :3] for v in use_filter.values()]
+            key = []
+            for a in arrays:
+                a = np.ascontiguousarray(a)
+                if a.dtype == object:
+                    key = None
+                    break
+                key.append((a.shape, str(a.dtype), _digest(a.view(np.uint8).reshape(-1))))
+            key = None if key is None else ("dict", tuple(key), self._n_ents, self._n_rels)
+            if key is not None and getattr(self, "_pair_filter_cache", (None, None))[0] == key:
+                return self._pair_filter_cache[1]
+            fi = PairFilterIndex([self.data_indexer.get_indexes(a) for a in arrays], self._n_ents, self._n_rels, engine=self._engine)
+            if key is not None:
+                self._pair_filter_cache = (key, fi)
+            return fi
+        if use_filter:
+            return PairFilterIndex([Xi], self._n_ents, self._n_rels, engine=self._engine)
+        return None
+
     # ------------------------------------------------------------------------------------ predict
     def _index_test(self, x):
         assert self.is_fitted, "Model is not fit on the data yet!"
@@ -392,6 +421,32 @@ class ScoringBasedEmbeddingModel:
         if corrupt_side == "s+o":  # :1459-1463 sums the two 0-based sides, then +1 (:1684)
             r = (r.sum(1, keepdims=True) - 1).astype(np.int32)
         return r
+
+    def evaluate_relations(self, x, use_filter=False, relations_subset=None, ranking_strategy="worst", verbose=False):
+        """Relation prediction's evaluate() (the reference has none): int32 ranks (n, 1), 1-based, of each triple's relation among
+        the candidate relations for its (s, o) pair -- every relation, or `relations_subset` with entities_subset's semantics (the
+        true relation's score is compared with the subset's, whether or not it is in it).  Ties and filters as in evaluate():
+        `ranking_strategy` worst / best / middle over the quantised scores; `use_filter` False, True (the evaluated data filters
+        itself) or a dict of datasets -- a relation KNOWN between s and o in them is not a competitor.  Unfiltered, a triple's own
+        relation is a candidate and counts as its own competitor, as an entity does in evaluate().  Rows with unseen labels
+        are dropped.  The result feeds mrr_score / hits_at_n_score as is.  One 1-vs-all pass over the relation table per chunk
+        of queries (amdkge_relation_scores); works on every placement."""
+        if ranking_strategy not in ("best", "middle", "worst"):
+            raise ValueError("`ranking_strategy` must be 'worst', 'best' or 'middle', got {!r}.".format(ranking_strategy))
+        if not self.is_fitted:
+            raise ValueError("Model is not fitted.")
+        if use_filter is None:
+            use_filter = False
+        if not isinstance(use_filter, (bool, dict)):
+            raise ValueError("`use_filter` must be False, True or a dict of datasets.")
+        Xi = self._index_test(x)
+        if Xi.shape[0] == 0:
+            return np.zeros((0, 1), dtype=np.int32)
+        subset = None
+        if relations_subset is not None and len(relations_subset) > 0:
+            subset = np.asarray(self.data_indexer.get_indexes(np.asarray(relations_subset), "r"))
+        fi = self._pair_filter_index(use_filter, Xi)
+        return self._placement.rank_relations(Xi, fi, subset, ranking_strategy).cpu().numpy().reshape(-1, 1)
 
     # ------------------------------------------------------------------------------------ accessors
     def is_fit(self):

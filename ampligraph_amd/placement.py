@@ -139,6 +139,46 @@ class Replicated:
             eng.rank_sides(xs, jobs, strategy, ent_ids, subset_pos)   # the sides run beside each other
         return ranks
 
+    # ---- relation prediction: the relation table is whole in every placement, so every rank computes every query
+    def _relation_chunks(self, Xd):
+        """(c0, c1, the triples Xd[c0:c1] in self.engine's row index space) -- collective where localise() is."""
+        yield 0, int(Xd.shape[0]), Xd
+
+    def _relation_subset(self, cand):
+        """candidate relation ids (or None) -> (rel_ids, subset_pos) device tensors; a repeated id keeps its last position"""
+        if cand is None:
+            return None, None
+        eng = self.engine
+        ids = np.asarray(cand, dtype=np.int32)
+        pos = np.full(eng.n_rels, -1, dtype=np.int32)
+        pos[ids] = np.arange(ids.shape[0], dtype=np.int32)
+        return torch.as_tensor(ids).to(eng.device), torch.as_tensor(pos).to(eng.device)
+
+    def rank_relations(self, Xi, pfi, subset, strategy):
+        """int32 device ranks (n,) of each test triple's relation among the candidate relations (all, or the ids `subset`), the
+        same on every rank; pfi: PairFilterIndex or None."""
+        eng = self.engine
+        rel_ids, subset_pos = self._relation_subset(subset)
+        Xd = torch.as_tensor(Xi).to(eng.device)
+        ranks = torch.empty(int(Xd.shape[0]), dtype=torch.int32, device=eng.device)
+        for c0, c1, xl in self._relation_chunks(Xd):
+            flt = pfi.device_filter(eng, Xd[c0:c1]) if pfi is not None else None   # (on the GLOBAL ids)
+            ranks[c0:c1] = eng.relation_rank(xl, strategy, flt, rel_ids, subset_pos)[0]
+        return ranks
+
+    def select_relations(self, Xd, k, cand, pfi):
+        """The k best candidate relations of every (s, o) pair of the int32 device triples Xd (global ids): (positions int64
+        [n, k] into `cand` / the relation table, -1 = missing; scores [n, k]) as numpy arrays, the same on every rank."""
+        eng = self.engine
+        rel_ids = self._relation_subset(cand)[0]
+        n = int(Xd.shape[0])
+        pos = torch.empty(n, int(k), dtype=torch.int32, device=eng.device)
+        val = torch.empty(n, int(k), dtype=torch.float32, device=eng.device)
+        for c0, c1, xl in self._relation_chunks(Xd):
+            flt = pfi.device_filter(eng, Xd[c0:c1]) if pfi is not None else None
+            pos[c0:c1], val[c0:c1] = eng.relation_topk(xl, k, rel_ids, flt)
+        return pos.cpu().numpy().astype(np.int64), val.cpu().numpy()
+
     # ---- checkpoints
     def save(self, filepath, loop):
         """The arrays of <filepath>.npz on the rank that writes it, None on the others (collective).  Replicated tables:
@@ -230,6 +270,12 @@ class Rows(Replicated):
         CH = self.m.EVAL_CHUNK_SHARDED   # every rank fetches the rows it lacks and scores all triples
         outs = [self.engine.score(self.localise(Xd[c0:c0 + CH])) for c0 in range(0, int(Xd.shape[0]), CH)]
         return torch.cat(outs) if outs else torch.zeros(0, dtype=torch.float32, device=Xd.device)
+
+    def _relation_chunks(self, Xd):
+        CH = self.m.EVAL_CHUNK_SHARDED   # as score(): every rank fetches the s / o rows it lacks behind its shard, chunk by chunk
+        for c0 in range(0, int(Xd.shape[0]), CH):
+            c1 = min(int(Xd.shape[0]), c0 + CH)
+            yield c0, c1, self.localise(Xd[c0:c1])
 
     def select(self, pick, cand, nq, k, largest=True):
         """Every rank selects among ITS rows, the W partial lists (global ids, values) are gathered and merged by a second

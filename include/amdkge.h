@@ -526,6 +526,44 @@ int amdkge_discover_select(const float* d_scores, int64_t n, int64_t m, int64_t 
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Relation prediction (kge_relation.hip, kge_filter.hip; no counterpart in the reference beyond query_topn's single-query relation
+ * branch, discovery/discovery.py:1096-1120, which materialises one triple per candidate): which relation holds between s and o?
+ *
+ * amdkge_relation_scores: d_scores[i * ld + j] = the score of (s_i, r_j, o_i) for query i = row i of d_triples [n, 3] (the predicate
+ *   column is ignored) and candidate j = relation row rel_lo + j, or d_rel_ids[rel_lo + j] when d_rel_ids is given (rel_lo / rel_hi
+ *   then index that list), j < rel_hi - rel_lo <= ld; columns beyond are left untouched.  Every score has the BITS amdkge_score
+ *   returns for the materialised triple (same unit -> lane map, per-lane order, reduction tree and final scaling), for all five models
+ *   and both row layouts.  A wave keeps the s / o fragments of several queries in registers and reads each relation row once for all
+ *   of them; nothing is materialised.  RotatE: the declared cos / sin of the candidates' phases are formed once per call in d_work
+ *   (amdkge_relation_workspace_bytes(m, rel_hi - rel_lo) bytes; 0 for the other models, whose d_work may be NULL; -1 for bad arguments).
+ * amdkge_relation_rank_counts: the rank counts of a true relation against a score block d_scores [n, m] (leading dimension ld), in the
+ *   conventions of the entity sides so that amdkge_rank_compose turns them into ranks: with q = trunc(score * 1000) and d_pos [n] the
+ *   positives' scores (amdkge_score),
+ *     d_counts [n, 2] += (#{j : q(pos_i) < q(col_j)}, #{j : q(pos_i) == q(col_j)})   -- the true relation's own column is a
+ *                        competitor like any other unless the filter holds the statement, as for entities;
+ *     d_sub [n]       += #{j : q(pos_i) <= q(col_j) and the relation of column j is among d_flt_ids[d_flt_lo[i] .. d_flt_hi[i])}
+ *                        (the ranges of amdkge_pair_filter_ranges, ids ascending inside a range; three NULLs: unfiltered, d_sub unused).
+ *   Column j stands for relation d_col_ids[j], or id_base + j when d_col_ids is NULL.  d_subset_pos (int32 [n_rels], -1 = not a
+ *   candidate; may be NULL) maps a relation to ITS column when a subset is ranked: a column counts in d_sub only if
+ *   d_subset_pos[its relation] is that column, so a relation listed twice is subtracted once (the last one, as on the entity sides).
+ * amdkge_pair_filter_build / amdkge_pair_filter_ranges: amdkge_filter_build's CSR keyed by the PAIR -- group key s * n_ents + o, values
+ *   the SET of relations seen between the two, ascending -- with the same arrays, the same workspace
+ *   (amdkge_filter_build_workspace_bytes) and the same limits, and the lookup of a batch of [n, 3] triples in it (0, 0 for an absent
+ *   pair).  Top-n needs no kernel of its own: amdkge_topk_rows_excluding over the score block with d_col_ids = the relation ids.
+ * All fail with AMDKGE_EINVAL before any launch for bad sizes, NULL pointers and a range array without its two siblings; n == 0 is a
+ * no-op. */
+int64_t amdkge_relation_workspace_bytes(const amdkge_model* m, int64_t n_cand);
+int amdkge_relation_scores(const amdkge_model* m, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t n,
+                           const int32_t* d_rel_ids, int64_t rel_lo, int64_t rel_hi, float* d_scores, int64_t ld, void* d_work, void* stream);
+int amdkge_relation_rank_counts(const float* d_scores, int64_t n, int64_t m, int64_t ld, const float* d_pos, const int32_t* d_col_ids,
+                                int64_t id_base, const int64_t* d_flt_lo, const int64_t* d_flt_hi, const int32_t* d_flt_ids,
+                                const int32_t* d_subset_pos, int32_t* d_counts, int32_t* d_sub, void* stream);
+int amdkge_pair_filter_build(const int32_t* d_triples, int64_t m, int64_t n_ents, int64_t n_rels, int64_t* d_keys, int64_t* d_start,
+                             int32_t* d_ids, int64_t* d_counts, void* d_work, void* stream);
+int amdkge_pair_filter_ranges(const int64_t* d_keys, const int64_t* d_start, int64_t n_keys, const int32_t* d_triples, int64_t n,
+                              int64_t n_ents, int64_t* d_lo, int64_t* d_hi, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU data path (one process per GPU; the host issues the RCCL collectives between these calls -- see
  * ampligraph_amd/sharded.py and trainer.py).  The reference has no multi-device path; what these replace is its
  * partitioned training loop, ScoringBasedEmbeddingModel.py:227,259-261 (corruptions from the partition's entities) and
