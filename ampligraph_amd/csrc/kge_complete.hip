@@ -6,17 +6,6 @@
 
 namespace kge {
 
-// is `id` one of the row's excluded ids?  binary search in the ascending range ids[lo .. hi) (amdkge_filter_build's order)
-__device__ __forceinline__ bool complete_excluded(const int32_t* __restrict__ ids, int64_t lo, int64_t hi, int64_t id) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const int64_t v = ids[mid];
-        if (v == id) return true;
-        if (v < id) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
-
 // One workgroup per row: the streaming selection of topk_rows_kernel (kge_discovery.hip; same key, same merges, so the same order)
 // with a membership test in front of the staging buffer.  Only a column whose key beats the current k-th best is looked up: after
 // the first merge that is a handful of columns per row, the known facts among them (they score highest), so the usual column costs
@@ -43,7 +32,7 @@ __global__ __launch_bounds__(256) void topk_rows_excluding_kernel(const float* _
             const unsigned long long key = ((unsigned long long)sortable(row[c]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
             if (key > kth) {
                 const int64_t id = col_ids ? (int64_t)col_ids[c] : id_base + c;
-                if (!(has_own && id == own_id) && !complete_excluded(ex_ids, lo, hi, id)) buf[TOPK_MAX + atomicAdd(&n_stage, 1)] = key;
+                if (!(has_own && id == own_id) && !sorted_contains(ex_ids, lo, hi, id)) buf[TOPK_MAX + atomicAdd(&n_stage, 1)] = key;
             }
         }
         __syncthreads();

@@ -168,6 +168,17 @@ __device__ __forceinline__ void atomic_add_f32_wg(float* p, float v) {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// is `id` in the ascending range ids[lo .. hi)?  (the id order inside a group of amdkge_filter_build / amdkge_pair_filter_build)
+__device__ __forceinline__ bool sorted_contains(const int32_t* __restrict__ ids, int64_t lo, int64_t hi, int64_t id) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const int64_t v = ids[mid];
+        if (v == id) return true;
+        if (v < id) lo = mid + 1; else hi = mid;
+    }
+    return false;
+}
+
 // ----------------------------------------------------------------------------------------------
 // Scoring-model arithmetic on one "unit": one float of each row (TransE, DistMult) or one complex
 // component pair (ComplEx, HolE, RotatE: re at column c, im at column k+c).
@@ -178,6 +189,16 @@ struct ModelTraits {
     static constexpr bool kComplex = (MODEL == AMDKGE_COMPLEX || MODEL == AMDKGE_HOLE || MODEL == AMDKGE_ROTATE);
     static constexpr int NC = kComplex ? 2 : 1;
 };
+
+// KGE_MODEL_DISPATCH(model, F): run F(MODEL) with the scoring type a compile-time constant.  HolE runs ComplEx's instantiations: its
+// fp32(2/k) scale reaches the kernels through ModelConst (folded into dL/dscore; the column-sharded scores apply it in amdkge_cols_loss).
+#define KGE_MODEL_DISPATCH(model, F)                         \
+    switch (model) {                                         \
+        case AMDKGE_TRANSE: F(AMDKGE_TRANSE); break;         \
+        case AMDKGE_DISTMULT: F(AMDKGE_DISTMULT); break;     \
+        case AMDKGE_ROTATE: F(AMDKGE_ROTATE); break;         \
+        default: F(AMDKGE_COMPLEX); break;                   \
+    }
 
 struct ModelConst {
     float score_scale;   // HolE: fp32(2/k) (HolE.py:45); others 1

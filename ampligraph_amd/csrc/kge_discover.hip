@@ -17,13 +17,7 @@ __device__ __forceinline__ bool select_non_finite(float v) { return (__float_as_
 // is column c one of the row's filter ids?  LDS bitmap of the columns, or a binary search in the ascending id list
 __device__ __forceinline__ bool select_masked(const uint32_t* bitmap, bool use_bitmap, const int32_t* __restrict__ ids, int64_t lo, int64_t hi, int64_t c) {
     if (use_bitmap) return (bitmap[c >> 5] >> (c & 31)) & 1u;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const int64_t v = ids[mid];
-        if (v == c) return true;
-        if (v < c) lo = mid + 1; else hi = mid;
-    }
-    return false;
+    return sorted_contains(ids, lo, hi, c);
 }
 
 // One workgroup per query row.  Sweep one: streaming top-R of the quantised keys of the counted columns (the selection of

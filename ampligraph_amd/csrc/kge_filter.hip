@@ -10,8 +10,10 @@
 //   2. device radix sort of the keys (rocPRIM, only the bits R * N^2 needs)
 //   3. flags "new key" / "new group" per sorted position, one exclusive scan of the packed pair of counters (rocPRIM)
 //   4. scatter: ids[unique position] = key % N; keys[group] = key / N, start[group] = unique position   (filter_emit_kernel)
-// The per-triple lookup into this index is amdkge_filter_ranges (kge_rank_filter.hip).  HBM-bound integer work: 310 k filter
-// triples at C2 are 2.5 MB of keys -- microseconds; the point is that evaluate() no longer spends 15 ms in host sorts.
+// HBM-bound integer work: 310 k filter triples at C2 are 2.5 MB of keys -- microseconds; the point is that evaluate() no longer
+// spends 15 ms in host sorts.
+// The per-triple lookup into this index (amdkge_filter_ranges, amdkge_pair_filter_ranges) is one lower-bound kernel below; build and
+// lookup take a triple's group key from the same function (filter_group_key).
 #include <string.h>
 
 #include <hip/hip_runtime.h>
@@ -25,11 +27,37 @@ namespace kge {
 // group and value is then R instead of N
 constexpr int FILTER_KEY_PAIR = 4;
 
-__global__ void filter_keys_kernel(const int32_t* __restrict__ tri, int64_t m, int side, uint64_t N, uint64_t R, uint64_t* __restrict__ keys) {
+// THE definition of the three key forms: the group a triple belongs to.  The build sorts by group * divisor + value, the lookup
+// searches the sorted groups for the query's.
+//   AMDKGE_SIDE_S: group (p, o), value s      AMDKGE_SIDE_O: group (s, p), value o      FILTER_KEY_PAIR: group (s, o), value p
+__host__ __device__ inline uint64_t filter_group_key(int form, uint64_t s, uint64_t p, uint64_t o, uint64_t N, uint64_t R) {
+    return form == FILTER_KEY_PAIR ? s * N + o : form == AMDKGE_SIDE_S ? p * N + o : s * R + p;
+}
+__host__ __device__ inline uint64_t filter_key_divisor(int form, uint64_t N, uint64_t R) { return form == FILTER_KEY_PAIR ? R : N; }
+
+__global__ void filter_keys_kernel(const int32_t* __restrict__ tri, int64_t m, int form, uint64_t N, uint64_t R, uint64_t* __restrict__ keys) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const uint64_t s = (uint64_t)tri[3 * i], p = (uint64_t)tri[3 * i + 1], o = (uint64_t)tri[3 * i + 2];
-    keys[i] = (side == FILTER_KEY_PAIR) ? (s * N + o) * R + p : (side == AMDKGE_SIDE_S) ? (p * N + o) * N + s : (s * R + p) * N + o;
+    const uint64_t value = form == FILTER_KEY_PAIR ? p : form == AMDKGE_SIDE_S ? s : o;
+    keys[i] = filter_group_key(form, s, p, o, N, R) * filter_key_divisor(form, N, R) + value;
+}
+
+// the lookup: one thread per query triple, lower_bound of its group key in the sorted group keys
+__global__ void filter_ranges_kernel(const int64_t* keys, const int64_t* start, int64_t n_keys, const int32_t* triples, int64_t n, int form,
+                                     int64_t n_ents, int64_t n_rels, int64_t* lo_out, int64_t* hi_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t q = (int64_t)filter_group_key(form, (uint64_t)triples[3 * i], (uint64_t)triples[3 * i + 1], (uint64_t)triples[3 * i + 2],
+                                                (uint64_t)n_ents, (uint64_t)n_rels);
+    int64_t a = 0, b = n_keys;
+    while (a < b) {
+        const int64_t m = (a + b) >> 1;
+        if (keys[m] < q) a = m + 1; else b = m;
+    }
+    const bool hit = a < n_keys && keys[a] == q;
+    lo_out[i] = hit ? start[a] : 0;
+    hi_out[i] = hit ? start[a + 1] : 0;
 }
 
 // low 32 bits: 1 where a NEW KEY starts (duplicates of a triple across the filter datasets collapse), high 32 bits: 1 where a
@@ -100,9 +128,19 @@ extern "C" int64_t amdkge_filter_build_workspace_bytes(int64_t m, int64_t n_ents
     return (int64_t)p.total;
 }
 
-// the build behind both entry points; form: AMDKGE_SIDE_S / AMDKGE_SIDE_O / FILTER_KEY_PAIR (arguments already validated)
-static int filter_build_run(const int32_t* d_triples, int64_t m, int form, int64_t n_ents, int64_t n_rels, int64_t* d_keys, int64_t* d_start,
-                            int32_t* d_ids, int64_t* d_counts, void* d_work, hipStream_t st) {
+static int filter_error(int code, const char* who, const char* what) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return set_error(code, msg);
+}
+
+// the build behind both entry points; form: AMDKGE_SIDE_S / AMDKGE_SIDE_O / FILTER_KEY_PAIR, who: the entry point, for the messages
+static int filter_build_run(const char* who, const int32_t* d_triples, int64_t m, int form, int64_t n_ents, int64_t n_rels, int64_t* d_keys,
+                            int64_t* d_start, int32_t* d_ids, int64_t* d_counts, void* d_work, hipStream_t st) {
+    if (m < 0 || n_ents <= 0 || n_rels <= 0 || m > 0xFFFFFFFFll) return filter_error(AMDKGE_EINVAL, who, "bad sizes (at most 2^32 - 1 filter triples)");
+    if ((long double)n_rels * (long double)n_ents * (long double)n_ents >= 9.2e18L)
+        return filter_error(AMDKGE_EUNSUPPORTED, who, "n_rels * n_ents^2 does not fit the packed 64-bit sort keys");
+    if (!d_start || !d_counts) return filter_error(AMDKGE_EINVAL, who, "NULL pointer");
     if (m == 0) {
         if (hipError_t e = hipMemsetAsync(d_start, 0, 8, st)) return set_error_hip(e, "hipMemsetAsync(filter start)");
         if (hipError_t e = hipMemsetAsync(d_counts, 0, 16, st)) return set_error_hip(e, "hipMemsetAsync(filter counts)");
@@ -111,7 +149,7 @@ static int filter_build_run(const int32_t* d_triples, int64_t m, int form, int64
     if (!d_triples || !d_keys || !d_ids || !d_work) return set_error(AMDKGE_EINVAL, "filter_build: NULL pointer");
     FilterPlan p;
     if (make_filter_plan(m, n_ents, n_rels, p)) return set_error(AMDKGE_EHIP, "filter_build: rocPRIM size query failed");
-    const uint64_t div = form == FILTER_KEY_PAIR ? (uint64_t)n_rels : (uint64_t)n_ents;   // key = group * div + value
+    const uint64_t div = filter_key_divisor(form, (uint64_t)n_ents, (uint64_t)n_rels);   // key = group * div + value
     char* w = (char*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
     uint64_t* a = (uint64_t*)(w + p.off_a);
     uint64_t* b = (uint64_t*)(w + p.off_b);
@@ -130,49 +168,38 @@ static int filter_build_run(const int32_t* d_triples, int64_t m, int form, int64
     return check_launch("filter_emit");
 }
 
+// the lookup behind both entry points (the pair form's group key has no n_rels in it: its entry point passes 1)
+static int filter_ranges_run(const char* who, const int64_t* d_keys, const int64_t* d_start, int64_t n_keys, const int32_t* d_triples, int64_t n,
+                             int form, int64_t n_ents, int64_t n_rels, int64_t* d_lo, int64_t* d_hi, hipStream_t st) {
+    if (n < 0 || n_keys < 0 || n_ents <= 0 || n_rels <= 0) return filter_error(AMDKGE_EINVAL, who, "bad sizes");
+    if (n == 0) return AMDKGE_OK;
+    if (!d_triples || !d_lo || !d_hi || (n_keys > 0 && (!d_keys || !d_start))) return filter_error(AMDKGE_EINVAL, who, "NULL pointer");
+    hipLaunchKernelGGL(filter_ranges_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_keys, d_start, n_keys, d_triples, n, form, n_ents,
+                       n_rels, d_lo, d_hi);
+    return check_launch(who);
+}
+
 extern "C" int amdkge_filter_build(const int32_t* d_triples, int64_t m, int32_t side, int64_t n_ents, int64_t n_rels,
                                    int64_t* d_keys, int64_t* d_start, int32_t* d_ids, int64_t* d_counts, void* d_work, void* stream) {
     if (side != AMDKGE_SIDE_S && side != AMDKGE_SIDE_O) return set_error(AMDKGE_EINVAL, "filter_build: side must be AMDKGE_SIDE_S or AMDKGE_SIDE_O");
-    if (m < 0 || n_ents <= 0 || n_rels <= 0 || m > 0xFFFFFFFFll) return set_error(AMDKGE_EINVAL, "filter_build: bad sizes (at most 2^32 - 1 filter triples)");
-    if ((long double)n_rels * (long double)n_ents * (long double)n_ents >= 9.2e18L)
-        return set_error(AMDKGE_EUNSUPPORTED, "filter_build: n_rels * n_ents^2 does not fit the packed 64-bit sort keys");
-    if (!d_start || !d_counts) return set_error(AMDKGE_EINVAL, "filter_build: NULL pointer");
-    return filter_build_run(d_triples, m, (int)side, n_ents, n_rels, d_keys, d_start, d_ids, d_counts, d_work, (hipStream_t)stream);
+    return filter_build_run("filter_build", d_triples, m, (int)side, n_ents, n_rels, d_keys, d_start, d_ids, d_counts, d_work, (hipStream_t)stream);
 }
 
 // Relation prediction's filter: the same CSR keyed by the PAIR, group key (s * n_ents + o) with the SET of relations seen between
 // the two (workspace: amdkge_filter_build_workspace_bytes, the plan is the same)
 extern "C" int amdkge_pair_filter_build(const int32_t* d_triples, int64_t m, int64_t n_ents, int64_t n_rels, int64_t* d_keys, int64_t* d_start,
                                         int32_t* d_ids, int64_t* d_counts, void* d_work, void* stream) {
-    if (m < 0 || n_ents <= 0 || n_rels <= 0 || m > 0xFFFFFFFFll) return set_error(AMDKGE_EINVAL, "pair_filter_build: bad sizes (at most 2^32 - 1 filter triples)");
-    if ((long double)n_rels * (long double)n_ents * (long double)n_ents >= 9.2e18L)
-        return set_error(AMDKGE_EUNSUPPORTED, "pair_filter_build: n_rels * n_ents^2 does not fit the packed 64-bit sort keys");
-    if (!d_start || !d_counts) return set_error(AMDKGE_EINVAL, "pair_filter_build: NULL pointer");
-    return filter_build_run(d_triples, m, FILTER_KEY_PAIR, n_ents, n_rels, d_keys, d_start, d_ids, d_counts, d_work, (hipStream_t)stream);
+    return filter_build_run("pair_filter_build", d_triples, m, FILTER_KEY_PAIR, n_ents, n_rels, d_keys, d_start, d_ids, d_counts, d_work, (hipStream_t)stream);
 }
 
-// pair lookup: one thread per query, lower_bound in the sorted (s, o) keys
-__global__ void pair_filter_ranges_kernel(const int64_t* keys, const int64_t* start, int64_t n_keys, const int32_t* triples, int64_t n, int64_t n_ents,
-                                          int64_t* lo_out, int64_t* hi_out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t q = (int64_t)triples[3 * i] * n_ents + (int64_t)triples[3 * i + 2];
-    int64_t a = 0, b = n_keys;
-    while (a < b) {
-        const int64_t m = (a + b) >> 1;
-        if (keys[m] < q) a = m + 1; else b = m;
-    }
-    const bool hit = a < n_keys && keys[a] == q;
-    lo_out[i] = hit ? start[a] : 0;
-    hi_out[i] = hit ? start[a + 1] : 0;
+extern "C" int amdkge_filter_ranges(const int64_t* d_keys, const int64_t* d_start, int64_t n_keys, const int32_t* d_triples,
+                                    int64_t n, int32_t side, int64_t n_ents, int64_t n_rels, int64_t* d_lo, int64_t* d_hi,
+                                    void* stream) {
+    if (side != AMDKGE_SIDE_S && side != AMDKGE_SIDE_O) return set_error(AMDKGE_EINVAL, "filter_ranges: side must be AMDKGE_SIDE_S or AMDKGE_SIDE_O");
+    return filter_ranges_run("filter_ranges", d_keys, d_start, n_keys, d_triples, n, (int)side, n_ents, n_rels, d_lo, d_hi, (hipStream_t)stream);
 }
 
 extern "C" int amdkge_pair_filter_ranges(const int64_t* d_keys, const int64_t* d_start, int64_t n_keys, const int32_t* d_triples, int64_t n,
                                          int64_t n_ents, int64_t* d_lo, int64_t* d_hi, void* stream) {
-    if (n < 0 || n_keys < 0 || n_ents <= 0) return set_error(AMDKGE_EINVAL, "pair_filter_ranges: bad sizes");
-    if (n == 0) return AMDKGE_OK;
-    if (!d_triples || !d_lo || !d_hi || (n_keys > 0 && (!d_keys || !d_start))) return set_error(AMDKGE_EINVAL, "pair_filter_ranges: NULL pointer");
-    hipLaunchKernelGGL(pair_filter_ranges_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_keys, d_start, n_keys,
-                       d_triples, n, n_ents, d_lo, d_hi);
-    return check_launch("pair_filter_ranges");
+    return filter_ranges_run("pair_filter_ranges", d_keys, d_start, n_keys, d_triples, n, FILTER_KEY_PAIR, n_ents, 1, d_lo, d_hi, (hipStream_t)stream);
 }

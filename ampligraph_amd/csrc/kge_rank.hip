@@ -84,13 +84,7 @@ int run_prep(const amdkge_model* m, const float* d_ent, const float* d_rel, cons
     const ModelConst mc = model_const(m);
     const unsigned grid = (unsigned)((n + 3) / 4);
 #define KGE_PREP(M) hipLaunchKernelGGL((rank_prep_kernel<M>), dim3(grid), dim3(256), 0, st, d_ent, d_rel, d_triples, n, stored_k(m), g.K, side, g.QW, mc, w.Q, w.qpos)
-    switch (m->scoring_type) {
-        case AMDKGE_TRANSE: KGE_PREP(AMDKGE_TRANSE); break;
-        case AMDKGE_DISTMULT: KGE_PREP(AMDKGE_DISTMULT); break;
-        case AMDKGE_COMPLEX:
-        case AMDKGE_HOLE: KGE_PREP(AMDKGE_COMPLEX); break;
-        default: KGE_PREP(AMDKGE_ROTATE); break;
-    }
+    KGE_MODEL_DISPATCH(m->scoring_type, KGE_PREP)
 #undef KGE_PREP
     return check_launch("rank_prep");
 }

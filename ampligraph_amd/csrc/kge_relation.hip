@@ -166,16 +166,6 @@ __global__ __launch_bounds__(256) void relation_prep_kernel(const float* __restr
     out[(int64_t)j * K + k + u] = p[1];
 }
 
-__device__ __forceinline__ bool id_in_range(const int32_t* __restrict__ ids, int64_t lo, int64_t hi, int64_t id) {
-    while (lo < hi) {   // ids ascending inside a range (amdkge_pair_filter_build's order)
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const int64_t v = ids[mid];
-        if (v == id) return true;
-        if (v < id) lo = mid + 1; else hi = mid;
-    }
-    return false;
-}
-
 // One wave per row of the score block: quantised comparisons of the positive against every column, and -- for the columns whose
 // relation the row's filter holds -- the "<=" count amdkge_rank_compose subtracts.  With a subset, a relation's column is
 // subset_pos[id] (a repeated id: the last one, as on the entity sides).
@@ -196,7 +186,7 @@ __global__ __launch_bounds__(256) void relation_counts_kernel(const float* __res
         eq += qp == q ? 1 : 0;
         if (lo < hi && qp <= q) {
             const int64_t id = col_ids ? (int64_t)col_ids[j] : id_base + j;
-            if ((!subset_pos || subset_pos[id] == j) && id_in_range(flt_ids, lo, hi, id)) ++known;
+            if ((!subset_pos || subset_pos[id] == j) && sorted_contains(flt_ids, lo, hi, id)) ++known;
         }
     }
     gt = wave_sum_i(gt); eq = wave_sum_i(eq);
@@ -267,19 +257,16 @@ extern "C" int amdkge_relation_scores(const amdkge_model* m, const float* d_ent,
     RelArgs a{};
     a.ent = d_ent; a.rel = d_rel; a.triples = d_triples; a.rel_ids = d_rel_ids; a.rel_lo = rel_lo; a.n = n; a.m = (int)mc_;
     a.k = stored_k(m); a.K = row_floats(m); a.mc = model_const(m); a.out = d_scores; a.ld = ld;
-    switch (m->scoring_type) {
-        case AMDKGE_TRANSE: return launch_relation<AMDKGE_TRANSE>(a, st);
-        case AMDKGE_DISTMULT: return launch_relation<AMDKGE_DISTMULT>(a, st);
-        case AMDKGE_COMPLEX:
-        case AMDKGE_HOLE: return launch_relation<AMDKGE_COMPLEX>(a, st);
-        default: break;
+    if (m->scoring_type == AMDKGE_ROTATE) {
+        float* w = (float*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+        const int64_t units = mc_ * a.k;
+        hipLaunchKernelGGL(relation_prep_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, st, d_rel, d_rel_ids, rel_lo, a.m, a.k, a.K, a.mc, w);
+        if (int rc = check_launch("relation_prep")) return rc;
+        a.rel = w; a.rel_ids = nullptr; a.rel_lo = 0;
     }
-    float* w = (float*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    const int64_t units = mc_ * a.k;
-    hipLaunchKernelGGL(relation_prep_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, st, d_rel, d_rel_ids, rel_lo, a.m, a.k, a.K, a.mc, w);
-    if (int rc = check_launch("relation_prep")) return rc;
-    a.rel = w; a.rel_ids = nullptr; a.rel_lo = 0;
-    return launch_relation<AMDKGE_ROTATE>(a, st);
+#define KGE_RUN(M) return launch_relation<M>(a, st)
+    KGE_MODEL_DISPATCH(m->scoring_type, KGE_RUN)
+#undef KGE_RUN
 }
 
 extern "C" int amdkge_relation_rank_counts(const float* d_scores, int64_t n, int64_t m, int64_t ld, const float* d_pos, const int32_t* d_col_ids,

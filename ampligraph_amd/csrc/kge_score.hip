@@ -53,13 +53,9 @@ int score_dispatch(const amdkge_model* m, const float* d_ent, const float* d_rel
     // stored layout: padding units score exactly 0 in every model (RotatE: sqrt(0)), so the kernels just see ks units
     const int ks = stored_k(m), K = row_floats(m);
     const ModelConst mc = model_const(m);
-    switch (m->scoring_type) {
-        case AMDKGE_TRANSE: return launch_score<AMDKGE_TRANSE>(d_ent, d_rel, d_triples, n, ks, K, mc, d_scores, st);
-        case AMDKGE_DISTMULT: return launch_score<AMDKGE_DISTMULT>(d_ent, d_rel, d_triples, n, ks, K, mc, d_scores, st);
-        case AMDKGE_COMPLEX:
-        case AMDKGE_HOLE: return launch_score<AMDKGE_COMPLEX>(d_ent, d_rel, d_triples, n, ks, K, mc, d_scores, st);
-        default: return launch_score<AMDKGE_ROTATE>(d_ent, d_rel, d_triples, n, ks, K, mc, d_scores, st);
-    }
+#define KGE_RUN(M) return launch_score<M>(d_ent, d_rel, d_triples, n, ks, K, mc, d_scores, st)
+    KGE_MODEL_DISPATCH(m->scoring_type, KGE_RUN)
+#undef KGE_RUN
 }
 
 // calibrate(): one evaluation of the Platt-scaling objective and its gradient for a batch of scores.

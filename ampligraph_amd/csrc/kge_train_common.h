@@ -194,14 +194,4 @@ __device__ __forceinline__ void slot_sync() {
     }
 }
 
-// KGE_MODEL_DISPATCH(model, F): run F(MODEL) with the scoring type a compile-time constant.  HolE runs ComplEx's instantiations: its
-// fp32(2/k) scale reaches the kernels through ModelConst (folded into dL/dscore; the column-sharded scores apply it in amdkge_cols_loss).
-#define KGE_MODEL_DISPATCH(model, F)                         \
-    switch (model) {                                         \
-        case AMDKGE_TRANSE: F(AMDKGE_TRANSE); break;         \
-        case AMDKGE_DISTMULT: F(AMDKGE_DISTMULT); break;     \
-        case AMDKGE_ROTATE: F(AMDKGE_ROTATE); break;         \
-        default: F(AMDKGE_COMPLEX); break;                   \
-    }
-
 }  // namespace kge

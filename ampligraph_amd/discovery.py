@@ -46,6 +46,14 @@ def _known(indexer, values, type_of):
     return len(indexer.get_indexes(vals, type_of)) == len(vals)
 
 
+def _check_to_consider(ix, values, name, kind):
+    """query_topn's checks of `ents_to_consider` / `rels_to_consider` (kind "e" / "r")"""
+    if not isinstance(values, (list, np.ndarray)):
+        raise ValueError("`{}` must be a list or numpy array.".format(name))
+    if not _known(ix, values, kind):
+        raise ValueError("{} in `{}` have not been seen by the model.".format("Entities" if kind == "e" else "Relations", name))
+
+
 def query_topn(model, top_n=10, head=None, relation=None, tail=None, ents_to_consider=None, rels_to_consider=None):
     """Score every completion of the two given triple elements and return the top_n (triples (n,3) of raw labels,
     scores (n,) float32), ordered by decreasing score.  True statements are not filtered out (as in the reference)."""
@@ -65,17 +73,11 @@ def query_topn(model, top_n=10, head=None, relation=None, tail=None, ents_to_con
     if ents_to_consider is not None:
         if head and tail:
             raise ValueError("Cannot specify `ents_to_consider` and both `subject` and `object` arguments.")
-        if not isinstance(ents_to_consider, (list, np.ndarray)):
-            raise ValueError("`ents_to_consider` must be a list or numpy array.")
-        if not _known(ix, ents_to_consider, "e"):
-            raise ValueError("Entities in `ents_to_consider` have not been seen by the model.")
+        _check_to_consider(ix, ents_to_consider, "ents_to_consider", "e")
     if rels_to_consider is not None:
         if relation:
             raise ValueError("Cannot specify both `rels_to_consider` and `relation` arguments.")
-        if not isinstance(rels_to_consider, (list, np.ndarray)):
-            raise ValueError("`rels_to_consider` must be a list or numpy array.")
-        if not _known(ix, rels_to_consider, "r"):
-            raise ValueError("Relations in `rels_to_consider` have not been seen by the model.")
+        _check_to_consider(ix, rels_to_consider, "rels_to_consider", "r")
     eng, pl = model._engine, model._placement
     dev = eng.device
     one = lambda v, t: int(ix.get_indexes(np.asarray([v]), t)[0])   # noqa: E731
@@ -124,6 +126,56 @@ def _ids_or_fail(ix, labels, kind):
     return got
 
 
+def _fitted_model(model):
+    """the model behind a 1.x compat wrapper; it must be fitted"""
+    model = getattr(model, "model", model) if getattr(model, "is_backward", False) else model
+    if not model.is_fitted:
+        raise ValueError("Model is not fitted.")
+    return model
+
+
+def _batch_top_n(top_n):
+    top_n = int(top_n)
+    if top_n < 1 or top_n > TOPN_BATCH_MAX:
+        raise ValueError("`top_n` must be between 1 and {} (the device selection's limit); query_topn takes any top_n for a single "
+                         "query. Got {}.".format(TOPN_BATCH_MAX, top_n))
+    return top_n
+
+
+def _known_statements(use_filter):
+    """use_filter of the batched queries -> None (no filter) or a dict of datasets; a bare (m, 3) array stands for {"known": array}"""
+    if use_filter is True:
+        raise ValueError("`use_filter=True` has no meaning here (there is no evaluated set that could filter itself): pass a dict of "
+                         "datasets or an (m, 3) array of known statements.")
+    if use_filter is None or use_filter is False:
+        return None
+    if isinstance(use_filter, dict):
+        return use_filter
+    known = np.asarray(use_filter)
+    if known.ndim != 2 or known.shape[1] < 3:
+        raise ValueError("`use_filter` must be False, a dict of datasets or an (m, 3) array of known statements.")
+    return {"known": known}
+
+
+def _to_consider_ids(ix, values, name, kind):
+    """ids (int64) of a checked `*_to_consider` list; None for None or an empty list: every entity / relation"""
+    if values is None:
+        return None
+    _check_to_consider(ix, values, name, kind)
+    return np.asarray(ix.get_indexes(np.asarray(values), kind), dtype=np.int64) if len(values) > 0 else None
+
+
+def _empty_topn(top_n):
+    return np.empty((0, top_n), dtype=object), np.empty((0, top_n), dtype=np.float32)
+
+
+def _labels_or_none(ix, ids, have, kind):
+    """(n, top_n) object array: the labels of ids where `have`, None where a row ran out of candidates"""
+    labels = np.empty(ids.shape, dtype=object)
+    labels[have] = ix.get_indexes(ids[have], kind, "ind2raw")
+    return labels
+
+
 def query_topn_batch(model, queries, top_n=10, corrupt_side="o", use_filter=False, ents_to_consider=None, exclude_reflexive=False):
     """The top_n best completions of MANY incomplete statements, without the ones already known to be true: what a trained
     link predictor is asked for most (recommendations for every head), and what query_topn -- one query per call, true
@@ -147,38 +199,17 @@ def query_topn_batch(model, queries, top_n=10, corrupt_side="o", use_filter=Fals
 
     from .placement import Columns, Rows
 
-    model = getattr(model, "model", model) if getattr(model, "is_backward", False) else model   # 1.x compat wrappers
-    if not model.is_fitted:
-        raise ValueError("Model is not fitted.")
+    model = _fitted_model(model)
     if corrupt_side not in ("s", "o"):
         raise ValueError("`corrupt_side` must be 's' or 'o', got {!r}.".format(corrupt_side))
     Q = np.asarray(queries)
     if Q.ndim != 2 or Q.shape[1] != 2:
         raise ValueError("`queries` must have shape (n, 2): [subject, predicate] for corrupt_side='o', [predicate, object] for 's'; "
                          "got {}.".format(Q.shape))
-    top_n = int(top_n)
-    if top_n < 1 or top_n > TOPN_BATCH_MAX:
-        raise ValueError("`top_n` must be between 1 and {} (the device selection's limit); query_topn takes any top_n for a single "
-                         "query. Got {}.".format(TOPN_BATCH_MAX, top_n))
-    if use_filter is True:
-        raise ValueError("`use_filter=True` has no meaning here (there is no evaluated set that could filter itself): pass a dict of "
-                         "datasets or an (m, 3) array of known statements.")
-    if use_filter is None or use_filter is False:
-        use_filter = None
-    elif not isinstance(use_filter, dict):
-        known = np.asarray(use_filter)
-        if known.ndim != 2 or known.shape[1] < 3:
-            raise ValueError("`use_filter` must be False, a dict of datasets or an (m, 3) array of known statements.")
-        use_filter = {"known": known}
+    top_n = _batch_top_n(top_n)
+    use_filter = _known_statements(use_filter)
     ix = model.data_indexer
-    cand_ids = None
-    if ents_to_consider is not None:
-        if not isinstance(ents_to_consider, (list, np.ndarray)):
-            raise ValueError("`ents_to_consider` must be a list or numpy array.")
-        if not _known(ix, ents_to_consider, "e"):
-            raise ValueError("Entities in `ents_to_consider` have not been seen by the model.")
-        if len(ents_to_consider) > 0:
-            cand_ids = np.asarray(ix.get_indexes(np.asarray(ents_to_consider), "e"), dtype=np.int64)
+    cand_ids = _to_consider_ids(ix, ents_to_consider, "ents_to_consider", "e")
     ent_col, rel_col = (0, 1) if corrupt_side == "o" else (1, 0)
     fixed = _ids_or_fail(ix, Q[:, ent_col], "e")
     r_id = _ids_or_fail(ix, Q[:, rel_col], "r")
@@ -188,7 +219,7 @@ def query_topn_batch(model, queries, top_n=10, corrupt_side="o", use_filter=Fals
                                   "(entity_sharding) are out of its scope; query_topn works there")
     n = int(Q.shape[0])
     if n == 0:
-        return np.empty((0, top_n), dtype=object), np.empty((0, top_n), dtype=np.float32)
+        return _empty_topn(top_n)
     eng = model._engine
     dev = eng.device
     side = _ffi.SIDE_O if corrupt_side == "o" else _ffi.SIDE_S
@@ -206,10 +237,7 @@ def query_topn_batch(model, queries, top_n=10, corrupt_side="o", use_filter=Fals
         return pos, val
 
     ents, val = pl.select(pick, cand_ids, n, top_n)
-    gone = missing[0].cpu().numpy()
-    labels = np.empty((n, top_n), dtype=object)
-    labels[~gone] = ix.get_indexes(ents[~gone], "e", "ind2raw")
-    return labels, val.astype(np.float32)
+    return _labels_or_none(ix, ents, ~missing[0].cpu().numpy(), "e"), val.astype(np.float32)
 
 
 def query_topn_relations(model, pairs, top_n=10, use_filter=False, rels_to_consider=None):
@@ -230,49 +258,25 @@ def query_topn_relations(model, pairs, top_n=10, use_filter=False, rels_to_consi
     rank; on a row-sharded model it is a collective: call it on every rank)."""
     import torch
 
-    model = getattr(model, "model", model) if getattr(model, "is_backward", False) else model   # 1.x compat wrappers
-    if not model.is_fitted:
-        raise ValueError("Model is not fitted.")
+    model = _fitted_model(model)
     Q = np.asarray(pairs)
     if Q.ndim != 2 or Q.shape[1] != 2:
         raise ValueError("`pairs` must have shape (n, 2): [subject, object]; got {}.".format(Q.shape))
-    top_n = int(top_n)
-    if top_n < 1 or top_n > TOPN_BATCH_MAX:
-        raise ValueError("`top_n` must be between 1 and {} (the device selection's limit); query_topn takes any top_n for a single "
-                         "query. Got {}.".format(TOPN_BATCH_MAX, top_n))
-    if use_filter is True:
-        raise ValueError("`use_filter=True` has no meaning here (there is no evaluated set that could filter itself): pass a dict of "
-                         "datasets or an (m, 3) array of known statements.")
-    if use_filter is None or use_filter is False:
-        use_filter = None
-    elif not isinstance(use_filter, dict):
-        known = np.asarray(use_filter)
-        if known.ndim != 2 or known.shape[1] < 3:
-            raise ValueError("`use_filter` must be False, a dict of datasets or an (m, 3) array of known statements.")
-        use_filter = {"known": known}
+    top_n = _batch_top_n(top_n)
+    use_filter = _known_statements(use_filter)
     ix = model.data_indexer
-    cand = None
-    if rels_to_consider is not None:
-        if not isinstance(rels_to_consider, (list, np.ndarray)):
-            raise ValueError("`rels_to_consider` must be a list or numpy array.")
-        if not _known(ix, rels_to_consider, "r"):
-            raise ValueError("Relations in `rels_to_consider` have not been seen by the model.")
-        if len(rels_to_consider) > 0:
-            cand = np.asarray(ix.get_indexes(np.asarray(rels_to_consider), "r"), dtype=np.int64)
+    cand = _to_consider_ids(ix, rels_to_consider, "rels_to_consider", "r")
     s_id = _ids_or_fail(ix, Q[:, 0], "e")
     o_id = _ids_or_fail(ix, Q[:, 1], "e")
     n = int(Q.shape[0])
     if n == 0:
-        return np.empty((0, top_n), dtype=object), np.empty((0, top_n), dtype=np.float32)
+        return _empty_topn(top_n)
     dev = model._engine.device
     q = torch.as_tensor(np.stack([s_id, np.zeros_like(s_id), o_id], 1).astype(np.int32)).to(dev)   # the predicate column is ignored
     pfi = model._pair_filter_index(use_filter, None) if use_filter is not None else None
     pos, val = model._placement.select_relations(q, top_n, cand, pfi)
-    have = pos >= 0
     rel = pos if cand is None else cand[np.maximum(pos, 0)]
-    labels = np.empty((n, top_n), dtype=object)
-    labels[have] = ix.get_indexes(rel[have], "r", "ind2raw")
-    return labels, val.astype(np.float32)
+    return _labels_or_none(ix, rel, pos >= 0, "r"), val.astype(np.float32)
 
 
 def find_nearest_neighbours(kge_model, entities, n_neighbors=10, entities_subset=None, metric="euclidean"):

@@ -45,6 +45,15 @@ def _set_reg(opt_desc, reg, default_p):
     opt_desc.reg_p, opt_desc.reg_lambda, opt_desc.reg2_p, opt_desc.reg2_lambda = reg_fields(reg, default_p)
 
 
+def subset_positions(ids, n_rows, device):
+    """Candidate subset (int array of row ids) -> int32 device tensor [n_rows]: a row's column in the subset, -1 = not a candidate.
+    A repeated id keeps its LAST column (the reference's DenseHashTable.insert: last wins, :1639-1643)."""
+    ids = np.asarray(ids)
+    pos = np.full(int(n_rows), -1, dtype=np.int32)
+    pos[ids] = np.arange(ids.shape[0], dtype=np.int32)
+    return torch.as_tensor(pos).to(device)
+
+
 class KgeEngine:
     def __init__(self, scoring_type, k, n_ents, n_rels, max_rel_size=None, device=None, pad=True, k_full=None):
         """k_full: this engine holds a COLUMN SLICE -- k of the k_full units of every row -- of a k_full-unit model (column-sharded
@@ -306,17 +315,16 @@ class KgeEngine:
                                            n_el, reg_ptr, _stream()))
         opt_desc.reg_p = p0
 
+    def _flat_segments(self, lo, hi, reg_e, reg_r):
+        """[lo, hi) of the flat parameter vector -> [(a, b, regulariser)]: its entity part and its relation part (the padding
+        between / behind the tables holds zero parameters and zero gradients: nothing to sweep)"""
+        parts = ((max(lo, 0), min(hi, self._ne), reg_e), (max(lo, self._off), min(hi, self._off + self._nr), reg_r))
+        return [(a, b, lam) for a, b, lam in parts if b > a]
+
     def opt_step_flat(self, opt_desc, lo, hi, reg_e=0.0, reg_r=0.0, reg_slot=1):
         """Dense sweep over elements [lo, hi) of the flat parameter vector (sharded-optimizer data parallelism: a rank
         sweeps only its slice).  The slice may straddle the entity / relation boundary; the regulariser lambda follows."""
-        segs = []
-        a, b = max(lo, 0), min(hi, self._ne)
-        if b > a:
-            segs.append((a, b, reg_e))
-        # (the padding between / behind the tables holds zero parameters and zero gradients: nothing to sweep)
-        a, b = max(lo, self._off), min(hi, self._off + self._nr)
-        if b > a:
-            segs.append((a, b, reg_r))
+        segs = self._flat_segments(lo, hi, reg_e, reg_r)
         reg_ptr = C.c_void_p(self.loss_acc.data_ptr() + 8 * int(reg_slot))
         names = _ffi.OPT_SLOTS[self.opt_kind]
         if opt_desc.lazy:
@@ -375,13 +383,7 @@ class KgeEngine:
     def opt_step_merged(self, opt_desc, lo, hi, parts, n_parts, part_stride, reg_e=0.0, reg_r=0.0, reg_slot=1):
         """Sharded-optimizer data parallelism: sweep elements [lo, hi) of the flat parameter vector with the gradient
         sum_q parts[q * part_stride + (i - lo)] (amdkge_opt_step_merged: the W partial slices are summed inside the sweep)."""
-        segs = []
-        a, b = max(lo, 0), min(hi, self._ne)
-        if b > a:
-            segs.append((a, b, reg_e))
-        a, b = max(lo, self._off), min(hi, self._off + self._nr)
-        if b > a:
-            segs.append((a, b, reg_r))
+        segs = self._flat_segments(lo, hi, reg_e, reg_r)
         reg_ptr = C.c_void_p(self.loss_acc.data_ptr() + 8 * int(reg_slot))
         names = _ffi.OPT_SLOTS[self.opt_kind]
         p0 = int(opt_desc.reg_p)
@@ -408,10 +410,12 @@ class KgeEngine:
             int(step), int(row_offset), int(b_global), _ptr(out), _stream()))
         return out
 
-    def filter_build(self, triples, side, n_ents, n_rels):
-        """amdkge_filter_build: the CSR filter index of one side from the concatenated id triples (int32 [m,3] device tensor).
-        -> (keys int64 [n_groups], start int64 [n_groups + 1], ids int32 [n_unique]) device tensors.  One stream
-        synchronisation (the two counts come back to size the views); an index is built once per evaluate() and cached."""
+    def _filter_build(self, triples, side, n_ents, n_rels):
+        """One CSR filter index from the concatenated id triples (int32 [m,3] device tensor) -> (keys int64 [n_groups], start
+        int64 [n_groups + 1], ids int32 [n_unique]) device tensors.  side "s" | "o": amdkge_filter_build; None: the (s, o) pair
+        form, amdkge_pair_filter_build.  One stream synchronisation (the two counts come back to size the views); an index is
+        built once per evaluate() and cached."""
+        name = "filter_build" if side is not None else "pair_filter_build"
         m = int(triples.shape[0])
         keys = torch.empty(max(m, 1), dtype=torch.int64, device=self.device)
         start = torch.empty(m + 1, dtype=torch.int64, device=self.device)
@@ -419,21 +423,34 @@ class KgeEngine:
         counts = torch.zeros(2, dtype=torch.int64, device=self.device)
         need = int(self.lib.amdkge_filter_build_workspace_bytes(m, int(n_ents), int(n_rels)))
         if need < 0:
-            raise ValueError("filter_build: bad sizes")
+            raise ValueError(name + ": bad sizes")
         work = self._buf("filter_build_work", (need,), torch.uint8)
-        check(self.lib.amdkge_filter_build(_ptr(triples), m, 1 if side == "s" else 2, int(n_ents), int(n_rels), _ptr(keys), _ptr(start),
-                                           _ptr(ids), _ptr(counts), _ptr(work), _stream()))
+        form = () if side is None else (1 if side == "s" else 2,)
+        check(getattr(self.lib, "amdkge_" + name)(_ptr(triples), m, *form, int(n_ents), int(n_rels), _ptr(keys), _ptr(start), _ptr(ids),
+                                                  _ptr(counts), _ptr(work), _stream()))
         ng, nu = (int(c) for c in counts.tolist())
         return keys[:ng], start[:ng + 1], ids[:nu]
 
-    def filter_ranges(self, keys, start, triples, side, n_ents, n_rels):
-        """(lo, hi) int64 device tensors: each triple's range in a FilterIndex id array (amdkge_filter_ranges)."""
+    def _filter_ranges(self, keys, start, triples, side, n_ents, n_rels=None):
+        """(lo, hi) int64 device tensors: each triple's range in the id array of a filter index.  side 1 | 2 (subject / object):
+        amdkge_filter_ranges; None: the (s, o) pair form, amdkge_pair_filter_ranges."""
         n = int(triples.shape[0])
         lo = torch.empty(n, dtype=torch.int64, device=self.device)
         hi = torch.empty(n, dtype=torch.int64, device=self.device)
-        check(self.lib.amdkge_filter_ranges(_ptr(keys), _ptr(start), int(keys.shape[0]), _ptr(triples), n, int(side),
-                                            int(n_ents), int(n_rels), _ptr(lo), _ptr(hi), _stream()))
+        head, tail = (_ptr(keys), _ptr(start), int(keys.shape[0]), _ptr(triples), n), (_ptr(lo), _ptr(hi), _stream())
+        if side is None:
+            check(self.lib.amdkge_pair_filter_ranges(*head, int(n_ents), *tail))
+        else:
+            check(self.lib.amdkge_filter_ranges(*head, int(side), int(n_ents), int(n_rels), *tail))
         return lo, hi
+
+    def filter_build(self, triples, side, n_ents, n_rels):
+        """amdkge_filter_build: the CSR filter index of one side ("s" | "o"), see _filter_build."""
+        return self._filter_build(triples, "s" if side == "s" else "o", n_ents, n_rels)
+
+    def filter_ranges(self, keys, start, triples, side, n_ents, n_rels):
+        """(lo, hi) int64 device tensors: each triple's range in a FilterIndex id array (amdkge_filter_ranges; side 1 | 2)."""
+        return self._filter_ranges(keys, start, triples, side, n_ents, n_rels)
 
     def compose_ranks(self, counts, sub, strategy, out=None, out_stride=1):
         """(greater, equal) counts [+ filter subtraction] -> 1-based ranks (amdkge_rank_compose)."""
@@ -455,6 +472,39 @@ class KgeEngine:
 
     # ------------------------------------------------------------------ discovery (kge_discovery.hip, kge_rank_tile.hip, kge_rank.hip)
     SCORE_CHUNK_BYTES = 256 << 20   # bound of the transient (queries x candidates) score block
+
+    def _score_chunks(self, n, m):
+        """Query ranges [(c0, c1), ...] whose (queries x m candidates) fp32 score block stays under SCORE_CHUNK_BYTES."""
+        rows = max(1, min(n, self.SCORE_CHUNK_BYTES // max(4 * m, 1)))
+        return [(c0, min(n, c0 + rows)) for c0 in range(0, n, rows)]
+
+    def _corruption_blocks(self, triples, side, ent_ids, ent_lo, ent_hi):
+        """(c0, c1, block) per chunk of the query triples: block = the 1-vs-all scores fp32 [c1 - c0, ent_hi - ent_lo] of one
+        corruption side (amdkge_corruption_scores) in the reused "disc_scores" buffer -- valid until the next chunk."""
+        m = int(ent_hi) - int(ent_lo)
+        for c0, c1 in self._score_chunks(int(triples.shape[0]), m):
+            blk = self._buf("disc_scores", (c1 - c0, m), torch.float32)
+            work = self._workspace(c1 - c0)
+            check(self.lib.amdkge_corruption_scores(C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples[c0:c1]), c1 - c0, int(side),
+                                                    _ptr(ent_ids), int(ent_lo), int(ent_hi), _ptr(blk), m, _ptr(work), _stream()))
+            yield c0, c1, blk
+
+    def _relation_blocks(self, triples, rel_ids, m):
+        """(c0, c1, block) per chunk of the query triples: block = relation_scores fp32 [c1 - c0, m] of the m candidate relations
+        (all, or rel_ids) in the reused "rel_scores" buffer -- valid until the next chunk."""
+        for c0, c1 in self._score_chunks(int(triples.shape[0]), m):
+            blk = self._buf("rel_scores", (c1 - c0, m), torch.float32)
+            self._relation_block(triples[c0:c1], rel_ids, 0, m, blk, m)
+            yield c0, c1, blk
+
+    @staticmethod
+    def _flt_chunk(flt, c0, c1):
+        """the filter (lo, hi, ids) of queries [c0, c1); the id array is shared"""
+        return None if flt is None else (flt[0][c0:c1], flt[1][c0:c1], flt[2])
+
+    def _idx_val(self, n, k):
+        """the (idx int32 [n,k], val fp32 [n,k]) output pair of a selection"""
+        return (torch.empty(n, int(k), dtype=torch.int32, device=self.device), torch.empty(n, int(k), dtype=torch.float32, device=self.device))
 
     def topk_rows(self, vals, k, largest=True, col_scale=None, col_bias=None, payload=None):
         """(idx int32 [n,k], val fp32 [n,k]) of the k best entries per row of vals [n,m] (amdkge_topk_rows); with `payload`
@@ -478,8 +528,7 @@ class KgeEngine:
             idx[:, :kk] = (sel if payload is None else torch.gather(payload[:, :m].to(torch.int64), 1, sel)).to(torch.int32)
             val[:, :kk] = sv[:, :kk]
             return idx, val
-        idx = torch.empty(n, int(k), dtype=torch.int32, device=self.device)
-        val = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
+        idx, val = self._idx_val(n, k)
         check(self.lib.amdkge_topk_rows(_ptr(vals), n, m, int(vals.stride(0)), _ptr(col_scale), _ptr(col_bias), _ptr(payload), int(k), 1 if largest else 0,
                                         _ptr(idx), _ptr(val), _stream()))
         return idx, val
@@ -490,8 +539,7 @@ class KgeEngine:
         (amdkge_topk_rows_excluding; 1 <= k <= 1024).  Same order and missing-entry convention as topk_rows."""
         n, m = int(vals.shape[0]), int(vals.shape[1])
         lo, hi, ids = flt if flt is not None else (None, None, None)
-        idx = torch.empty(n, int(k), dtype=torch.int32, device=self.device)
-        val = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
+        idx, val = self._idx_val(n, k)
         check(self.lib.amdkge_topk_rows_excluding(_ptr(vals), n, m, int(vals.stride(0)) if n else m, _ptr(col_ids), int(id_base), _ptr(lo), _ptr(hi),
                                                   _ptr(ids), _ptr(own), int(k), _ptr(idx), _ptr(val), _stream()))
         return idx, val
@@ -505,52 +553,25 @@ class KgeEngine:
         n = int(triples.shape[0])
         if ent_hi is None:
             ent_hi = self.n_ents if ent_ids is None else int(ent_ids.shape[0])
-        m = int(ent_hi) - int(ent_lo)
-        rows = max(1, min(n, self.SCORE_CHUNK_BYTES // max(4 * m, 1)))
-        out_i = torch.empty(n, int(k), dtype=torch.int32, device=self.device)
-        out_v = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
+        out_i, out_v = self._idx_val(n, k)
         excluding = flt is not None or own is not None
         col_ids = None if ent_ids is None else ent_ids[int(ent_lo):int(ent_hi)]
-        for c0 in range(0, n, rows):
-            c1 = min(n, c0 + rows)
-            blk = self._buf("disc_scores", (c1 - c0, m), torch.float32)
-            work = self._workspace(c1 - c0)
-            check(self.lib.amdkge_corruption_scores(C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples[c0:c1]), c1 - c0, int(side),
-                                                    _ptr(ent_ids), int(ent_lo), int(ent_hi), _ptr(blk), m, _ptr(work), _stream()))
+        for c0, c1, blk in self._corruption_blocks(triples, side, ent_ids, ent_lo, ent_hi):
             if excluding:
-                f = None if flt is None else (flt[0][c0:c1], flt[1][c0:c1], flt[2])
-                i_, v_ = self.topk_rows_excluding(blk, k, col_ids, int(ent_lo), f, None if own is None else own[c0:c1])
+                out_i[c0:c1], out_v[c0:c1] = self.topk_rows_excluding(blk, k, col_ids, int(ent_lo), self._flt_chunk(flt, c0, c1),
+                                                                      None if own is None else own[c0:c1])
             else:
-                i_, v_ = self.topk_rows(blk, k)
-            out_i[c0:c1], out_v[c0:c1] = i_, v_
+                out_i[c0:c1], out_v[c0:c1] = self.topk_rows(blk, k)
         return out_i, out_v
 
     # ------------------------------------------------------------------ relation prediction (kge_relation.hip, kge_filter.hip)
     def pair_filter_build(self, triples, n_ents, n_rels):
-        """amdkge_pair_filter_build: the CSR of the relations known between every (s, o) pair of the id triples (int32 [m,3] device
-        tensor) -> (keys int64 [n_groups], start int64 [n_groups + 1], ids int32 [n_unique]) device tensors, as filter_build."""
-        m = int(triples.shape[0])
-        keys = torch.empty(max(m, 1), dtype=torch.int64, device=self.device)
-        start = torch.empty(m + 1, dtype=torch.int64, device=self.device)
-        ids = torch.empty(max(m, 1), dtype=torch.int32, device=self.device)
-        counts = torch.zeros(2, dtype=torch.int64, device=self.device)
-        need = int(self.lib.amdkge_filter_build_workspace_bytes(m, int(n_ents), int(n_rels)))
-        if need < 0:
-            raise ValueError("pair_filter_build: bad sizes")
-        work = self._buf("filter_build_work", (need,), torch.uint8)
-        check(self.lib.amdkge_pair_filter_build(_ptr(triples), m, int(n_ents), int(n_rels), _ptr(keys), _ptr(start), _ptr(ids), _ptr(counts),
-                                                _ptr(work), _stream()))
-        ng, nu = (int(c) for c in counts.tolist())
-        return keys[:ng], start[:ng + 1], ids[:nu]
+        """amdkge_pair_filter_build: the CSR of the relations known between every (s, o) pair of the id triples, see _filter_build."""
+        return self._filter_build(triples, None, n_ents, n_rels)
 
     def pair_filter_ranges(self, keys, start, triples, n_ents):
         """(lo, hi) int64 device tensors: each triple's (s, o) range in a PairFilterIndex id array (amdkge_pair_filter_ranges)."""
-        n = int(triples.shape[0])
-        lo = torch.empty(n, dtype=torch.int64, device=self.device)
-        hi = torch.empty(n, dtype=torch.int64, device=self.device)
-        check(self.lib.amdkge_pair_filter_ranges(_ptr(keys), _ptr(start), int(keys.shape[0]), _ptr(triples), n, int(n_ents), _ptr(lo), _ptr(hi),
-                                                 _stream()))
-        return lo, hi
+        return self._filter_ranges(keys, start, triples, None, n_ents)
 
     def _relation_block(self, triples, rel_ids, lo, hi, out, ld):
         work = None
@@ -559,11 +580,6 @@ class KgeEngine:
             work = self._buf("relation_work", (need,), torch.uint8)
         check(self.lib.amdkge_relation_scores(C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples), int(triples.shape[0]),
                                               _ptr(rel_ids), int(lo), int(hi), _ptr(out), int(ld), _ptr(work), _stream()))
-
-    def _relation_chunks(self, n, m):
-        """Query ranges whose (queries x candidates) score block stays under SCORE_CHUNK_BYTES, as corruption_topk chunks them."""
-        rows = max(1, min(max(n, 1), self.SCORE_CHUNK_BYTES // max(4 * m, 1)))
-        return [(c0, min(n, c0 + rows)) for c0 in range(0, n, rows)]
 
     def relation_scores(self, triples, rel_ids=None, out=None, rel_lo=0, rel_hi=None):
         """Scores fp32 [n, m] of (s_i, r_j, o_i) for every query row of `triples` (int32 [n,3] device tensor; the predicate column is
@@ -590,20 +606,14 @@ class KgeEngine:
         n = int(triples.shape[0])
         m = self.n_rels if rel_ids is None else int(rel_ids.shape[0])
         if rel_ids is not None and subset_pos is None:
-            at = np.full(self.n_rels, -1, dtype=np.int32)   # (on the host: a repeated id keeps its LAST column, as Replicated._rank)
-            at[rel_ids.cpu().numpy()] = np.arange(m, dtype=np.int32)
-            subset_pos = torch.as_tensor(at).to(self.device)
+            subset_pos = subset_positions(rel_ids.cpu().numpy(), self.n_rels, self.device)
         pos = self.score(triples)
         counts = torch.zeros(n, 2, dtype=torch.int32, device=self.device)
         sub = torch.zeros(n, dtype=torch.int32, device=self.device) if flt is not None else None
-        lo, hi, ids = flt if flt is not None else (None, None, None)
-        for c0, c1 in self._relation_chunks(n, m):
-            blk = self._buf("rel_scores", (c1 - c0, m), torch.float32)
-            self._relation_block(triples[c0:c1], rel_ids, 0, m, blk, m)
-            check(self.lib.amdkge_relation_rank_counts(_ptr(blk), c1 - c0, m, m, _ptr(pos[c0:c1]), _ptr(rel_ids), 0,
-                                                       _ptr(lo[c0:c1]) if flt is not None else _ptr(None),
-                                                       _ptr(hi[c0:c1]) if flt is not None else _ptr(None), _ptr(ids), _ptr(subset_pos),
-                                                       _ptr(counts[c0:c1]), _ptr(sub[c0:c1]) if sub is not None else _ptr(None), _stream()))
+        for c0, c1, blk in self._relation_blocks(triples, rel_ids, m):
+            lo, hi, ids = self._flt_chunk(flt, c0, c1) or (None, None, None)
+            check(self.lib.amdkge_relation_rank_counts(_ptr(blk), c1 - c0, m, m, _ptr(pos[c0:c1]), _ptr(rel_ids), 0, _ptr(lo), _ptr(hi), _ptr(ids),
+                                                       _ptr(subset_pos), _ptr(counts[c0:c1]), _ptr(None if sub is None else sub[c0:c1]), _stream()))
         return self.compose_ranks(counts, sub, strategy), counts, sub
 
     def relation_topk(self, triples, k, rel_ids=None, flt=None):
@@ -613,13 +623,9 @@ class KgeEngine:
         part in the selection (amdkge_topk_rows_excluding over each chunk's relation_scores block)."""
         n = int(triples.shape[0])
         m = self.n_rels if rel_ids is None else int(rel_ids.shape[0])
-        out_i = torch.empty(n, int(k), dtype=torch.int32, device=self.device)
-        out_v = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
-        for c0, c1 in self._relation_chunks(n, m):
-            blk = self._buf("rel_scores", (c1 - c0, m), torch.float32)
-            self._relation_block(triples[c0:c1], rel_ids, 0, m, blk, m)
-            f = None if flt is None else (flt[0][c0:c1], flt[1][c0:c1], flt[2])
-            out_i[c0:c1], out_v[c0:c1] = self.topk_rows_excluding(blk, k, rel_ids, 0, f, None)
+        out_i, out_v = self._idx_val(n, k)
+        for c0, c1, blk in self._relation_blocks(triples, rel_ids, m):
+            out_i[c0:c1], out_v[c0:c1] = self.topk_rows_excluding(blk, k, rel_ids, 0, self._flt_chunk(flt, c0, c1), None)
         return out_i, out_v
 
     def nearest_rows(self, q_rows, k, metric="euclidean", ent_ids=None, ent_lo=0, ent_hi=None, table=None):
@@ -638,16 +644,12 @@ class KgeEngine:
         col = torch.empty(m, dtype=torch.float32, device=self.device)
         cosine = metric == "cosine"
         check(self.lib.amdkge_row_sqnorms(_ptr(table), Kf, _ptr(ent_ids), int(ent_lo), m, -0.5, 1 if cosine else 0, _ptr(col), _stream()))
-        rows = max(1, min(n, self.SCORE_CHUNK_BYTES // max(4 * m, 1)))
-        out_i = torch.empty(n, int(k), dtype=torch.int32, device=self.device)
-        out_v = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
-        for c0 in range(0, n, rows):
-            c1 = min(n, c0 + rows)
+        out_i, out_v = self._idx_val(n, k)
+        for c0, c1 in self._score_chunks(n, m):
             blk = self._buf("disc_scores", (c1 - c0, m), torch.float32)
             check(self.lib.amdkge_row_dots(_ptr(q_rows[c0:c1]), c1 - c0, _ptr(table), Kf, _ptr(ent_ids), int(ent_lo), int(ent_hi), _ptr(blk), m,
                                            _stream()))
-            i_, v_ = self.topk_rows(blk, k, True, col if cosine else None, None if cosine else col)
-            out_i[c0:c1], out_v[c0:c1] = i_, v_
+            out_i[c0:c1], out_v[c0:c1] = self.topk_rows(blk, k, True, col if cosine else None, None if cosine else col)
         dist = torch.empty(n, int(k), dtype=torch.float32, device=self.device)
         check(self.lib.amdkge_pair_distances(_ptr(q_rows), n, _ptr(table), Kf, _ptr(ent_ids), int(ent_lo), _ptr(out_i), int(k), 1 if cosine else 0,
                                              _ptr(dist), _stream()))
@@ -843,19 +845,11 @@ class KgeEngine:
         amdkge_corruption_scores in chunks whose score block stays under SCORE_CHUNK_BYTES (as corruption_topk), each chunk
         straight into the selection.  -> (pairs int32 [c, 2] of (query, entity), thresholds int32 [n])."""
         n, m = int(triples.shape[0]), self.n_ents
-        rows = max(1, min(n, self.SCORE_CHUNK_BYTES // max(4 * m, 1)))
         out = [torch.empty(0, 2, dtype=torch.int32, device=self.device)]
         thr = torch.empty(n, dtype=torch.int32, device=self.device)
-        for c0 in range(0, n, rows):
-            c1 = min(n, c0 + rows)
-            blk = self._buf("disc_scores", (c1 - c0, m), torch.float32)
-            work = self._workspace(c1 - c0)
-            check(self.lib.amdkge_corruption_scores(C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples[c0:c1]), c1 - c0, int(side),
-                                                    None, 0, m, _ptr(blk), m, _ptr(work), _stream()))
-            f = None if flt is None else (flt[0][c0:c1], flt[1][c0:c1], flt[2])
-            p_, t_ = self.select_rows(blk, triples[c0:c1], side, R, margin_q, f, row_base=c0)
+        for c0, c1, blk in self._corruption_blocks(triples, side, None, 0, m):
+            p_, thr[c0:c1] = self.select_rows(blk, triples[c0:c1], side, R, margin_q, self._flt_chunk(flt, c0, c1), row_base=c0)
             out.append(p_)
-            thr[c0:c1] = t_
         return torch.cat(out), thr
 
     def platt_step(self, scores_pos, scores_neg, w, b, label_pos, label_neg, weight_pos, weight_neg):

@@ -324,11 +324,11 @@ class ScoringBasedEmbeddingModel:
         return self.history
 
     # ------------------------------------------------------------------------------------ filters
-    def _filter_index(self, use_filter, Xi):
-        """FilterIndex for evaluate(): the union of the given datasets (dict) or the evaluated data itself (True), all
-        indexed with the training id map (graph_data_loader.py:184-190,652-653).  The id mapping is host work (labels), the
-        index itself (sort + CSR) is built on the device (amdkge_filter_build); the last one is cached by content checksum, so
-        validation during fit() and repeated evaluate() calls reuse it."""
+    def _cached_index(self, cls, cache_attr, use_filter, Xi):
+        """An index of class `cls` over the union of the given datasets (dict) or the evaluated data itself (True), all indexed
+        with the training id map (graph_data_loader.py:184-190,652-653); None for no filter.  The id mapping is host work
+        (labels), the index itself (sort + CSR) is built on the device (kge_filter.hip).  The last dict's index is kept in
+        self.<cache_attr> = (content checksum key, index), so validation during fit() and repeated calls reuse it."""
         try:   # (content checksum of the filter arrays: xxh3 runs at ~10 GB/s, zlib's crc32 at ~2)
             from xxhash import xxh3_64_intdigest as _digest
         except Exception:   # pragma: no cover
@@ -344,45 +344,24 @@ class ScoringBasedEmbeddingModel:
                     break
                 key.append((a.shape, str(a.dtype), _digest(a.view(np.uint8).reshape(-1))))
             key = None if key is None else ("dict", tuple(key), self._n_ents, self._n_rels)
-            if key is not None and getattr(self, "_filter_cache", (None, None))[0] == key:
-                return self._filter_cache[1]
-            # (id mapping on the host -- labels are host data --, then the index itself is built on the device: kge_filter.hip)
-            fi = FilterIndex([self.data_indexer.get_indexes(a) for a in arrays], self._n_ents, self._n_rels, engine=self._engine)
+            if key is not None and getattr(self, cache_attr, (None, None))[0] == key:
+                return getattr(self, cache_attr)[1]
+            fi = cls([self.data_indexer.get_indexes(a) for a in arrays], self._n_ents, self._n_rels, engine=self._engine)
             if key is not None:
-                self._filter_cache = (key, fi)
+                setattr(self, cache_attr, (key, fi))
             return fi
         if use_filter:
-            return FilterIndex([Xi], self._n_ents, self._n_rels, engine=self._engine)
+            return cls([Xi], self._n_ents, self._n_rels, engine=self._engine)
         return None
+
+    def _filter_index(self, use_filter, Xi):
+        """FilterIndex for evaluate() (amdkge_filter_build), cached in _filter_cache."""
+        return self._cached_index(FilterIndex, "_filter_cache", use_filter, Xi)
 
     def _pair_filter_index(self, use_filter, Xi):
-        """PairFilterIndex for evaluate_relations() / query_topn_relations(): _filter_index's dict / True semantics with the
-        (s, o) pair as the key (the SET of relations known between the two), built on the device (amdkge_pair_filter_build);
-        a cache of its own holds the last dict's index by content checksum."""
-        try:
-            from xxhash import xxh3_64_intdigest as _digest
-        except Exception:   # pragma: no cover
-            from zlib import crc32 as _digest
-
-        if isinstance(use_filter, dict):
-            arrays = [_load_triples(v)[:, :3] for v in use_filter.values()]
-            key = []
-            for a in arrays:
-                a = np.ascontiguousarray(a)
-                if a.dtype == object:
-                    key = None
-                    break
-                key.append((a.shape, str(a.dtype), _digest(a.view(np.uint8).reshape(-1))))
-            key = None if key is None else ("dict", tuple(key), self._n_ents, self._n_rels)
-            if key is not None and getattr(self, "_pair_filter_cache", (None, None))[0] == key:
-                return self._pair_filter_cache[1]
-            fi = PairFilterIndex([self.data_indexer.get_indexes(a) for a in arrays], self._n_ents, self._n_rels, engine=self._engine)
-            if key is not None:
-                self._pair_filter_cache = (key, fi)
-            return fi
-        if use_filter:
-            return PairFilterIndex([Xi], self._n_ents, self._n_rels, engine=self._engine)
-        return None
+        """PairFilterIndex for evaluate_relations() / query_topn_relations(): the (s, o) pair as the key, the SET of relations known
+        between the two (amdkge_pair_filter_build), in a cache of its own (_pair_filter_cache)."""
+        return self._cached_index(PairFilterIndex, "_pair_filter_cache", use_filter, Xi)
 
     # ------------------------------------------------------------------------------------ predict
     def _index_test(self, x):

@@ -15,7 +15,7 @@ import torch
 
 from . import _ffi
 from .colsharded import ColumnStepLoop, check_columns, column_merge, column_slice
-from .engine import KgeEngine
+from .engine import KgeEngine, subset_positions
 from .sharded import RowExchange, ShardedStepLoop, ShardSpec, sharded_rank_counts
 from .trainer import StepLoop, shard_bounds
 
@@ -123,9 +123,7 @@ class Replicated:
         ent_ids = subset_pos = None
         if subset is not None:
             sub = np.asarray(subset, dtype=np.int32)
-            pos = np.full(eng.n_ents, -1, dtype=np.int32)
-            pos[sub] = np.arange(sub.shape[0], dtype=np.int32)  # DenseHashTable.insert: last wins (:1639-1643)
-            ent_ids, subset_pos = torch.as_tensor(sub).to(dev), torch.as_tensor(pos).to(dev)
+            ent_ids, subset_pos = torch.as_tensor(sub).to(dev), subset_positions(sub, eng.n_ents, dev)
         n = Xi.shape[0]
         Xd = torch.as_tensor(Xi).to(dev)
         ranks = torch.empty(n, len(sides), dtype=torch.int32, device=dev)
@@ -150,9 +148,7 @@ class Replicated:
             return None, None
         eng = self.engine
         ids = np.asarray(cand, dtype=np.int32)
-        pos = np.full(eng.n_rels, -1, dtype=np.int32)
-        pos[ids] = np.arange(ids.shape[0], dtype=np.int32)
-        return torch.as_tensor(ids).to(eng.device), torch.as_tensor(pos).to(eng.device)
+        return torch.as_tensor(ids).to(eng.device), subset_positions(ids, eng.n_rels, eng.device)
 
     def rank_relations(self, Xi, pfi, subset, strategy):
         """int32 device ranks (n,) of each test triple's relation among the candidate relations (all, or the ids `subset`), the

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_kernels import dev, make_engine
+from test_gpu_kernels import dev, make_engine, rand_triples
 
 pytestmark = pytest.mark.gpu
 
@@ -213,6 +213,31 @@ def test_exhaustive_with_tied_scores(gpu_lib, model):
     per_row = np.bincount(pairs[:, 0].cpu().numpy(), minlength=N_ENT)
     print("tied scores", model, "largest emission of a row", per_row.max(), "R", R)
     assert per_row.max() > R and (thr.cpu().numpy() > INT32_MIN).all()
+
+
+def test_corruption_select_chunk_invariance(gpu_lib):
+    """corruption_select walks the queries in chunks of SCORE_CHUNK_BYTES: 40 filtered queries against 300 entities, R = 8, seven
+    queries per chunk, give the pairs (as a set: their order is free) and the thresholds of the one-chunk run exactly."""
+    from ampligraph_amd import _ffi
+    from ampligraph_amd.datasets.filters import FilterIndex
+
+    N, n_rels, R = 300, 4, 8
+    eng, _, _ = make_engine("ComplEx", 16, N, n_rels, scale=0.5)
+    rng = np.random.default_rng(12)
+    X = rand_triples(rng, 2000, N, n_rels)
+    q = dev(X[:40])
+    flt = FilterIndex([X], N, n_rels, engine=eng).device_filter(eng, q, "o")
+    assert eng._score_chunks(40, N) == [(0, 40)]
+    one = eng.corruption_select(q, _ffi.SIDE_O, R, 1, flt)
+    eng.SCORE_CHUNK_BYTES = 4 * N * 7                                     # instance attribute: this engine only
+    try:
+        assert len(eng._score_chunks(40, N)) == 6
+        many = eng.corruption_select(q, _ffi.SIDE_O, R, 1, flt)
+    finally:
+        del eng.SCORE_CHUNK_BYTES
+    as_set = lambda pairs: np.sort(pairs[:, 0].cpu().numpy().astype(np.int64) * N + pairs[:, 1].cpu().numpy())   # noqa: E731
+    assert len(one[0]) >= 40 * (R - 1) and np.array_equal(as_set(one[0]), as_set(many[0]))
+    assert torch.equal(one[1], many[1]) and (one[1].cpu().numpy() > INT32_MIN).all()
 
 
 @pytest.mark.parametrize("model,scale", [("DistMult", 6.0), ("ComplEx", 5.0), ("TransE", 300.0)])

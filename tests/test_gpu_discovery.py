@@ -87,6 +87,23 @@ def test_nearest_rows_against_numpy(gpu_lib, metric):
             assert (pos[:, 0] == qid).all()          # a point is its own nearest neighbour
 
 
+@pytest.mark.parametrize("metric", ["euclidean", "cosine"])
+def test_nearest_rows_chunk_invariance(gpu_lib, metric):
+    """nearest_rows walks the queries in chunks of SCORE_CHUNK_BYTES: 40 queries against 300 rows, seven queries per chunk, give
+    the indices and distances of the one-chunk run exactly."""
+    eng, _, _ = make_engine("ComplEx", 16, 300, 3, scale=0.5)
+    Q = eng.ent[dev(np.random.default_rng(6).choice(300, 40, replace=False).astype(np.int64))]
+    assert eng._score_chunks(40, 300) == [(0, 40)]
+    one = eng.nearest_rows(Q, 8, metric)
+    eng.SCORE_CHUNK_BYTES = 4 * 300 * 7                                   # instance attribute: this engine only
+    try:
+        assert len(eng._score_chunks(40, 300)) == 6
+        many = eng.nearest_rows(Q, 8, metric)
+    finally:
+        del eng.SCORE_CHUNK_BYTES
+    assert torch.equal(one[0], many[0]) and torch.equal(one[1], many[1])
+
+
 def _fit_model(dist=None, sharding=None):
     from ampligraph_amd.latent_features import ScoringBasedEmbeddingModel
 

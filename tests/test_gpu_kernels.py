@@ -715,6 +715,29 @@ def test_filter_ranges_kernel_equals_host_lookup(gpu_lib):
             assert np.array_equal(lo, l2.cpu().numpy()) and np.array_equal(hi, h2.cpu().numpy()), sd
 
 
+def filter_range_case():
+    """(X, T, N, R) for the range lookup of all three key forms at N = 57, R = 9: 300 filter triples with s, o in [1, N - 2] and
+    p in [1, R - 2], (1, 1, 1) and (N - 2, R - 2, N - 2) among them -- the first and the last group of every form; 200 queries:
+    70 copied from X, 126 random ones over the whole id range, then T[-4:] = a hit on the first group, a hit on the last group,
+    (0, 0, 0) -- key 0, below the first key of every form -- and (N - 1, R - 1, N - 1), above the last."""
+    rng = np.random.default_rng(57)
+    N, R = 57, 9
+    X = np.stack([rng.integers(1, N - 1, 298), rng.integers(1, R - 1, 298), rng.integers(1, N - 1, 298)], 1)
+    X = np.concatenate([X, [[1, 1, 1], [N - 2, R - 2, N - 2]]]).astype(np.int32)
+    T = np.concatenate([X[rng.integers(0, 298, 70)], rand_triples(rng, 126, N, R),
+                        [[1, 1, 1], [N - 2, R - 2, N - 2], [0, 0, 0], [N - 1, R - 1, N - 1]]]).astype(np.int32)
+    return X, T, N, R
+
+
+def check_filter_range_case(keys, q, lo, hi):
+    """the host side of filter_range_case for one key form (q: the queries' group keys): the case holds what it claims"""
+    assert len(q) == 200 and keys.size > 0
+    assert q[-4] == keys[0] and hi[-4] > lo[-4] and lo[-4] == 0            # hit on the first group
+    assert q[-3] == keys[-1] and hi[-3] > lo[-3]                           # hit on the last group
+    assert q[-2] < keys[0] and q[-1] > keys[-1] and hi[-2] == 0 and hi[-1] == 0
+    assert 3 * int((hi == 0).sum()) >= len(q) and int((hi > lo).sum()) >= 72
+
+
 def test_filter_index_built_on_device_equals_host_build(gpu_lib):
     """amdkge_filter_build (keys, radix sort, scan, scatter on the device) produces the very arrays of the host build
     (datasets/filters.py: numpy unique / searchsorted, itself pinned by the reference's KAT and the oracle's sets): group keys,
@@ -745,6 +768,18 @@ def test_filter_index_built_on_device_equals_host_build(gpu_lib):
             lo, hi = fn(T)
             l2, h2, ids = devi.device_filter(eng, dev(T.astype(np.int32)), sd)
             assert np.array_equal(lo, l2.cpu().numpy()) and np.array_equal(hi, h2.cpu().numpy()), sd
+    # the one lookup kernel against the host ranges, both entity-side forms (the pair form: test_gpu_relation.py): misses, keys
+    # outside the index, the first and the last group, and an index with no keys
+    X, T, N, R = filter_range_case()
+    host, devi, none = FilterIndex([X], N, R), FilterIndex([X], N, R, engine=eng), FilterIndex([], N, R, engine=eng)
+    t = T.astype(np.int64)
+    for sd, fn, keys, q in (("s", host.subject_ranges, host.po_keys, t[:, 1] * N + t[:, 2]), ("o", host.object_ranges, host.sp_keys, t[:, 0] * R + t[:, 1])):
+        lo, hi = fn(T)
+        check_filter_range_case(keys, q, lo, hi)
+        l2, h2, _ = devi.device_filter(eng, dev(T), sd)
+        assert np.array_equal(lo, l2.cpu().numpy()) and np.array_equal(hi, h2.cpu().numpy()), sd
+        l0, h0, ids0 = none.device_filter(eng, dev(T), sd)
+        assert l0.shape == (200,) and not l0.any().item() and not h0.any().item() and ids0.numel() >= 1, sd
 
 
 @pytest.mark.parametrize("model,k", [("ComplEx", 16), ("TransE", 50), ("RotatE", 9), ("DistMult", 600)])

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import kge_oracle as O
-from test_gpu_kernels import dev, make_engine, rand_triples
+from test_gpu_kernels import check_filter_range_case, dev, filter_range_case, make_engine, rand_triples
 
 pytestmark = pytest.mark.gpu
 
@@ -195,6 +195,16 @@ def test_pair_filter_index_device_build_equals_host_build(gpu_lib):
     assert empty.so_keys.size == 0 and empty.so_start.tolist() == [0] and empty.r_ids.size == 0
     dlo, dhi, _ = empty.device_filter(eng, dev(q[:5]))
     assert not dlo.any().item() and not dhi.any().item()
+    # the one lookup kernel against the host ranges in the pair form (the entity-side forms: test_gpu_kernels.py): misses, keys
+    # outside the index, the first and the last group, and an index with no keys
+    X, T, N, R = filter_range_case()
+    host, device = PairFilterIndex([X], N, R), PairFilterIndex([X], N, R, engine=eng)
+    lo, hi = host.relation_ranges(T)
+    check_filter_range_case(host.so_keys, T[:, 0].astype(np.int64) * N + T[:, 2], lo, hi)
+    dlo, dhi, _ = device.device_filter(eng, dev(T))
+    assert np.array_equal(dlo.cpu().numpy(), lo) and np.array_equal(dhi.cpu().numpy(), hi)
+    dlo, dhi, ids = PairFilterIndex([], N, R, engine=eng).device_filter(eng, dev(T))
+    assert dlo.shape == (200,) and not dlo.any().item() and not dhi.any().item() and ids.numel() >= 1
 
 
 # ------------------------------------------------------------------------------------------------ the public surface
@@ -275,7 +285,7 @@ def test_evaluate_relations_against_brute_force(gpu_lib, scoring):
     want = m.evaluate_relations(test, use_filter=True)
     m._engine.SCORE_CHUNK_BYTES = 4 * N_R * 7                             # seven queries per chunk
     try:
-        assert len(m._engine._relation_chunks(len(test), N_R)) > 3
+        assert len(m._engine._score_chunks(len(test), N_R)) > 3
         assert np.array_equal(m.evaluate_relations(test, use_filter=True), want)
     finally:
         del m._engine.SCORE_CHUNK_BYTES

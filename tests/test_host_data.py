@@ -144,6 +144,121 @@ def test_device_filter_plumbing_with_a_stub_engine():
     assert fi.device_filter(eng, torch.as_tensor(T), "s")[2] is fi.device_filter(eng, torch.as_tensor(T), "s")[2]   # cached upload
 
 
+def test_pair_device_filter_plumbing_with_a_stub_engine():
+    """PairFilterIndex.device_filter, as the FilterIndex one above: the engine gets the sorted pair keys and starts, its ranges come
+    back with the relation id array, the upload is cached, and an index of no datasets gives all-zero ranges with a placeholder
+    id tensor (the kernels take no NULL id pointer).  Stub engine doing amdkge_pair_filter_ranges' search in numpy."""
+    import torch
+
+    from ampligraph_amd.datasets.filters import PairFilterIndex
+
+    class StubEngine:
+        device = torch.device("cpu")
+
+        def pair_filter_ranges(self, keys, start, triples, n_ents):
+            t = triples.numpy().astype(np.int64)
+            q = t[:, 0] * n_ents + t[:, 2]
+            k, s = keys.numpy(), start.numpy()
+            pos = np.minimum(np.searchsorted(k, q), max(0, k.size - 1))
+            hit = (k[pos] == q) if k.size else np.zeros(len(q), bool)
+            return torch.as_tensor(np.where(hit, s[pos], 0)), torch.as_tensor(np.where(hit, s[np.minimum(pos + 1, s.size - 1)], 0))
+
+    rng = np.random.default_rng(5)
+    N, R = 40, 3
+    X = np.stack([rng.integers(0, N, 400), rng.integers(0, R, 400), rng.integers(0, N, 400)], 1).astype(np.int32)
+    T = np.stack([rng.integers(0, N, 90), rng.integers(0, R, 90), rng.integers(0, N, 90)], 1).astype(np.int32)
+    T[:30] = X[:30]
+    fi = PairFilterIndex([X], N, R)
+    eng = StubEngine()
+    lo, hi = fi.relation_ranges(T)
+    assert (hi > lo).sum() >= 30 and (hi == 0).any()
+    l2, h2, ids = fi.device_filter(eng, torch.as_tensor(T))
+    assert np.array_equal(lo, l2.numpy()) and np.array_equal(hi, h2.numpy()) and np.array_equal(ids.numpy(), fi.r_ids)
+    assert fi.device_filter(eng, torch.as_tensor(T))[2] is ids                                  # cached upload
+    l0, h0, ids0 = PairFilterIndex([], N, R).device_filter(eng, torch.as_tensor(T))
+    assert l0.shape == (90,) and not l0.numpy().any() and not h0.numpy().any() and ids0.numel() >= 1
+
+
+def test_group_key_forms_agree_with_the_host_indexes():
+    """The three key forms restated -- subject side: group (p, o), values s; object side: group (s, p), values o; pair: group
+    (s, o), values p -- against datasets/filters.py's one definition (_group_key) and the arrays FilterIndex / PairFilterIndex
+    build from it on the host: sorted group keys, CSR starts, ascending unique ids per group."""
+    from ampligraph_amd.datasets import filters
+    from ampligraph_amd.datasets.filters import PairFilterIndex
+
+    rng = np.random.default_rng(11)
+    N, R = 57, 9
+    X = np.stack([rng.integers(0, N, 260), rng.integers(0, R, 260), rng.integers(0, N, 260)], 1).astype(np.int64)
+    X = np.concatenate([X, X[:40]])                                                             # 300 triples, 40 of them twice
+    s, p, o = X[:, 0], X[:, 1], X[:, 2]
+    fi, pfi = FilterIndex([X[:200], X[200:]], N, R), PairFilterIndex([X[:200], X[200:]], N, R)
+    forms = {"s": (p * N + o, s, fi.po_keys, fi.po_start, fi.s_ids, fi.subject_ranges),
+             "o": (s * R + p, o, fi.sp_keys, fi.sp_start, fi.o_ids, fi.object_ranges),
+             "pair": (s * N + o, p, pfi.so_keys, pfi.so_start, pfi.r_ids, pfi.relation_ranges)}
+    for form, (group, value, keys, start, ids, ranges) in forms.items():
+        assert np.array_equal(filters._group_key(form, s, p, o, N, R), group), form
+        sets = {}
+        for g, v in zip(group.tolist(), value.tolist()):
+            sets.setdefault(g, set()).add(v)
+        want_keys = sorted(sets)
+        assert keys.tolist() == want_keys and keys.dtype == np.int64, form
+        assert start.tolist() == np.cumsum([0] + [len(sets[g]) for g in want_keys]).tolist() and start.dtype == np.int64, form
+        assert ids.tolist() == [v for g in want_keys for v in sorted(sets[g])] and ids.dtype == np.int32, form
+        lo, hi = ranges(X)
+        assert all(ids[a:b].tolist() == sorted(sets[g]) for a, b, g in zip(lo, hi, group.tolist())), form
+        assert len(ids) < len(X)                                                                # the duplicates collapsed
+
+
+def test_cached_index_helper_with_stand_in_classes(monkeypatch):
+    """ScoringBasedEmbeddingModel._filter_index / _pair_filter_index are one helper with two caches: equal dict content gives the
+    cached object, a changed array a new one, a reset cache a rebuild, the two caches do not evict each other, and object-dtype
+    arrays are never cached.  Stand-in index classes, no engine."""
+    from ampligraph_amd.datasets.indexer import DataIndexer
+    from ampligraph_amd.latent_features import ScoringBasedEmbeddingModel, models
+
+    built = []
+
+    def stand_in(tag):
+        class Index:
+            def __init__(self, datasets, n_ents, n_rels, engine=None):
+                assert engine is None
+                self.tag, self.datasets, self.sizes = tag, datasets, (n_ents, n_rels)
+                built.append(tag)
+        return Index
+
+    monkeypatch.setattr(models, "FilterIndex", stand_in("side"))
+    monkeypatch.setattr(models, "PairFilterIndex", stand_in("pair"))
+    m = ScoringBasedEmbeddingModel(eta=1, k=4, scoring_type="DistMult")
+    X = np.array([[0, 0, 1], [1, 1, 2], [2, 0, 0]], dtype=np.int64)
+    m.data_indexer = DataIndexer(X)
+    m._n_ents, m._n_rels = 3, 2
+    assert m._engine is None
+    first = {}
+    for tag, get, attr in (("side", m._filter_index, "_filter_cache"), ("pair", m._pair_filter_index, "_pair_filter_cache")):
+        assert get(False, None) is None and get(None, None) is None
+        a = get({"train": X, "test": X[:2]}, None)
+        assert a.tag == tag and a.sizes == (3, 2) and len(a.datasets) == 2 and getattr(m, attr)[1] is a
+        assert get({"other": X.copy(), "names": X[:2].copy()}, None) is a                     # same content: the cached object
+        Y = X.copy()
+        Y[2, 2] = 1
+        b = get({"train": Y, "test": X[:2]}, None)
+        assert b is not a and getattr(m, attr)[1] is b                                        # one array changed: a new index
+        setattr(m, attr, (None, None))
+        c = get({"train": Y, "test": X[:2]}, None)
+        assert c is not b and get({"train": Y, "test": X[:2]}, None) is c                     # reset: rebuilt, then cached again
+        n = len(built)
+        objs = X.astype(object)
+        assert get({"train": objs}, None) is not get({"train": objs}, None) and len(built) == n + 2   # object dtype: not cached
+        assert getattr(m, attr)[1] is c
+        t = get(True, X)
+        assert t.tag == tag and len(t.datasets) == 1 and getattr(m, attr)[1] is c             # True: the evaluated data, uncached
+        first[tag] = c
+    # the pair calls above left the side cache alone, and a side call leaves the pair cache alone
+    assert m._filter_cache[1] is first["side"] and m._filter_index({"train": Y, "test": X[:2]}, None) is first["side"]
+    assert m._pair_filter_cache[1] is first["pair"] and m._pair_filter_index({"train": Y, "test": X[:2]}, None) is first["pair"]
+    assert m._filter_cache[0] == m._pair_filter_cache[0]                                      # (the same key recipe)
+
+
 def test_select_best_model_ranking_with_a_stub_model():
     """evaluation.select_best_model_ranking (reference protocol.py:447-933): grid and random search, selection on the odd
     validation rows, failing combinations recorded and skipped, retraining for the early-stopping epoch count, test metrics.

@@ -233,13 +233,13 @@ def test_relation_kernels_use_no_scratch():
 
     assert os.path.exists(LIB), "library not built: run build() first"
     res = kernel_resources(LIB)
-    new = {n: k for n, k in res.items() if re.match(r"_ZN3kge\d+(relation_|pair_filter_)", n) or n.startswith("_Z25pair_filter_ranges_kernel")}
+    new = {n: k for n, k in res.items() if re.match(r"_ZN3kge\d+(relation_|pair_filter_)", n) or n.startswith("_ZN3kge20filter_ranges_kernel")}
     main = [n for n in new if "relation_scores_kernel" in n]
     reload_ = [n for n in new if "relation_scores_reload_kernel" in n]
     # four model families x (four lane-iteration counts of the register form + three vector widths of the reload form)
     assert len(main) == 16 and len(reload_) == 12, sorted(new)
     assert any("relation_prep_kernel" in n for n in new) and any("relation_counts_kernel" in n for n in new)
-    assert any("pair_filter_ranges_kernel" in n for n in new)
+    assert any("filter_ranges_kernel" in n for n in new)
     for n, k in new.items():
         assert k["scratch"] == 0, (n, k)
         assert k["vgpr"] <= 256 and k["waves_per_simd"] >= 2, (n, k)
