@@ -1,5 +1,6 @@
 // Host-side staging of amdkge_session_group_rank for a ROW-SHARDED group (kge_session_group.hip rows_rank): which entity rows a chunk of
-// queries needs, where they sit behind every shard, and what each replica is asked to gather.  Pure C++ (no HIP types): compiled into the
+// queries needs, where they sit behind every shard, and what each replica is asked to gather -- with the two host-only pieces every
+// session entry shares (triple validation, the entities-subset tables).  Pure C++ (no HIP types): compiled into the
 // library and, by tests/test_group_staging.py, into a CPU harness -- the logic every replica's host thread runs on a multi-GPU node.
 //
 // The reference's analogue is the partition loop of evaluate() (/root/reference/ampligraph/latent_features/models/ScoringBasedEmbeddingModel.py:1431-1452):
@@ -39,6 +40,33 @@ inline void stage_replica(const int32_t* tq, int64_t nq, const std::vector<int32
         const int64_t v = (int64_t)U[(size_t)j] - lo;
         idx[(size_t)j] = (v >= 0 && v < n_local) ? (int32_t)v : -1;
     }
+}
+
+// the first of n host triples (s, p, o) with an id outside [0, n_ents) / [0, n_rels), or -1: an out-of-range id would become an
+// out-of-bounds gather (or a scatter into the gradient tables) on the device, so every entry checks before anything is uploaded
+inline int64_t first_bad_triple(const int32_t* t, int64_t n, int64_t n_ents, int64_t n_rels) {
+    for (int64_t i = 0; i < n; ++i)
+        if (t[3 * i] < 0 || t[3 * i] >= n_ents || t[3 * i + 2] < 0 || t[3 * i + 2] >= n_ents || t[3 * i + 1] < 0 || t[3 * i + 1] >= n_rels) return i;
+    return -1;
+}
+
+// entities_subset for the candidates that live in rows [lo, lo + n_local) of the entity table (a whole table: lo = 0, n_local = N):
+//   lst           the owned candidates as local rows (id - lo), in the caller's order, duplicates counted as given
+//   pos [total_rows]  local row -> position in lst of the filter pass (last wins, ScoringBasedEmbeddingModel.py:1639-1643); -1 elsewhere,
+//                     the scratch rows [n_local, total_rows) behind a shard included
+// false when an id lies outside [0, N) (nothing is usable then)
+inline bool stage_subset(const int32_t* subset, int64_t n_subset, int64_t N, int64_t lo, int64_t n_local, int64_t total_rows,
+                         std::vector<int32_t>& lst, std::vector<int32_t>& pos) {
+    lst.clear();
+    pos.assign((size_t)total_rows, -1);
+    for (int64_t i = 0; i < n_subset; ++i) {
+        const int64_t v = (int64_t)subset[i] - lo;
+        if (subset[i] < 0 || subset[i] >= N) return false;
+        if (v < 0 || v >= n_local) continue;
+        pos[(size_t)v] = (int32_t)lst.size();
+        lst.push_back((int32_t)v);
+    }
+    return true;
 }
 
 // the chunk's slice [q0, q0 + nq] of a CSR offset array, zero-based

@@ -6,18 +6,14 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "kge_opt.h"
+#include "kge_group_staging.h"
+#include "kge_session_impl.h"
 
 using namespace kge;
 
-#include "kge_session_impl.h"
-
 namespace {
 
-#define KGE_HIP(call, what) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return set_error_hip(e_, what); } while (0)
-#define KGE_RC(call) do { const int rc_ = (call); if (rc_ != AMDKGE_OK) return rc_; } while (0)
-
-int64_t table_rows(const amdkge_session* s, int t) { return (t == AMDKGE_TABLE_ENT || t == AMDKGE_TABLE_ENT_SLOT0 || t == AMDKGE_TABLE_ENT_SLOT1) ? s->cfg.model.n_ents : s->cfg.model.n_rels; }
+int64_t table_rows(const amdkge_session* s, int t) { return is_entity_table(t) ? s->cfg.model.n_ents : s->cfg.model.n_rels; }
 
 // scratch slot `i` with at least `bytes` bytes (contents undefined)
 int scratch(amdkge_session* s, int i, int64_t bytes, void** out) {
@@ -37,17 +33,10 @@ int upload(amdkge_session* s, int slot, const void* host, int64_t bytes, void** 
     return AMDKGE_OK;
 }
 
-// ids arrive from the host: an out-of-range id would become an out-of-bounds gather (or a scatter into the gradient
-// tables) on the device, so they are checked here, O(n) on host memory, before anything is uploaded
-int check_triples(const amdkge_session* s, const int32_t* t, int64_t n, const char* who) {
-    const int64_t ne = s->cfg.model.n_ents, nr = s->cfg.model.n_rels;
-    for (int64_t i = 0; i < n; ++i)
-        if (t[3 * i] < 0 || t[3 * i] >= ne || t[3 * i + 2] < 0 || t[3 * i + 2] >= ne || t[3 * i + 1] < 0 || t[3 * i + 1] >= nr) {
-            static thread_local char msg[160];
-            snprintf(msg, sizeof(msg), "%s: triple %lld has an entity / relation id outside the tables", who, (long long)i);
-            return set_error(AMDKGE_EINVAL, msg);
-        }
-    return AMDKGE_OK;
+amdkge_opt step_opt(const amdkge_session* s) {
+    amdkge_opt opt = s->cfg.opt;
+    opt.iteration = s->iteration + 1;
+    return opt;
 }
 
 __global__ void gather_rows_kernel(const float* src, const int32_t* ids, int64_t n, int K, float* dst) {
@@ -58,6 +47,91 @@ __global__ void gather_rows_kernel(const float* src, const int32_t* ids, int64_t
 
 }  // namespace
 
+// ---- building blocks of a step (kge_session_impl.h) -----------------------------------------------------------------------
+// ids arrive from the host and are checked, O(n) on host memory, before anything is uploaded (kge_group_staging.h)
+int session_check_triples(const int32_t* t, int64_t n, int64_t n_ents, int64_t n_rels, const char* who) {
+    const int64_t i = first_bad_triple(t, n, n_ents, n_rels);
+    if (i < 0) return AMDKGE_OK;
+    static thread_local char msg[160];
+    snprintf(msg, sizeof(msg), "%s: triple %lld has an entity / relation id outside the tables", who, (long long)i);
+    return set_error(AMDKGE_EINVAL, msg);
+}
+
+int session_twork(amdkge_session* s, const amdkge_model* m, int64_t b, int64_t* need) {
+    *need = amdkge_train_tiled_workspace_bytes(m, b, s->cfg.eta);
+    if (*need <= s->twork_bytes) return AMDKGE_OK;
+    if (s->twork) KGE_HIP(hipFree(s->twork), "hipFree(twork)");
+    s->twork = nullptr; s->twork_bytes = 0;
+    KGE_HIP(hipMalloc(&s->twork, (size_t)*need), "hipMalloc(twork)");
+    KGE_HIP(hipMemsetAsync(s->twork, 0, (size_t)*need, s->st), "hipMemsetAsync(twork)");
+    s->twork_bytes = *need;
+    s->hot_dirty = !s->hot_ids.empty();
+    return AMDKGE_OK;
+}
+
+void session_drop_twork(amdkge_session* s) {
+    if (s->twork) (void)hipFree(s->twork);
+    s->twork = nullptr; s->twork_bytes = 0;
+}
+
+int session_step_loss(amdkge_session* s, const float* focus_w, int64_t lo, int64_t b, const char* who, const char* whose, amdkge_loss* out) {
+    *out = session_step_loss(s);
+    if (!focus_w) return AMDKGE_OK;
+    if (!s->cfg.loss.focus_nonlinearity) {
+        static thread_local char msg[160];
+        snprintf(msg, sizeof(msg), "%s: FocusE weights given but the %s's loss has focus_nonlinearity == 0", who, whose);
+        return set_error(AMDKGE_EINVAL, msg);
+    }
+    void* d_fw;
+    KGE_RC(upload(s, 1, focus_w + lo, b * (int64_t)sizeof(float), &d_fw));
+    out->focus_nonlinearity = s->cfg.loss.focus_nonlinearity;
+    out->d_focus_w = (const float*)d_fw;
+    return AMDKGE_OK;
+}
+
+int session_share_kernels(amdkge_session* s, const amdkge_model* m, const amdkge_loss* loss, const amdkge_opt* opt, const int32_t* d_tri, int64_t b,
+                          int64_t sample_range, uint64_t step, int64_t row_offset, int64_t b_global, const int32_t* d_neg_override,
+                          int32_t apply_update, int32_t flags, double* d_loss, double* d_reg, bool* tiled) {
+    int64_t need = 0;
+    KGE_RC(session_twork(s, m, b, &need));
+    if (tiled) *tiled = need > 0;
+    if (need <= 0)   // shapes the pair does not cover
+        return amdkge_train_fwdbwd(m, loss, s->tab[0], s->tab[1], d_tri, b, s->cfg.eta, 0, sample_range, s->cfg.seed, step, row_offset, b_global,
+                                   d_neg_override, s->g_ent, s->g_rel, d_loss, nullptr, nullptr, s->st);
+    if ((flags & AMDKGE_TILED_HOT_ROWS) && s->hot_dirty) {
+        void* d_hot;
+        KGE_RC(upload(s, 6, s->hot_ids.data(), (int64_t)(s->hot_ids.size() * sizeof(int32_t)), &d_hot));   // (scratch slot of its own)
+        KGE_RC(amdkge_train_tiled_set_hot_rows(m, s->twork, (const int32_t*)d_hot, (int32_t)s->hot_ids.size(), s->st));
+        s->hot_dirty = false;
+    }
+    float* const* t = s->tab;
+    const int rc = amdkge_train_step_tiled(m, loss, opt, t[0], t[1], apply_update ? t[2] : nullptr, apply_update ? t[3] : nullptr,
+                                           apply_update ? t[4] : nullptr, apply_update ? t[5] : nullptr, apply_update ? s->cfg.rel_reg_lambda : 0.f,
+                                           d_tri, b, s->cfg.eta, 0, sample_range, s->cfg.seed, step, row_offset, b_global, d_neg_override,
+                                           s->g_ent, s->g_rel, apply_update, flags, d_loss, d_reg, nullptr, nullptr, s->twork, s->st);
+    if (rc != AMDKGE_OK) session_drop_twork(s);
+    return rc;
+}
+
+int session_dense_sweep(amdkge_session* s, const amdkge_opt* opt, int64_t n_rows, double* d_reg_ent, double* d_reg_rel) {
+    if (n_rows > 0) KGE_RC(amdkge_opt_step(opt, s->tab[0], s->g_ent, s->tab[2], s->tab[3], n_rows * (int64_t)s->Ks, d_reg_ent, s->st));
+    amdkge_opt orel = *opt;
+    orel.reg_lambda = s->cfg.rel_reg_lambda;
+    if (opt->rel_reg_p > 0) orel.reg_p = opt->rel_reg_p;
+    orel.reg2_p = opt->rel_reg2_p; orel.reg2_lambda = opt->rel_reg2_lambda;
+    return amdkge_opt_step(&orel, s->tab[1], s->g_rel, s->tab[4], s->tab[5], s->cfg.model.n_rels * (int64_t)s->Ks, d_reg_rel, s->st);
+}
+
+int session_ranks_to_host(amdkge_session* s, const int32_t* d_ranks, int64_t n, int32_t corrupt_side, int32_t* ranks_out) {
+    const bool sum = corrupt_side == AMDKGE_CORRUPT_S_PLUS_O;
+    const size_t cols = (sum || corrupt_side == AMDKGE_CORRUPT_S_O) ? 2 : 1;
+    std::vector<int32_t> h(sum ? (size_t)2 * n : 0);
+    KGE_HIP(hipMemcpyAsync(sum ? h.data() : ranks_out, d_ranks, (size_t)n * cols * sizeof(int32_t), hipMemcpyDeviceToHost, s->st), "hipMemcpyAsync(D2H)");
+    KGE_HIP(hipStreamSynchronize(s->st), "hipStreamSynchronize");
+    for (int64_t i = 0; sum && i < n; ++i) ranks_out[i] = h[(size_t)i] + h[(size_t)(n + i)] - 1;
+    return AMDKGE_OK;
+}
+
 extern "C" void amdkge_session_destroy(amdkge_session* s) {
     if (!s) return;
     (void)hipSetDevice(s->cfg.device);
@@ -66,7 +140,7 @@ extern "C" void amdkge_session_destroy(amdkge_session* s) {
     if (s->g_ent) (void)hipFree(s->g_ent);
     if (s->g_rel) (void)hipFree(s->g_rel);
     if (s->acc) (void)hipFree(s->acc);
-    if (s->twork) (void)hipFree(s->twork);
+    session_drop_twork(s);
     for (void* p : s->buf) if (p) (void)hipFree(p);
     if (s->st) (void)hipStreamDestroy(s->st);
     delete s;
@@ -167,61 +241,27 @@ extern "C" int amdkge_session_train_step(amdkge_session* s, const int32_t* tripl
     if (loss_out) *loss_out = 0.0;
     if (B == 0) return AMDKGE_OK;   // (the reference never produces an empty batch; nothing happens, no step is counted)
     if (!triples) return set_error(AMDKGE_EINVAL, "session_train_step: NULL triples");
-    if (focus_w && !s->cfg.loss.focus_nonlinearity) return set_error(AMDKGE_EINVAL, "session_train_step: FocusE weights given but the session's loss has focus_nonlinearity == 0");
-    KGE_RC(check_triples(s, triples, B, "session_train_step"));
+    KGE_RC(session_check_triples(triples, B, s->cfg.model.n_ents, s->cfg.model.n_rels, "session_train_step"));
     KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
     const amdkge_model* m = &s->cfg.model;
-    void *d_tri, *d_fw = nullptr;
+    void* d_tri;
     KGE_RC(upload(s, 0, triples, B * 3 * (int64_t)sizeof(int32_t), &d_tri));
-    amdkge_loss loss = s->cfg.loss;
-    if (focus_w) { KGE_RC(upload(s, 1, focus_w, B * (int64_t)sizeof(float), &d_fw)); loss.d_focus_w = (const float*)d_fw; }
-    else { loss.focus_nonlinearity = AMDKGE_FOCUS_OFF; loss.d_focus_w = nullptr; }
-    amdkge_opt opt = s->cfg.opt;
-    opt.iteration = s->iteration + 1;
+    amdkge_loss loss;
+    KGE_RC(session_step_loss(s, focus_w, 0, B, "session_train_step", "session", &loss));
+    const amdkge_opt opt = step_opt(s);
     KGE_HIP(hipMemsetAsync(s->acc, 0, 2 * sizeof(double), s->st), "hipMemsetAsync");
-    const int64_t need = amdkge_train_tiled_workspace_bytes(m, B, s->cfg.eta);
-    if (need > 0) {   // owner-computes kernel pair: the complete step
-        if (need > s->twork_bytes) {
-            if (s->twork) KGE_HIP(hipFree(s->twork), "hipFree(twork)");
-            s->twork = nullptr; s->twork_bytes = 0;
-            KGE_HIP(hipMalloc(&s->twork, (size_t)need), "hipMalloc(twork)");
-            KGE_HIP(hipMemsetAsync(s->twork, 0, (size_t)need, s->st), "hipMemsetAsync(twork)");
-            s->twork_bytes = need;
-            s->hot_dirty = !s->hot_ids.empty();
+    const int32_t step_flags = s->cfg.flags | (s->hot_ids.empty() ? 0 : AMDKGE_TILED_HOT_ROWS);
+    bool tiled = false;
+    KGE_RC(session_share_kernels(s, m, &loss, &opt, (const int32_t*)d_tri, B, m->n_ents, s->step, 0, 0, nullptr, 1, step_flags, s->acc, s->acc + 1, &tiled));
+    if (!tiled) {   // the atomic forward/backward left gradients: dense sweeps
+        KGE_RC(session_dense_sweep(s, &opt, m->n_ents, s->acc + 1, s->acc + 1));
+    } else if (step_flags & AMDKGE_TILED_DETERMINISTIC) {   // a tile beyond its sort buffer fell back to arrival order: say so
+        int32_t st_flag = 0;
+        KGE_RC(amdkge_train_tiled_status(m, B, s->cfg.eta, step_flags, s->twork, &st_flag, s->st));
+        if (st_flag) {
+            s->step += 1; s->iteration += 1;   // the step itself was carried out
+            return set_error(AMDKGE_EUNSUPPORTED, "session_train_step: deterministic mode -- a tile received more entries than its sort buffer holds (a very hot row); this step's sums were not all added in canonical order");
         }
-        int32_t step_flags = s->cfg.flags;
-        if (s->hot_dirty) {
-            void* d_hot;
-            KGE_RC(upload(s, 6, s->hot_ids.data(), (int64_t)(s->hot_ids.size() * sizeof(int32_t)), &d_hot));   // (scratch slot of its own)
-            KGE_RC(amdkge_train_tiled_set_hot_rows(m, s->twork, (const int32_t*)d_hot, (int32_t)s->hot_ids.size(), s->st));
-            s->hot_dirty = false;
-        }
-        if (!s->hot_ids.empty()) step_flags |= AMDKGE_TILED_HOT_ROWS;
-        const int rc = amdkge_train_step_tiled(m, &loss, &opt, s->tab[0], s->tab[1], s->tab[2], s->tab[3], s->tab[4], s->tab[5],
-                                               s->cfg.rel_reg_lambda, (const int32_t*)d_tri, B, s->cfg.eta, 0, m->n_ents, s->cfg.seed,
-                                               s->step, 0, 0, nullptr, s->g_ent, s->g_rel, 1, step_flags, s->acc, s->acc + 1,
-                                               nullptr, nullptr, s->twork, s->st);
-        if (rc != AMDKGE_OK) {   // bookkeeping may be dirty after a failed launch: start from a fresh zeroed buffer next time
-            (void)hipFree(s->twork); s->twork = nullptr; s->twork_bytes = 0;
-            return rc;
-        }
-        if (step_flags & AMDKGE_TILED_DETERMINISTIC) {   // a tile beyond its sort buffer fell back to arrival order: say so
-            int32_t st_flag = 0;
-            KGE_RC(amdkge_train_tiled_status(m, B, s->cfg.eta, step_flags, s->twork, &st_flag, s->st));
-            if (st_flag) {
-                s->step += 1; s->iteration += 1;   // the step itself was carried out
-                return set_error(AMDKGE_EUNSUPPORTED, "session_train_step: deterministic mode -- a tile received more entries than its sort buffer holds (a very hot row); this step's sums were not all added in canonical order");
-            }
-        }
-    } else {          // shapes the pair does not cover: atomic forward/backward + dense sweeps
-        KGE_RC(amdkge_train_fwdbwd(m, &loss, s->tab[0], s->tab[1], (const int32_t*)d_tri, B, s->cfg.eta, 0, m->n_ents, s->cfg.seed,
-                                   s->step, 0, 0, nullptr, s->g_ent, s->g_rel, s->acc, nullptr, nullptr, s->st));
-        KGE_RC(amdkge_opt_step(&opt, s->tab[0], s->g_ent, s->tab[2], s->tab[3], m->n_ents * (int64_t)s->Ks, s->acc + 1, s->st));
-        amdkge_opt orel = opt;
-        orel.reg_lambda = s->cfg.rel_reg_lambda;
-        if (opt.rel_reg_p > 0) orel.reg_p = opt.rel_reg_p;
-        orel.reg2_p = opt.rel_reg2_p; orel.reg2_lambda = opt.rel_reg2_lambda;
-        KGE_RC(amdkge_opt_step(&orel, s->tab[1], s->g_rel, s->tab[4], s->tab[5], m->n_rels * (int64_t)s->Ks, s->acc + 1, s->st));
     }
     double h[2] = {0.0, 0.0};
     KGE_HIP(hipMemcpyAsync(h, s->acc, sizeof(h), hipMemcpyDeviceToHost, s->st), "hipMemcpyAsync(D2H)");
@@ -235,51 +275,25 @@ extern "C" int amdkge_session_train_step(amdkge_session* s, const int32_t* tripl
 // ---- data-parallel phases of a step (session group) ----------------------------------------------------------------------
 int amdkge_session_grad_step(amdkge_session* s, const int32_t* triples, int64_t b, const float* focus_w, int64_t row_offset, int64_t b_global) {
     if (!s || b < 0 || (b > 0 && !triples)) return set_error(AMDKGE_EINVAL, "session_grad_step: bad arguments");
-    if (focus_w && !s->cfg.loss.focus_nonlinearity) return set_error(AMDKGE_EINVAL, "session_grad_step: FocusE weights given but the session's loss has focus_nonlinearity == 0");
-    KGE_RC(check_triples(s, triples, b, "session_grad_step"));
+    KGE_RC(session_check_triples(triples, b, s->cfg.model.n_ents, s->cfg.model.n_rels, "session_grad_step"));
     KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
     KGE_HIP(hipMemsetAsync(s->acc, 0, 2 * sizeof(double), s->st), "hipMemsetAsync");
     if (b == 0) return AMDKGE_OK;   // (a replica without a share: its zero gradients still take part in the sum)
     const amdkge_model* m = &s->cfg.model;
-    void *d_tri, *d_fw = nullptr;
+    void* d_tri;
     KGE_RC(upload(s, 0, triples, b * 3 * (int64_t)sizeof(int32_t), &d_tri));
-    amdkge_loss loss = s->cfg.loss;
-    if (focus_w) { KGE_RC(upload(s, 1, focus_w, b * (int64_t)sizeof(float), &d_fw)); loss.d_focus_w = (const float*)d_fw; }
-    else { loss.focus_nonlinearity = AMDKGE_FOCUS_OFF; loss.d_focus_w = nullptr; }
-    amdkge_opt opt = s->cfg.opt;
-    opt.iteration = s->iteration + 1;
-    const int64_t need = amdkge_train_tiled_workspace_bytes(m, b, s->cfg.eta);
-    if (need > 0) {
-        if (need > s->twork_bytes) {
-            if (s->twork) KGE_HIP(hipFree(s->twork), "hipFree(twork)");
-            s->twork = nullptr; s->twork_bytes = 0;
-            KGE_HIP(hipMalloc(&s->twork, (size_t)need), "hipMalloc(twork)");
-            KGE_HIP(hipMemsetAsync(s->twork, 0, (size_t)need, s->st), "hipMemsetAsync(twork)");
-            s->twork_bytes = need;
-        }
-        const int32_t flags = s->cfg.flags & (AMDKGE_TILED_POS_ATOMIC | AMDKGE_TILED_DETERMINISTIC | AMDKGE_TILED_DET_WIDE_SORT);   // (hot-row replicas: single-GPU steps only)
-        const int rc = amdkge_train_step_tiled(m, &loss, &opt, s->tab[0], s->tab[1], nullptr, nullptr, nullptr, nullptr, 0.f,
-                                               (const int32_t*)d_tri, b, s->cfg.eta, 0, m->n_ents, s->cfg.seed, s->step, row_offset, b_global,
-                                               nullptr, s->g_ent, s->g_rel, 0, flags, s->acc, s->acc + 1, nullptr, nullptr, s->twork, s->st);
-        if (rc != AMDKGE_OK) { (void)hipFree(s->twork); s->twork = nullptr; s->twork_bytes = 0; return rc; }
-        return AMDKGE_OK;
-    }
-    return amdkge_train_fwdbwd(m, &loss, s->tab[0], s->tab[1], (const int32_t*)d_tri, b, s->cfg.eta, 0, m->n_ents, s->cfg.seed, s->step,
-                               row_offset, b_global, nullptr, s->g_ent, s->g_rel, s->acc, nullptr, nullptr, s->st);
+    amdkge_loss loss;
+    KGE_RC(session_step_loss(s, focus_w, 0, b, "session_grad_step", "session", &loss));
+    const amdkge_opt opt = step_opt(s);
+    const int32_t flags = s->cfg.flags & (AMDKGE_TILED_POS_ATOMIC | AMDKGE_TILED_DETERMINISTIC | AMDKGE_TILED_DET_WIDE_SORT);   // (hot-row replicas: single-GPU steps only)
+    return session_share_kernels(s, m, &loss, &opt, (const int32_t*)d_tri, b, m->n_ents, s->step, row_offset, b_global, nullptr, 0, flags, s->acc, s->acc + 1, nullptr);
 }
 
 int amdkge_session_apply_step(amdkge_session* s) {
     if (!s) return set_error(AMDKGE_EINVAL, "session_apply_step: NULL session");
     KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
-    const amdkge_model* m = &s->cfg.model;
-    amdkge_opt opt = s->cfg.opt;
-    opt.iteration = s->iteration + 1;
-    KGE_RC(amdkge_opt_step(&opt, s->tab[0], s->g_ent, s->tab[2], s->tab[3], m->n_ents * (int64_t)s->Ks, s->acc + 1, s->st));
-    amdkge_opt orel = opt;
-    orel.reg_lambda = s->cfg.rel_reg_lambda;
-    if (opt.rel_reg_p > 0) orel.reg_p = opt.rel_reg_p;
-    orel.reg2_p = opt.rel_reg2_p; orel.reg2_lambda = opt.rel_reg2_lambda;
-    return amdkge_opt_step(&orel, s->tab[1], s->g_rel, s->tab[4], s->tab[5], m->n_rels * (int64_t)s->Ks, s->acc + 1, s->st);
+    const amdkge_opt opt = step_opt(s);
+    return session_dense_sweep(s, &opt, s->cfg.model.n_ents, s->acc + 1, s->acc + 1);
 }
 
 int amdkge_session_finish_step(amdkge_session* s, double (&h)[2]) {
@@ -297,7 +311,7 @@ int amdkge_session_finish_step(amdkge_session* s, double (&h)[2]) {
 // A: the slice's partial score sums of the WHOLE batch into the session's score buffer (scratch slot 2), left on the device
 int amdkge_session_cols_scores(amdkge_session* s, const int32_t* triples, int64_t B, float** d_scores_out) {
     if (!s || B < 1 || !triples || !d_scores_out) return set_error(AMDKGE_EINVAL, "session_cols_scores: bad arguments");
-    KGE_RC(check_triples(s, triples, B, "session_group_train_step"));
+    KGE_RC(session_check_triples(triples, B, s->cfg.model.n_ents, s->cfg.model.n_rels, "session_group_train_step"));
     KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
     void *d_tri, *d_sc;
     KGE_RC(upload(s, 0, triples, B * 3 * (int64_t)sizeof(int32_t), &d_tri));
@@ -317,24 +331,16 @@ int amdkge_session_cols_apply(amdkge_session* s, int64_t B) {
     const amdkge_model* m = &s->cfg.model;
     float* d_sc = (float*)s->buf[2];
     void* d_tri = s->buf[0];
-    amdkge_loss loss = s->cfg.loss;
-    loss.focus_nonlinearity = AMDKGE_FOCUS_OFF; loss.d_focus_w = nullptr;
+    const amdkge_loss loss = session_step_loss(s);   // (FocusE is not offered for column-sharded groups)
     KGE_RC(amdkge_cols_loss(m, &loss, d_sc, B, s->cfg.eta, s->acc, s->st));
-    amdkge_opt opt = s->cfg.opt;
-    opt.iteration = s->iteration + 1;
-    const int64_t need = amdkge_train_tiled_workspace_bytes(m, B, s->cfg.eta);
+    const amdkge_opt opt = step_opt(s);
+    int64_t need = 0;
+    KGE_RC(session_twork(s, m, B, &need));
     if (need <= 0) return set_error(AMDKGE_EUNSUPPORTED, "session_group_train_step: the column-sharded step needs the owner-computes pair for this slice shape");
-    if (need > s->twork_bytes) {
-        if (s->twork) KGE_HIP(hipFree(s->twork), "hipFree(twork)");
-        s->twork = nullptr; s->twork_bytes = 0;
-        KGE_HIP(hipMalloc(&s->twork, (size_t)need), "hipMalloc(twork)");
-        KGE_HIP(hipMemsetAsync(s->twork, 0, (size_t)need, s->st), "hipMemsetAsync(twork)");
-        s->twork_bytes = need;
-    }
     const int rc = amdkge_train_step_tiled(m, &loss, &opt, s->tab[0], s->tab[1], s->tab[2], s->tab[3], s->tab[4], s->tab[5], s->cfg.rel_reg_lambda,
                                            (const int32_t*)d_tri, B, s->cfg.eta, 0, m->n_ents, s->cfg.seed, s->step, 0, 0, nullptr, s->g_ent, s->g_rel, 1,
                                            AMDKGE_TILED_GIVEN_COEFFS, s->acc, s->acc + 1, d_sc, d_sc + B, s->twork, s->st);
-    if (rc != AMDKGE_OK) { (void)hipFree(s->twork); s->twork = nullptr; s->twork_bytes = 0; }
+    if (rc != AMDKGE_OK) session_drop_twork(s);
     return rc;
 }
 
@@ -342,7 +348,7 @@ extern "C" int amdkge_session_score(amdkge_session* s, const int32_t* triples, i
     if (!s || n < 0) return set_error(AMDKGE_EINVAL, "session_score: bad arguments");
     if (n == 0) return AMDKGE_OK;
     if (!triples || !scores_out) return set_error(AMDKGE_EINVAL, "session_score: NULL buffer");
-    KGE_RC(check_triples(s, triples, n, "session_score"));
+    KGE_RC(session_check_triples(triples, n, s->cfg.model.n_ents, s->cfg.model.n_rels, "session_score"));
     KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
     void *d_tri, *d_sc;
     KGE_RC(upload(s, 0, triples, n * 3 * (int64_t)sizeof(int32_t), &d_tri));
@@ -428,7 +434,7 @@ extern "C" int amdkge_session_rank(amdkge_session* s, const int32_t* triples, in
     if (n == 0) return AMDKGE_OK;
     if (!triples || !ranks_out) return set_error(AMDKGE_EINVAL, "session_rank: NULL buffer");
     if (n_subset < 0 || (n_subset > 0 && !ent_subset)) return set_error(AMDKGE_EINVAL, "session_rank: bad entities subset");
-    KGE_RC(check_triples(s, triples, n, "session_rank"));
+    KGE_RC(session_check_triples(triples, n, s->cfg.model.n_ents, s->cfg.model.n_rels, "session_rank"));
     const amdkge_model* m = &s->cfg.model;
     KGE_RC(amdkge_session_check_filter(fs_off, fs_ids, n, m->n_ents, "session_rank"));
     KGE_RC(amdkge_session_check_filter(fo_off, fo_ids, n, m->n_ents, "session_rank"));
@@ -439,16 +445,13 @@ extern "C" int amdkge_session_rank(amdkge_session* s, const int32_t* triples, in
     const int32_t* d_ent_ids = nullptr;
     const int32_t* d_subset_pos = nullptr;
     int64_t ent_hi = m->n_ents;
-    if (n_subset > 0) {   // entities_subset: candidate list + id -> position table (last wins, ScoringBasedEmbeddingModel.py:1639-1643)
-        std::vector<int32_t> pos((size_t)m->n_ents, -1);
-        for (int64_t i = 0; i < n_subset; ++i) {
-            if (ent_subset[i] < 0 || ent_subset[i] >= m->n_ents) return set_error(AMDKGE_EINVAL, "session_rank: subset id outside the entity table");
-            pos[(size_t)ent_subset[i]] = (int32_t)i;
-        }
+    if (n_subset > 0) {   // entities_subset: candidate list + id -> position table (kge_group_staging.h)
+        std::vector<int32_t> lst, pos;
+        if (!stage_subset(ent_subset, n_subset, m->n_ents, 0, m->n_ents, m->n_ents, lst, pos)) return set_error(AMDKGE_EINVAL, "session_rank: subset id outside the entity table");
         KGE_RC(scratch(s, 6, (n_subset + m->n_ents) * (int64_t)sizeof(int32_t), &d_sel));
-        KGE_HIP(hipMemcpyAsync(d_sel, ent_subset, (size_t)n_subset * sizeof(int32_t), hipMemcpyHostToDevice, s->st), "hipMemcpyAsync(H2D)");
+        KGE_HIP(hipMemcpyAsync(d_sel, lst.data(), (size_t)n_subset * sizeof(int32_t), hipMemcpyHostToDevice, s->st), "hipMemcpyAsync(H2D)");
         KGE_HIP(hipMemcpyAsync((int32_t*)d_sel + n_subset, pos.data(), (size_t)m->n_ents * sizeof(int32_t), hipMemcpyHostToDevice, s->st), "hipMemcpyAsync(H2D)");
-        KGE_HIP(hipStreamSynchronize(s->st), "hipStreamSynchronize");   // `pos` leaves scope below
+        KGE_HIP(hipStreamSynchronize(s->st), "hipStreamSynchronize");   // the host lists leave scope below
         d_ent_ids = (const int32_t*)d_sel;
         d_subset_pos = (const int32_t*)d_sel + n_subset;
         ent_hi = n_subset;
@@ -456,8 +459,7 @@ extern "C" int amdkge_session_rank(amdkge_session* s, const int32_t* triples, in
     const bool two_cols = corrupt_side == AMDKGE_CORRUPT_S_O;
     int col = 0;
     for (int side = AMDKGE_SIDE_S; side <= AMDKGE_SIDE_O; ++side) {
-        const bool want = (side == AMDKGE_SIDE_S) ? (corrupt_side != AMDKGE_CORRUPT_O) : (corrupt_side != AMDKGE_CORRUPT_S);
-        if (!want) continue;
+        if (!rank_side_wanted(side, corrupt_side)) continue;
         const int64_t* off = (side == AMDKGE_SIDE_S) ? fs_off : fo_off;
         const int32_t* ids = (side == AMDKGE_SIDE_S) ? fs_ids : fo_ids;
         int32_t* d_counts = nullptr;
@@ -469,16 +471,7 @@ extern "C" int amdkge_session_rank(amdkge_session* s, const int32_t* triples, in
     if (s->screen_ran) {   // (of the LAST side counted: the workspace is reused per side)
         KGE_HIP(hipMemcpyAsync(s->screen_stats, s->buf[7], sizeof(s->screen_stats), hipMemcpyDeviceToHost, s->st), "hipMemcpyAsync(D2H)");
     }
-    if (corrupt_side == AMDKGE_CORRUPT_S_PLUS_O) {   // the two 0-based sides are summed, then +1 (:1459-1463,1684)
-        std::vector<int32_t> h((size_t)2 * n);
-        KGE_HIP(hipMemcpyAsync(h.data(), d_ranks, (size_t)2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, s->st), "hipMemcpyAsync(D2H)");
-        KGE_HIP(hipStreamSynchronize(s->st), "hipStreamSynchronize");
-        for (int64_t i = 0; i < n; ++i) ranks_out[i] = h[(size_t)i] + h[(size_t)(n + i)] - 1;
-        return AMDKGE_OK;
-    }
-    KGE_HIP(hipMemcpyAsync(ranks_out, d_ranks, (size_t)n * (two_cols ? 2 : 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s->st), "hipMemcpyAsync(D2H)");
-    KGE_HIP(hipStreamSynchronize(s->st), "hipStreamSynchronize");
-    return AMDKGE_OK;
+    return session_ranks_to_host(s, (const int32_t*)d_ranks, n, corrupt_side, ranks_out);
 } KGE_CATCH("session_rank")
 
 extern "C" int amdkge_session_screen_stats(const amdkge_session* s, int32_t* ran, int64_t* rechecked_pairs, int32_t* fell_back) try {

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "kge_group_staging.h"
@@ -28,9 +29,6 @@
 using namespace kge;
 
 namespace {
-
-#define KGE_HIP(call, what) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return set_error_hip(e_, what); } while (0)
-#define KGE_RC(call) do { const int rc_ = (call); if (rc_ != AMDKGE_OK) return rc_; } while (0)
 
 // the slice of rccl.h this file needs (ABI of RCCL 2.x: ncclResult_t / ncclDataType_t / ncclRedOp_t are plain enums)
 typedef void* ncclComm_t;
@@ -67,7 +65,8 @@ int load_rccl(Rccl& r) {
     return AMDKGE_OK;
 }
 
-// same-device replicas: dst[0] = sum of all, then every replica receives the sum (grid-stride, float4 body + tail)
+// same-device replicas: every replica receives the sum over all of them.  fp32 (gradients, partial scores): in place, grid-stride,
+// float4 body + tail; int32 (bit patterns of gathered rows, rank counts): src -> dst
 struct SumArgs { float* p[16]; int n; int64_t len; };
 __global__ void replica_sum_kernel(SumArgs a) {
     const int64_t n4 = a.len >> 2;
@@ -81,6 +80,29 @@ __global__ void replica_sum_kernel(SumArgs a) {
         for (int q = 1; q < a.n; ++q) t += a.p[q][i];
         for (int q = 0; q < a.n; ++q) a.p[q][i] = t;
     }
+}
+struct ISumArgs { const int32_t* src[16]; int32_t* dst[16]; int n; int64_t len; };
+__global__ void replica_isum_kernel(ISumArgs a) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.len; i += (int64_t)gridDim.x * blockDim.x) {
+        int32_t t = a.src[0][i];
+        for (int q = 1; q < a.n; ++q) t += a.src[q][i];
+        for (int q = 0; q < a.n; ++q) a.dst[q][i] = t;
+    }
+}
+unsigned sum_grid(int64_t work) { return (unsigned)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096); }
+int launch_replica_sum(hipStream_t st, int n, int64_t len, const float* const*, float* const* dst) {   // (fp32 sums are in place: src == dst)
+    SumArgs a{};
+    a.n = n; a.len = len;
+    for (int d = 0; d < n; ++d) a.p[d] = dst[d];
+    hipLaunchKernelGGL(replica_sum_kernel, dim3(sum_grid((len + 3) / 4)), dim3(256), 0, st, a);
+    return check_launch("replica_sum");
+}
+int launch_replica_sum(hipStream_t st, int n, int64_t len, const int32_t* const* src, int32_t* const* dst) {
+    ISumArgs a{};
+    a.n = n; a.len = len;
+    for (int d = 0; d < n; ++d) { a.src[d] = src[d]; a.dst[d] = dst[d]; }
+    hipLaunchKernelGGL(replica_isum_kernel, dim3(sum_grid(len)), dim3(256), 0, st, a);
+    return check_launch("replica_isum");
 }
 
 }  // namespace
@@ -103,6 +125,7 @@ struct amdkge_session_group {
         void* route_work = nullptr;
         float *rows_out = nullptr, *back = nullptr;
         double* acc3 = nullptr;     // [data loss, entity-shard regulariser, relation regulariser]
+        std::vector<void*> owned;   // every device allocation above, as create_rows made them: what destroy frees
     };
     std::vector<Shard> sh;
     // ---- AMDKGE_GROUP_COLS: every table COLUMN-sharded over the replicas (see the COLS section below) ----
@@ -117,10 +140,7 @@ extern "C" void amdkge_session_group_destroy(amdkge_session_group* g) {
     for (size_t d = 0; d < g->sh.size() && d < g->rep.size(); ++d) {
         (void)hipSetDevice(g->rep[d]->cfg.device);
         if (g->rep[d]->st) (void)hipStreamSynchronize(g->rep[d]->st);
-        amdkge_session_group::Shard& h = g->sh[d];
-        for (void* p : {(void*)h.tri, (void*)h.negs, (void*)h.xl, (void*)h.nl, (void*)h.send, (void*)h.recv, (void*)h.counts, h.route_work,
-                        (void*)h.rows_out, (void*)h.back, (void*)h.acc3})
-            if (p) (void)hipFree(p);
+        for (void* p : g->sh[d].owned) (void)hipFree(p);
     }
     for (size_t d = 0; d < g->comm.size(); ++d)
         if (g->comm[d] && g->rccl.CommDestroy) (void)g->rccl.CommDestroy(g->comm[d]);
@@ -212,39 +232,64 @@ extern "C" int amdkge_session_group_set_rows(amdkge_session_group* g, int32_t ta
     return AMDKGE_OK;
 } KGE_CATCH("session_group_set_rows")
 
-// sum `len` floats at `ptr_of(replica)` over the replicas, result on every replica, stream-ordered on each replica's stream
-static int group_sum(amdkge_session_group* g, float* (*ptr_of)(amdkge_session*), int64_t len) {
+// dst(d)[i] = sum over the replicas q of src(q)[i] (T: float or int32_t; dst may be src), on every replica, stream-ordered on each
+// replica's stream: nothing to add for a single replica, events + the library's kernel for same-device replicas, else one grouped ncclAllReduce
+template <class T, class FS, class FD>
+static int group_sum(amdkge_session_group* g, FS src, FD dst, int64_t len) {
+    constexpr bool fp = std::is_same<T, float>::value;
     const int n = (int)g->rep.size();
-    if ((n == 1 && g->comm.empty()) || len == 0) return AMDKGE_OK;
+    if (len == 0) return AMDKGE_OK;
+    if (n == 1 && g->comm.empty()) {
+        if ((const void*)src(0) != (const void*)dst(0)) {
+            KGE_HIP(hipSetDevice(g->rep[0]->cfg.device), "hipSetDevice");
+            KGE_HIP(hipMemcpyAsync(dst(0), src(0), (size_t)len * sizeof(T), hipMemcpyDeviceToDevice, g->rep[0]->st), "hipMemcpyAsync(D2D)");
+        }
+        return AMDKGE_OK;
+    }
     if (g->same_device) {
-        // replica 0's stream waits for the others' work, sums in place for everybody, and the others wait for the sum
+        // replica 0's stream waits for the others' work, sums for everybody, and the others wait for the sum
         amdkge_session* s0 = g->rep[0];
         KGE_HIP(hipSetDevice(s0->cfg.device), "hipSetDevice");
         for (int d = 1; d < n; ++d) {
             KGE_HIP(hipEventRecord(g->ev[d], g->rep[d]->st), "hipEventRecord");
             KGE_HIP(hipStreamWaitEvent(s0->st, g->ev[d], 0), "hipStreamWaitEvent");
         }
-        SumArgs a{};
-        a.n = n; a.len = len;
-        for (int d = 0; d < n; ++d) a.p[d] = ptr_of(g->rep[d]);
-        const int64_t n4 = (len + 3) / 4;
-        const unsigned grid = (unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-        hipLaunchKernelGGL(replica_sum_kernel, dim3(grid), dim3(256), 0, s0->st, a);
-        KGE_RC(check_launch("replica_sum"));
+        const T* sp[16]; T* dp[16];
+        for (int d = 0; d < n; ++d) { sp[d] = src(d); dp[d] = dst(d); }
+        KGE_RC(launch_replica_sum(s0->st, n, len, sp, dp));
         KGE_HIP(hipEventRecord(g->ev[0], s0->st), "hipEventRecord");
         for (int d = 1; d < n; ++d) KGE_HIP(hipStreamWaitEvent(g->rep[d]->st, g->ev[0], 0), "hipStreamWaitEvent");
         return AMDKGE_OK;
     }
     if (int rc = g->rccl.GroupStart()) return rccl_error(g->rccl, rc, "ncclGroupStart");
-    for (int d = 0; d < n; ++d) {
-        float* p = ptr_of(g->rep[d]);
-        if (int rc = g->rccl.AllReduce(p, p, (size_t)len, kNcclFloat, kNcclSum, g->comm[(size_t)d], g->rep[d]->st)) {
+    for (int d = 0; d < n; ++d)
+        if (int rc = g->rccl.AllReduce(src(d), dst(d), (size_t)len, fp ? kNcclFloat : kNcclInt32, kNcclSum, g->comm[(size_t)d], g->rep[d]->st)) {
             (void)g->rccl.GroupEnd();
-            return rccl_error(g->rccl, rc, "ncclAllReduce");
+            return rccl_error(g->rccl, rc, fp ? "ncclAllReduce" : "ncclAllReduce(int32)");
         }
-    }
     if (int rc = g->rccl.GroupEnd()) return rccl_error(g->rccl, rc, "ncclGroupEnd");
     return AMDKGE_OK;
+}
+// the in-place fp32 form: `len` floats at ptr_of(replica)
+template <class F>
+static int group_sum_floats(amdkge_session_group* g, F ptr_of, int64_t len) {
+    auto p = [&](int d) { return ptr_of(g->rep[(size_t)d]); };
+    return group_sum<float>(g, p, p, len);
+}
+
+// A step that fails part-way -- some replicas have accumulated g_ent / g_rel, an exchange is half enqueued -- must not leave gradients
+// behind that a retried step would add to: every replica's gradient tables are cleared over all the rows it allocated (a row shard's
+// scratch rows included) and its workspace is dropped (bookkeeping may be dirty).  The failed call's error message is kept (the
+// clean-up reports nothing).
+static void group_abandon_step(amdkge_session_group* g) {
+    for (amdkge_session* s : g->rep) {
+        (void)hipSetDevice(s->cfg.device);
+        (void)hipStreamSynchronize(s->st);
+        (void)hipMemsetAsync(s->g_ent, 0, (size_t)s->cfg.model.n_ents * s->Ks * sizeof(float), s->st);
+        (void)hipMemsetAsync(s->g_rel, 0, (size_t)s->cfg.model.n_rels * s->Ks * sizeof(float), s->st);
+        session_drop_twork(s);
+        (void)hipStreamSynchronize(s->st);
+    }
 }
 
 extern "C" int amdkge_session_group_train_step(amdkge_session_group* g, const int32_t* triples, int64_t B, const float* focus_w, double* loss_out) try {
@@ -260,20 +305,13 @@ extern "C" int amdkge_session_group_train_step(amdkge_session_group* g, const in
     for (int d = 0; d < n; ++d) {
         const int64_t lo = B * d / n, hi = B * (d + 1) / n;
         if (const int rc = amdkge_session_grad_step(g->rep[d], triples + 3 * lo, hi - lo, focus_w ? focus_w + lo : nullptr, lo, B)) {
-            // replicas 0 .. d-1 already hold this batch's gradients: clear them, or the next call would add to them (their loss
-            // accumulators are reset by every grad_step)
-            for (int q = 0; q < d; ++q) {
-                amdkge_session* s = g->rep[q];
-                (void)hipSetDevice(s->cfg.device);
-                (void)hipMemsetAsync(s->g_ent, 0, (size_t)s->cfg.model.n_ents * s->Ks * sizeof(float), s->st);
-                (void)hipMemsetAsync(s->g_rel, 0, (size_t)s->cfg.model.n_rels * s->Ks * sizeof(float), s->st);
-            }
+            group_abandon_step(g);   // (replicas 0 .. d-1 already hold this batch's gradients; the loss accumulators are reset by every grad_step)
             return rc;
         }
     }
     // ---- 2. gradient sum over the replicas (RCCL all-reduce, or the local sum of same-device replicas) ----
-    KGE_RC(group_sum(g, [](amdkge_session* s) { return s->g_ent; }, g->rep[0]->cfg.model.n_ents * (int64_t)g->rep[0]->Ks));
-    KGE_RC(group_sum(g, [](amdkge_session* s) { return s->g_rel; }, g->rep[0]->cfg.model.n_rels * (int64_t)g->rep[0]->Ks));
+    KGE_RC(group_sum_floats(g, [](amdkge_session* s) { return s->g_ent; }, g->rep[0]->cfg.model.n_ents * (int64_t)g->rep[0]->Ks));
+    KGE_RC(group_sum_floats(g, [](amdkge_session* s) { return s->g_rel; }, g->rep[0]->cfg.model.n_rels * (int64_t)g->rep[0]->Ks));
     // ---- 3. every replica: the same dense sweep; data loss = sum of the shares, regulariser terms from replica 0 ----
     double data = 0.0, reg = 0.0;
     for (int d = 0; d < n; ++d) KGE_RC(amdkge_session_apply_step(g->rep[d]));
@@ -327,10 +365,7 @@ namespace {
 
 typedef amdkge_session_group::Shard Shard;
 
-int64_t table_rows_global(const amdkge_session_group* g, int t) {
-    return (t == AMDKGE_TABLE_ENT || t == AMDKGE_TABLE_ENT_SLOT0 || t == AMDKGE_TABLE_ENT_SLOT1) ? g->N : g->rep[0]->cfg.model.n_rels;
-}
-bool is_entity_table(int t) { return t == AMDKGE_TABLE_ENT || t == AMDKGE_TABLE_ENT_SLOT0 || t == AMDKGE_TABLE_ENT_SLOT1; }
+int64_t table_rows_global(const amdkge_session_group* g, int t) { return is_entity_table(t) ? g->N : g->rep[0]->cfg.model.n_rels; }
 
 // all_to_all with equal splits: slice q of `send(d)` (elems elements of `bytes_per` bytes) -> slice d of `recv(q)`, stream-ordered on
 // every replica's stream.  The self slice is a device-to-device copy; the others go through RCCL or, for same-device replicas, copies
@@ -411,18 +446,17 @@ extern "C" int amdkge_session_group_create_rows(const amdkge_session_config* cfg
         const int64_t hi = (int64_t)(d + 1) * rows_per < N ? (int64_t)(d + 1) * rows_per : N;
         h.n_local = hi - h.lo;
         if (hipError_t e = hipSetDevice(s->cfg.device)) return fail(set_error_hip(e, "hipSetDevice"));
-        auto alloc = [&](void** p, size_t bytes) -> int { const hipError_t e = hipMalloc(p, bytes ? bytes : 16); return e == hipSuccess ? AMDKGE_OK : set_error_hip(e, "hipMalloc(row-shard scratch)"); };
-        int rc = alloc((void**)&h.tri, (size_t)share * 12);
-        if (!rc) rc = alloc((void**)&h.negs, (size_t)nneg * 12);
-        if (!rc) rc = alloc((void**)&h.xl, (size_t)share * 12);
-        if (!rc) rc = alloc((void**)&h.nl, (size_t)nneg * 12);
-        if (!rc) rc = alloc((void**)&h.send, (size_t)W * cap * 4);
-        if (!rc) rc = alloc((void**)&h.recv, (size_t)W * cap * 4);
-        if (!rc) rc = alloc((void**)&h.counts, (size_t)(W + 1) * 4);
-        if (!rc) rc = alloc(&h.route_work, (size_t)rw);
-        if (!rc) rc = alloc((void**)&h.rows_out, (size_t)W * cap * s->Ks * 4);
-        if (!rc) rc = alloc((void**)&h.back, (size_t)W * cap * s->Ks * 4);
-        if (!rc) rc = alloc((void**)&h.acc3, 3 * sizeof(double));
+        int rc = AMDKGE_OK;
+        auto alloc = [&](auto*& p, size_t bytes) {
+            void* q = nullptr;
+            if (rc) return;
+            if (const hipError_t e = hipMalloc(&q, bytes ? bytes : 16)) { rc = set_error_hip(e, "hipMalloc(row-shard scratch)"); return; }
+            h.owned.push_back(q);
+            p = static_cast<std::remove_reference_t<decltype(p)>>(q);
+        };
+        alloc(h.tri, (size_t)share * 12); alloc(h.negs, (size_t)nneg * 12); alloc(h.xl, (size_t)share * 12); alloc(h.nl, (size_t)nneg * 12);
+        alloc(h.send, (size_t)W * cap * 4); alloc(h.recv, (size_t)W * cap * 4); alloc(h.counts, (size_t)(W + 1) * 4); alloc(h.route_work, (size_t)rw);
+        alloc(h.rows_out, (size_t)W * cap * s->Ks * 4); alloc(h.back, (size_t)W * cap * s->Ks * 4); alloc(h.acc3, 3 * sizeof(double));
         if (rc) return fail(rc);
         if (hipError_t e = hipMemsetAsync(h.counts, 0, (size_t)(W + 1) * 4, s->st)) return fail(set_error_hip(e, "hipMemsetAsync"));
         if (hipError_t e = hipStreamSynchronize(s->st)) return fail(set_error_hip(e, "hipStreamSynchronize"));
@@ -500,23 +534,9 @@ extern "C" int amdkge_session_group_route_overflow(amdkge_session_group* g, int3
 
 static int rows_train_step_body(amdkge_session_group* g, const int32_t* triples, int64_t B, const float* focus_w, double* loss_out);
 
-//  a step that fails part-way -- some replicas have accumulated g_ent / g_rel, an exchange is half enqueued -- must not
-// leave gradients behind that a retried step would add to: on ANY error every replica's gradient tables (shard + scratch rows) are
-// cleared and its workspace is dropped (bookkeeping may be dirty), as the replicated group step does.  The error message of the
-// failed call is kept (the clean-up below reports nothing).
 static int rows_train_step(amdkge_session_group* g, const int32_t* triples, int64_t B, const float* focus_w, double* loss_out) {
     const int rc = rows_train_step_body(g, triples, B, focus_w, loss_out);
-    if (rc == AMDKGE_OK) return rc;
-    const int64_t Wcap = (int64_t)g->rep.size() * g->cap;
-    for (size_t d = 0; d < g->rep.size(); ++d) {
-        amdkge_session* s = g->rep[d];
-        (void)hipSetDevice(s->cfg.device);
-        (void)hipStreamSynchronize(s->st);
-        (void)hipMemsetAsync(s->g_ent, 0, (size_t)(g->sh[d].n_local + Wcap) * s->Ks * sizeof(float), s->st);
-        (void)hipMemsetAsync(s->g_rel, 0, (size_t)s->cfg.model.n_rels * s->Ks * sizeof(float), s->st);
-        if (s->twork) { (void)hipFree(s->twork); s->twork = nullptr; s->twork_bytes = 0; }
-        (void)hipStreamSynchronize(s->st);
-    }
+    if (rc != AMDKGE_OK) group_abandon_step(g);   // (on ANY error, as the replicated group step does)
     return rc;
 }
 
@@ -527,11 +547,9 @@ static int rows_train_step_body(amdkge_session_group* g, const int32_t* triples,
     if (!triples) return set_error(AMDKGE_EINVAL, "session_group_train_step: NULL triples");
     if ((B + W - 1) / W > g->max_share) return set_error(AMDKGE_EINVAL, "session_group_train_step: batch larger than the max_batch the row-sharded group was created for");
     const amdkge_session_config& c0 = g->rep[0]->cfg;
+    // (session_step_loss would refuse this in step 3, behind the routing and two exchanges: an argument error is refused before any device work)
     if (focus_w && !c0.loss.focus_nonlinearity) return set_error(AMDKGE_EINVAL, "session_group_train_step: FocusE weights given but the group's loss has focus_nonlinearity == 0");
-    for (int64_t i = 0; i < B; ++i)
-        if (triples[3 * i] < 0 || triples[3 * i] >= g->N || triples[3 * i + 2] < 0 || triples[3 * i + 2] >= g->N || triples[3 * i + 1] < 0 ||
-            triples[3 * i + 1] >= c0.model.n_rels)
-            return set_error(AMDKGE_EINVAL, "session_group_train_step: a triple has an entity / relation id outside the tables");
+    KGE_RC(session_check_triples(triples, B, g->N, c0.model.n_rels, "session_group_train_step"));
     const bool global = (g->flags & AMDKGE_GROUP_GLOBAL_NEGATIVES) != 0;
     const int eta = c0.eta;
     const int64_t cap = g->cap, Wcap = (int64_t)W * cap;
@@ -568,38 +586,13 @@ static int rows_train_step_body(amdkge_session_group* g, const int32_t* triples,
         KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
         amdkge_model m = s->cfg.model;
         m.n_ents = h.n_local + Wcap;
-        amdkge_loss loss = s->cfg.loss;
-        if (focus_w) {   // (FocusE weights of the share ride in the session's scratch slot 1)
-            if (s->buf_bytes[1] < b * (int64_t)sizeof(float)) {
-                if (s->buf[1]) KGE_HIP(hipFree(s->buf[1]), "hipFree(scratch)");
-                s->buf[1] = nullptr; s->buf_bytes[1] = 0;
-                KGE_HIP(hipMalloc(&s->buf[1], (size_t)b * sizeof(float)), "hipMalloc(scratch)");
-                s->buf_bytes[1] = b * (int64_t)sizeof(float);
-            }
-            KGE_HIP(hipMemcpyAsync(s->buf[1], focus_w + lo, (size_t)b * sizeof(float), hipMemcpyHostToDevice, s->st), "hipMemcpyAsync(H2D)");
-            loss.d_focus_w = (const float*)s->buf[1];
-        } else { loss.focus_nonlinearity = AMDKGE_FOCUS_OFF; loss.d_focus_w = nullptr; }
+        amdkge_loss loss;
+        KGE_RC(session_step_loss(s, focus_w, lo, b, "session_group_train_step", "group", &loss));
         amdkge_opt opt = s->cfg.opt;
         opt.iteration = g->iteration + 1;
         const int64_t srange = global ? m.n_ents : h.n_local;   // shard-local negatives: replacement rows are local rows [0, n_local)
-        const int32_t* nov = global ? h.nl : nullptr;
-        const int64_t need = amdkge_train_tiled_workspace_bytes(&m, b, eta);
-        if (need > 0) {
-            if (need > s->twork_bytes) {
-                if (s->twork) KGE_HIP(hipFree(s->twork), "hipFree(twork)");
-                s->twork = nullptr; s->twork_bytes = 0;
-                KGE_HIP(hipMalloc(&s->twork, (size_t)need), "hipMalloc(twork)");
-                KGE_HIP(hipMemsetAsync(s->twork, 0, (size_t)need, s->st), "hipMemsetAsync(twork)");
-                s->twork_bytes = need;
-            }
-            const int rc = amdkge_train_step_tiled(&m, &loss, &opt, s->tab[0], s->tab[1], nullptr, nullptr, nullptr, nullptr, 0.f, h.xl, b, eta, 0, srange,
-                                                   c0.seed, g->step, lo, B, nov, s->g_ent, s->g_rel, 0, s->cfg.flags & AMDKGE_TILED_POS_ATOMIC, h.acc3,
-                                                   h.acc3 + 1, nullptr, nullptr, s->twork, s->st);
-            if (rc != AMDKGE_OK) { (void)hipFree(s->twork); s->twork = nullptr; s->twork_bytes = 0; return rc; }
-        } else {
-            KGE_RC(amdkge_train_fwdbwd(&m, &loss, s->tab[0], s->tab[1], h.xl, b, eta, 0, srange, c0.seed, g->step, lo, B, nov, s->g_ent, s->g_rel, h.acc3,
-                                       nullptr, nullptr, s->st));
-        }
+        KGE_RC(session_share_kernels(s, &m, &loss, &opt, h.xl, b, srange, g->step, lo, B, global ? h.nl : nullptr, 0, s->cfg.flags & AMDKGE_TILED_POS_ATOMIC,
+                                     h.acc3, h.acc3 + 1, nullptr));
     }
     // ---- 4. gradients of the fetched copies go home; the relation gradient is summed over the replicas ----
     KGE_RC(exchange(g, [&](int d) { return (void*)(g->rep[d]->g_ent + g->sh[(size_t)d].n_local * (int64_t)g->rep[d]->Ks); },
@@ -611,7 +604,7 @@ static int rows_train_step_body(amdkge_session_group* g, const int32_t* triples,
         KGE_RC(amdkge_scatter_add_rows(s->g_ent, s->Ks, h.recv, Wcap, h.back, s->st));
         KGE_HIP(hipMemsetAsync(s->g_ent + h.n_local * (int64_t)s->Ks, 0, (size_t)Wcap * s->Ks * sizeof(float), s->st), "hipMemsetAsync(scratch gradients)");
     }
-    KGE_RC(group_sum(g, [](amdkge_session* s) { return s->g_rel; }, c0.model.n_rels * (int64_t)g->rep[0]->Ks));
+    KGE_RC(group_sum_floats(g, [](amdkge_session* s) { return s->g_rel; }, c0.model.n_rels * (int64_t)g->rep[0]->Ks));
     // ---- 5. every replica sweeps its rows and the replicated relation table ----
     double data = 0.0, reg = 0.0;
     for (int d = 0; d < W; ++d) {
@@ -620,12 +613,7 @@ static int rows_train_step_body(amdkge_session_group* g, const int32_t* triples,
         KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
         amdkge_opt opt = s->cfg.opt;
         opt.iteration = g->iteration + 1;
-        if (h.n_local > 0) KGE_RC(amdkge_opt_step(&opt, s->tab[0], s->g_ent, s->tab[2], s->tab[3], h.n_local * (int64_t)s->Ks, h.acc3 + 1, s->st));
-        amdkge_opt orel = opt;
-        orel.reg_lambda = s->cfg.rel_reg_lambda;
-        if (opt.rel_reg_p > 0) orel.reg_p = opt.rel_reg_p;
-        orel.reg2_p = opt.rel_reg2_p; orel.reg2_lambda = opt.rel_reg2_lambda;
-        KGE_RC(amdkge_opt_step(&orel, s->tab[1], s->g_rel, s->tab[4], s->tab[5], c0.model.n_rels * (int64_t)s->Ks, h.acc3 + 2, s->st));
+        KGE_RC(session_dense_sweep(s, &opt, h.n_local, h.acc3 + 1, h.acc3 + 2));
     }
     for (int d = 0; d < W; ++d) {
         amdkge_session* s = g->rep[d];
@@ -656,54 +644,6 @@ static int rows_train_step_body(amdkge_session_group* g, const int32_t* triples,
 //   replicated group: every replica holds the whole model: the queries are split over the replicas (one host thread per device).
 // Ranks are those of amdkge_session_rank on the whole table, bit for bit (integer counts of the same per-pair comparisons).
 namespace {
-
-struct ISumArgs { const int32_t* src[16]; int32_t* dst[16]; int n; int64_t len; };
-__global__ void replica_isum_kernel(ISumArgs a) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.len; i += (int64_t)gridDim.x * blockDim.x) {
-        int32_t t = a.src[0][i];
-        for (int q = 1; q < a.n; ++q) t += a.src[q][i];
-        for (int q = 0; q < a.n; ++q) a.dst[q][i] = t;
-    }
-}
-
-// dst(d)[i] = sum over the replicas of src(q)[i] (int32), on every replica, stream-ordered on each replica's stream
-template <class FS, class FD>
-int group_isum(amdkge_session_group* g, FS src, FD dst, int64_t len) {
-    const int n = (int)g->rep.size();
-    if (len == 0) return AMDKGE_OK;
-    if (n == 1 && g->comm.empty()) {
-        if ((const void*)src(0) != (const void*)dst(0)) {
-            KGE_HIP(hipSetDevice(g->rep[0]->cfg.device), "hipSetDevice");
-            KGE_HIP(hipMemcpyAsync(dst(0), src(0), (size_t)len * 4, hipMemcpyDeviceToDevice, g->rep[0]->st), "hipMemcpyAsync(D2D)");
-        }
-        return AMDKGE_OK;
-    }
-    if (g->same_device) {
-        amdkge_session* s0 = g->rep[0];
-        KGE_HIP(hipSetDevice(s0->cfg.device), "hipSetDevice");
-        for (int d = 1; d < n; ++d) {
-            KGE_HIP(hipEventRecord(g->ev[d], g->rep[d]->st), "hipEventRecord");
-            KGE_HIP(hipStreamWaitEvent(s0->st, g->ev[d], 0), "hipStreamWaitEvent");
-        }
-        ISumArgs a{};
-        a.n = n; a.len = len;
-        for (int d = 0; d < n; ++d) { a.src[d] = src(d); a.dst[d] = dst(d); }
-        const unsigned grid = (unsigned)((len + 255) / 256 < 4096 ? (len + 255) / 256 : 4096);
-        hipLaunchKernelGGL(replica_isum_kernel, dim3(grid), dim3(256), 0, s0->st, a);
-        KGE_RC(check_launch("replica_isum"));
-        KGE_HIP(hipEventRecord(g->ev[0], s0->st), "hipEventRecord");
-        for (int d = 1; d < n; ++d) KGE_HIP(hipStreamWaitEvent(g->rep[d]->st, g->ev[0], 0), "hipStreamWaitEvent");
-        return AMDKGE_OK;
-    }
-    if (int rc = g->rccl.GroupStart()) return rccl_error(g->rccl, rc, "ncclGroupStart");
-    for (int d = 0; d < n; ++d)
-        if (int rc = g->rccl.AllReduce(src(d), dst(d), (size_t)len, kNcclInt32, kNcclSum, g->comm[(size_t)d], g->rep[d]->st)) {
-            (void)g->rccl.GroupEnd();
-            return rccl_error(g->rccl, rc, "ncclAllReduce(int32)");
-        }
-    if (int rc = g->rccl.GroupEnd()) return rccl_error(g->rccl, rc, "ncclGroupEnd");
-    return AMDKGE_OK;
-}
 
 // fn(d) for every replica d: ONE HOST THREAD PER REPLICA when the replicas sit on distinct devices (or AMDKGE_GROUP_FORCE_THREADS asks
 // for it on one device: what a one-GPU box can test) -- the calls fn makes (staging copies, launches, the 8-byte read-back of the
@@ -747,10 +687,7 @@ int rows_rank(amdkge_session_group* g, const int32_t* triples, int64_t n, const 
               const int32_t* fo_ids, const int32_t* ent_subset, int64_t n_subset, int32_t corrupt_side, int32_t strategy, int32_t* ranks_out) {
     const int W = (int)g->rep.size();
     const amdkge_session_config& c0 = g->rep[0]->cfg;
-    for (int64_t i = 0; i < n; ++i)
-        if (triples[3 * i] < 0 || triples[3 * i] >= g->N || triples[3 * i + 2] < 0 || triples[3 * i + 2] >= g->N || triples[3 * i + 1] < 0 ||
-            triples[3 * i + 1] >= c0.model.n_rels)
-            return set_error(AMDKGE_EINVAL, "session_group_rank: a triple has an entity / relation id outside the tables");
+    KGE_RC(session_check_triples(triples, n, g->N, c0.model.n_rels, "session_group_rank"));
     KGE_RC(amdkge_session_check_filter(fs_off, fs_ids, n, g->N, "session_group_rank"));
     KGE_RC(amdkge_session_check_filter(fo_off, fo_ids, n, g->N, "session_group_rank"));
     const int64_t S = (int64_t)W * g->cap;            // scratch rows behind every shard
@@ -761,37 +698,29 @@ int rows_rank(amdkge_session_group* g, const int32_t* triples, int64_t n, const 
     // id -> position table of the filter pass (last wins, ScoringBasedEmbeddingModel.py:1639-1643; -1 elsewhere, scratch rows included)
     std::vector<DevBuf> sel((size_t)W);
     std::vector<int64_t> nsel((size_t)W, 0);
-    if (n_subset > 0) {
-        std::vector<std::vector<int32_t>> lst((size_t)W), pos((size_t)W);
-        for (int d = 0; d < W; ++d) pos[(size_t)d].assign((size_t)(g->sh[(size_t)d].n_local + S), -1);
-        for (int64_t i = 0; i < n_subset; ++i) {
-            const int64_t id = ent_subset[i];
-            if (id < 0 || id >= g->N) return set_error(AMDKGE_EINVAL, "session_group_rank: subset id outside the entity table");
-            const size_t d = (size_t)(id / g->rows_per);
-            pos[d][(size_t)(id - g->sh[d].lo)] = (int32_t)lst[d].size();
-            lst[d].push_back((int32_t)(id - g->sh[d].lo));
-        }
-        for (int d = 0; d < W; ++d) {
-            amdkge_session* s = g->rep[d];
-            nsel[(size_t)d] = (int64_t)lst[(size_t)d].size();
-            KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
-            sel[(size_t)d].dev = s->cfg.device;
-            const size_t nl = lst[(size_t)d].size(), np = pos[(size_t)d].size();
-            KGE_HIP(hipMalloc(&sel[(size_t)d].p, (nl + np) * 4 + 16), "hipMalloc(subset lists)");
-            if (nl) KGE_HIP(hipMemcpyAsync(sel[(size_t)d].p, lst[(size_t)d].data(), nl * 4, hipMemcpyHostToDevice, s->st), "hipMemcpyAsync(H2D)");
-            KGE_HIP(hipMemcpyAsync((int32_t*)sel[(size_t)d].p + nl, pos[(size_t)d].data(), np * 4, hipMemcpyHostToDevice, s->st), "hipMemcpyAsync(H2D)");
-            KGE_HIP(hipStreamSynchronize(s->st), "hipStreamSynchronize");   // the host lists leave scope
-        }
+    std::vector<int32_t> lst, pos;
+    // (kge_group_staging.h: CPU-tested.  Every call validates the whole subset against N, so a bad id is refused at d = 0, before the first hipMalloc)
+    for (int d = 0; n_subset > 0 && d < W; ++d) {
+        amdkge_session* s = g->rep[d];
+        if (!stage_subset(ent_subset, n_subset, g->N, g->sh[(size_t)d].lo, g->sh[(size_t)d].n_local, g->sh[(size_t)d].n_local + S, lst, pos))
+            return set_error(AMDKGE_EINVAL, "session_group_rank: subset id outside the entity table");
+        const size_t nl = lst.size(), np = pos.size();
+        nsel[(size_t)d] = (int64_t)nl;
+        KGE_HIP(hipSetDevice(s->cfg.device), "hipSetDevice");
+        sel[(size_t)d].dev = s->cfg.device;
+        KGE_HIP(hipMalloc(&sel[(size_t)d].p, (nl + np) * 4 + 16), "hipMalloc(subset lists)");
+        if (nl) KGE_HIP(hipMemcpyAsync(sel[(size_t)d].p, lst.data(), nl * 4, hipMemcpyHostToDevice, s->st), "hipMemcpyAsync(H2D)");
+        KGE_HIP(hipMemcpyAsync((int32_t*)sel[(size_t)d].p + nl, pos.data(), np * 4, hipMemcpyHostToDevice, s->st), "hipMemcpyAsync(H2D)");
+        KGE_HIP(hipStreamSynchronize(s->st), "hipStreamSynchronize");   // the host lists are reused
     }
     const bool two_cols = corrupt_side == AMDKGE_CORRUPT_S_O;
-    const int ncols = (corrupt_side == AMDKGE_CORRUPT_S || corrupt_side == AMDKGE_CORRUPT_O) ? 1 : 2;
     // Host staging: everything a replica's copies read is PER REPLICA (xl, idxl) or read-only during the parallel phases (U, the CSR
     // slices), and lives until the chunk's closing synchronisation -- no synchronisation inside a phase (round 5 shared one `idx` and
     // synchronised every replica's stream before moving to the next: on distinct devices the shards' passes ran one after the other).
     // Per chunk the replicas meet exactly at the two kinds of exchange: the bit-wise sum of the gathered query rows and, per side, the
-    // int32 sum of the counts (group_isum: one grouped ncclAllReduce, or the local kernel); everything else of a replica -- staging,
+    // int32 sum of the counts (group_sum: one grouped ncclAllReduce, or the local kernel); everything else of a replica -- staging,
     // gather, prep, probe read-back, count and filter passes -- runs in its own host thread (for_each_replica).
-    std::vector<int32_t> U, hr;
+    std::vector<int32_t> U;
     std::vector<std::vector<int32_t>> xl((size_t)W), idxl((size_t)W);
     std::vector<int64_t> offs, offo;
     for (int64_t q0 = 0; q0 < n; q0 += chunk) {
@@ -816,7 +745,7 @@ int rows_rank(amdkge_session_group* g, const int32_t* triples, int64_t n, const 
             KGE_RC(amdkge_gather_rows(s->tab[AMDKGE_TABLE_ENT], Ks, h.recv, nu, h.rows_out, s->st));
             return AMDKGE_OK;
         }));
-        KGE_RC(group_isum(g, [&](int d) { return (const int32_t*)g->sh[(size_t)d].rows_out; },
+        KGE_RC(group_sum<int32_t>(g, [&](int d) { return (const int32_t*)g->sh[(size_t)d].rows_out; },
                           [&](int d) { return (int32_t*)(g->rep[d]->tab[AMDKGE_TABLE_ENT] + g->sh[(size_t)d].n_local * (int64_t)Ks); }, nu * (int64_t)Ks));
         // ---- every wanted side: per-shard counts, summed over the replicas, composed on replica 0 ----
         void* d_ranks = nullptr;
@@ -824,8 +753,7 @@ int rows_rank(amdkge_session_group* g, const int32_t* triples, int64_t n, const 
         KGE_RC(amdkge_session_scratch(g->rep[0], 3, nq * 2 * (int64_t)sizeof(int32_t), &d_ranks));
         int col = 0;
         for (int side = AMDKGE_SIDE_S; side <= AMDKGE_SIDE_O; ++side) {
-            const bool want = (side == AMDKGE_SIDE_S) ? (corrupt_side != AMDKGE_CORRUPT_O) : (corrupt_side != AMDKGE_CORRUPT_S);
-            if (!want) continue;
+            if (!rank_side_wanted(side, corrupt_side)) continue;
             const int64_t* off = (side == AMDKGE_SIDE_S) ? fs_off : fo_off;
             const int32_t* ids = (side == AMDKGE_SIDE_S) ? fs_ids : fo_ids;
             std::vector<int64_t>& lo = (side == AMDKGE_SIDE_S) ? offs : offo;
@@ -852,21 +780,18 @@ int rows_rank(amdkge_session_group* g, const int32_t* triples, int64_t n, const 
                 return AMDKGE_OK;
             }));
             KGE_HIP(hipSetDevice(g->rep[0]->cfg.device), "hipSetDevice");
-            KGE_RC(group_isum(g, [&](int d) { return (const int32_t*)c3[(size_t)d]; }, [&](int d) { return c3[(size_t)d]; }, nq * 3));
+            KGE_RC(group_sum<int32_t>(g, [&](int d) { return (const int32_t*)c3[(size_t)d]; }, [&](int d) { return c3[(size_t)d]; }, nq * 3));
             KGE_HIP(hipSetDevice(g->rep[0]->cfg.device), "hipSetDevice");
             KGE_RC(amdkge_rank_compose(c3[0], off ? c3[0] + 2 * nq : nullptr, nq, strategy, (int32_t*)d_ranks + (two_cols ? col : col * nq), two_cols ? 2 : 1, g->rep[0]->st));
             ++col;
         }
         // ---- the chunk's ranks to the host; every replica idle before its scratch (and the host staging above) is reused ----
-        hr.resize((size_t)(nq * ncols));
         KGE_HIP(hipSetDevice(g->rep[0]->cfg.device), "hipSetDevice");
-        KGE_HIP(hipMemcpyAsync(hr.data(), d_ranks, (size_t)nq * ncols * sizeof(int32_t), hipMemcpyDeviceToHost, g->rep[0]->st), "hipMemcpyAsync(D2H)");
-        for (int d = 0; d < W; ++d) {
+        KGE_RC(session_ranks_to_host(g->rep[0], (const int32_t*)d_ranks, nq, corrupt_side, ranks_out + q0 * (two_cols ? 2 : 1)));
+        for (int d = 1; d < W; ++d) {
             KGE_HIP(hipSetDevice(g->rep[d]->cfg.device), "hipSetDevice");
             KGE_HIP(hipStreamSynchronize(g->rep[d]->st), "hipStreamSynchronize");
         }
-        if (corrupt_side == AMDKGE_CORRUPT_S_PLUS_O) for (int64_t i = 0; i < nq; ++i) ranks_out[q0 + i] = hr[(size_t)i] + hr[(size_t)(nq + i)] - 1;   // (:1459-1463,1684)
-        else memcpy(ranks_out + q0 * ncols, hr.data(), (size_t)nq * ncols * sizeof(int32_t));
     }
     return AMDKGE_OK;
 }
@@ -989,14 +914,7 @@ static int cols_train_step(amdkge_session_group* g, const int32_t* triples, int6
     int applied = 0;
     const int rc = cols_train_step_body(g, triples, B, focus_w, loss_out, &applied);
     if (rc == AMDKGE_OK) return rc;
-    for (amdkge_session* s : g->rep) {
-        (void)hipSetDevice(s->cfg.device);
-        (void)hipStreamSynchronize(s->st);
-        (void)hipMemsetAsync(s->g_ent, 0, (size_t)s->cfg.model.n_ents * s->Ks * sizeof(float), s->st);
-        (void)hipMemsetAsync(s->g_rel, 0, (size_t)s->cfg.model.n_rels * s->Ks * sizeof(float), s->st);
-        if (s->twork) { (void)hipFree(s->twork); s->twork = nullptr; s->twork_bytes = 0; }
-        (void)hipStreamSynchronize(s->st);
-    }
+    group_abandon_step(g);
     if (applied > 0) g->poisoned = true;
     return rc;
 }
@@ -1011,7 +929,7 @@ static int cols_train_step_body(amdkge_session_group* g, const int32_t* triples,
     std::vector<float*> sc((size_t)W, nullptr);
     for (int d = 0; d < W; ++d) KGE_RC(amdkge_session_cols_scores(g->rep[d], triples, B, &sc[(size_t)d]));
     // ---- the one exchange of the step: the partial sums meet (ncclAllReduce over xGMI / the local kernel) ----
-    KGE_RC(group_sum(g, [](amdkge_session* s) { return (float*)s->buf[2]; }, B * (int64_t)(1 + g->rep[0]->cfg.eta)));
+    KGE_RC(group_sum_floats(g, [](amdkge_session* s) { return (float*)s->buf[2]; }, B * (int64_t)(1 + g->rep[0]->cfg.eta)));
     // ---- B + C: loss on the complete scores (the same values on every replica), backward / merge / optimizer on the slice ----
     for (int d = 0; d < W; ++d) {
         *applied = d + 1;   // (a slice whose apply fails may have launched part of its sequence: it counts)

@@ -453,3 +453,103 @@ def test_session_group_rank_replicated(gpu_lib, threads):
                               single.rank(T, _csr(fs), _csr(fo), corrupt_side=side, ranking_strategy="middle")), side
     single.close()
     group.close()
+
+
+@pytest.mark.parametrize("k,nl", [(8, "tanh"), (200, "linear")])
+def test_session_paths_with_focuse_weights_against_oracle(gpu_lib, k, nl):
+    """FocusE weights through every session path that sets up the loss of a step: a Session (the complete step), a replicated group
+    (gradient-only shares of 203 over 3: the weights of a share start at focus_w + lo) and a row-sharded group (203 over 2, global
+    negatives: the corruptions of one GPU), ComplEx k = 8 and the owner-computes shape k = 200.  Every loss and the final tables are
+    held to the oracle's step with focus=(w, beta, nl), beta the structural weight of the session's own config."""
+    from ampligraph_amd.latent_features import loss_functions, optimizers, regularizers
+    from ampligraph_amd.session import Session, SessionGroup
+
+    rng = np.random.default_rng(17)
+    model, N, R, B, eta, seed, lr = "ComplEx", 131, 4, 203, 3, 7, 1e-2
+    K = O.internal_k(model, k)
+    sc = 0.3 if k < 100 else 0.08
+    ent = (rng.normal(size=(N, K)) * sc).astype(np.float32)
+    rel = (rng.normal(size=(R, K)) * sc).astype(np.float32)
+    X = np.stack([rng.integers(0, N, 3 * B), rng.integers(0, R, 3 * B), rng.integers(0, N, 3 * B)], 1).astype(np.int32)
+    Wt = (0.05 + 0.9 * rng.random(3 * B)).astype(np.float32)
+    reg = regularizers.get("LP", {"p": 2, "lambda": 1e-3})
+    mk = lambda: (loss_functions.get("self_adversarial"), optimizers.get("adam", {"learning_rate": lr}))   # noqa: E731
+    beta = float(mk()[0].to_ffi().focus_beta)   # what Session / SessionGroup put into cfg.loss
+    runs = {"session": Session(model, k, N, R, eta, *mk(), reg, seed=seed, focus_nonlinearity=nl),
+            "replicated": SessionGroup([0, 0, 0], model, k, N, R, eta, *mk(), reg, seed=seed, focus_nonlinearity=nl),
+            "rows": SessionGroup([0, 0], model, k, N, R, eta, *mk(), reg, seed=seed, focus_nonlinearity=nl, rows=True, max_batch=B,
+                                 global_negatives=True)}
+    for s in runs.values():
+        s.set_rows("ent", ent)
+        s.set_rows("rel", rel)
+    st = O.TrainState(ent, rel, "adam", lr)
+    for t in range(3):
+        xb, wb = X[t * B:(t + 1) * B], Wt[t * B:(t + 1) * B]
+        ref = float(O.train_step(st, model, xb, eta, "self_adversarial", seed, t, max_rel_size=R, reg=dict(p=2, lam_e=1e-3, lam_r=1e-3),
+                                 focus=(wb, beta, nl)))
+        for name, s in runs.items():
+            got = s.train_step(xb, focus_w=wb)
+            print(f"focuse {name} k={k} step {t}: loss {got!r} oracle {ref!r} rel {abs(got - ref) / abs(ref):.3e}")
+            assert abs(got - ref) <= 3e-5 * abs(ref), (name, t, got, ref)
+    for name, s in runs.items():
+        e, r = (s.replica(0) if name == "replicated" else s).get_rows("ent"), (s.replica(0) if name == "replicated" else s).get_rows("rel")
+        print(f"focuse {name} k={k}: ent within {np.mean(np.abs(e - st.ent) <= 1e-5 + 1e-3 * np.abs(st.ent)):.4f} max {np.abs(e - st.ent).max():.3e}"
+              f" rel within {np.mean(np.abs(r - st.rel) <= 1e-5 + 1e-3 * np.abs(st.rel)):.4f}")
+        assert np.mean(np.abs(e - st.ent) <= 1e-5 + 1e-3 * np.abs(st.ent)) > 0.99 and np.abs(e - st.ent).max() < 2.5e-2, name
+        assert np.mean(np.abs(r - st.rel) <= 1e-5 + 1e-3 * np.abs(st.rel)) > 0.99, name
+        s.close()
+
+
+@pytest.mark.parametrize("mode", ["replicated", "rows", "cols"])
+def test_session_group_refuses_a_bad_triple_and_carries_on(gpu_lib, mode):
+    """A triple whose entity id equals N, through every group entry: the step (and, for the row-sharded group, the rank call) raises
+    before any kernel is launched and the message names the triple's index -- the index within the replica's share where a replicated
+    group hands shares to its replicas.  Nothing of the refused step stays behind: the valid steps that follow match a fresh group fed
+    only those (two runs of the same code: equal losses up to the arrival order of the loss partials at the first step, of the fp32
+    row-adds after it)."""
+    from ampligraph_amd import _ffi
+    from ampligraph_amd.latent_features import loss_functions, optimizers, regularizers
+    from ampligraph_amd.session import SessionGroup
+
+    rng = np.random.default_rng(23)
+    model, k, N, R, B, eta, seed = "ComplEx", 16, 131, 4, 203, 3, 7
+    K = O.internal_k(model, k)
+    ent = (rng.normal(size=(N, K)) * 0.3).astype(np.float32)
+    rel = (rng.normal(size=(R, K)) * 0.3).astype(np.float32)
+    X = np.stack([rng.integers(0, N, 2 * B), rng.integers(0, R, 2 * B), rng.integers(0, N, 2 * B)], 1).astype(np.int32)
+    reg = regularizers.get("LP", {"p": 2, "lambda": 1e-3})
+    kw = {"replicated": {}, "rows": dict(rows=True, max_batch=B, global_negatives=True), "cols": dict(cols=True)}[mode]
+    W = 3 if mode == "replicated" else 2
+    mk = lambda: SessionGroup([0] * W, model, k, N, R, eta, loss_functions.get("self_adversarial"),   # noqa: E731
+                              optimizers.get("adam", {"learning_rate": 1e-2}), reg, seed=seed, **kw)
+    used, fresh = mk(), mk()
+    for g in (used, fresh):
+        g.set_rows("ent", ent)
+        g.set_rows("rel", rel)
+    i = B - 5                                        # in the LAST share: the replicas before it have been given theirs
+    lo = B * (W - 1) // W
+    bad = X[:B].copy()
+    bad[i, 2] = N
+    with pytest.raises(_ffi.AmdKgeError) as err:
+        used.train_step(bad)
+    assert f"triple {i - lo if mode == 'replicated' else i} has" in str(err.value), str(err.value)
+    if mode == "replicated":                         # in the first share the two numberings agree
+        bad0 = X[:B].copy()
+        bad0[3, 0] = N
+        with pytest.raises(_ffi.AmdKgeError) as err:
+            used.train_step(bad0)
+        assert "triple 3 has" in str(err.value), str(err.value)
+    if mode == "rows":
+        with pytest.raises(_ffi.AmdKgeError) as err:
+            used.rank(bad[i - 2:i + 3])
+        assert "session_group_rank: triple 2 has" in str(err.value), str(err.value)
+        assert np.array_equal(used.rank(X[:20]), fresh.rank(X[:20]))
+    for t in range(2):
+        xb = X[t * B:(t + 1) * B]
+        lu, lf = used.train_step(xb), fresh.train_step(xb)
+        print(f"after a refused step, {mode} step {t}: {lu!r} vs fresh {lf!r} rel {rel_gap(lu, lf):.3e}")
+        assert within(f"session/after_refused_step/{mode}/loss_step{t}", rel_gap(lu, lf), 1e-11 if t == 0 else 3e-6), (t, lu, lf)
+    eu, ef = (g.replica(0).get_rows("ent") if mode == "replicated" else g.get_rows("ent") for g in (used, fresh))
+    assert np.mean(np.abs(eu - ef) <= 1e-5 + 1e-3 * np.abs(ef)) > 0.99 and np.abs(eu - ef).max() < 2.5e-2
+    used.close()
+    fresh.close()
