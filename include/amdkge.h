@@ -20,6 +20,7 @@
  *     16-byte kernels (owner-computes train pair, pipelined MFMA rank kernel); amdkge_padded_k(k) returns the
  *     smallest such value, amdkge_pack_rows / amdkge_unpack_rows convert to and from the dense [rows, NC*k] form
  *     the reference's get_embeddings / checkpoints use.  k_pad == 0 means dense rows (k_pad = k).
+ *   - alignment: the kernels assume every device pointer on a 256-byte boundary (what hipMalloc and torch give; 16 bytes is what the float4 paths need); only the d_work of the rank / filter / corruption-score, relation-score, tiled-step, shard-route and filter-build calls and d_screen may start anywhere: the library aligns them up to 256 bytes itself (their *_workspace_bytes include that slack).
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  All compute entry
  *     points are asynchronous on that stream; the caller owns synchronisation.
  *   - return value: 0 = ok, negative = error class below; amdkge_last_error() gives a message
