@@ -164,6 +164,13 @@ SIGNATURES = {
     "amdkge_session_group_rank": (C.c_int, [P, P, I64, P, P, P, P, P, I64, I32, I32, P]),
 }
 
+# name -> (restype, argtypes): every symbol the extension headers declare (include/amdkge_lists.h: entry points added to ABI 5
+# without changing one of include/amdkge.h's)
+EXT_SIGNATURES = {
+    "amdkge_rank_lists_workspace_bytes": (I64, [C.POINTER(Model), I64]),
+    "amdkge_rank_lists": (C.c_int, [C.POINTER(Model), P, P, I64, P, I64, I32, P, P, P, I64, P, P, P, P, P, P, P, P]),
+}
+
 _lib = None
 
 
@@ -180,7 +187,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

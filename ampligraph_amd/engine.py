@@ -974,3 +974,25 @@ class KgeEngine:
         check(self.lib.amdkge_rank_compose(_ptr(counts), _ptr(sub), n, _ffi.RANK_STRATEGY[strategy], _ptr(out),
                                            int(out_stride), _stream()))
         return out, counts, sub
+
+    def rank_lists(self, triples, side, cand, strategy="worst", flt=None, out=None, out_stride=1, want_scores=False, lane=0):
+        """Ranks (1-based) of `triples` for one corruption side, each against ITS OWN candidate list (amdkge_rank_lists,
+        include/amdkge_lists.h): cand = (lo int64[n], hi int64[n], ids int32[*], max_len) -- triple i's candidates are the table
+        rows ids[lo[i]:hi[i]], every occurrence a candidate of its own, ids outside the table skipped; max_len bounds hi - lo (it
+        only plans the launch).  flt as in rank_side: None or (lo, hi, ids), the known positives ascending inside a range.  Returns
+        (ranks, counts, sub), and with want_scores a fourth: fp32 scores parallel to `ids` (-inf at a skipped id; positions no list
+        covers are not written)."""
+        n = int(triples.shape[0])
+        lo, hi, ids, max_len = cand
+        work = self._workspace(n, lane)
+        counts = torch.zeros(n, 2, dtype=torch.int32, device=self.device)
+        sub = f_lo = f_hi = f_ids = None
+        if flt is not None:
+            f_lo, f_hi, f_ids = flt
+            sub = torch.zeros(n, dtype=torch.int32, device=self.device)
+        scores = torch.empty(int(ids.shape[0]), dtype=torch.float32, device=self.device) if want_scores else None
+        check(self.lib.amdkge_rank_lists(C.byref(self.model), _ptr(self.ent), _ptr(self.rel), int(self.ent.shape[0]), _ptr(triples), n,
+                                         int(side), _ptr(lo), _ptr(hi), _ptr(ids), int(max_len), _ptr(f_lo), _ptr(f_hi), _ptr(f_ids),
+                                         _ptr(counts), _ptr(sub), _ptr(scores), _ptr(work), _stream()))
+        out = self.compose_ranks(counts, sub, strategy, out, out_stride)
+        return (out, counts, sub, scores) if want_scores else (out, counts, sub)

@@ -427,6 +427,57 @@ class ScoringBasedEmbeddingModel:
         fi = self._pair_filter_index(use_filter, Xi)
         return self._placement.rank_relations(Xi, fi, subset, ranking_strategy).cpu().numpy().reshape(-1, 1)
 
+    def evaluate_candidates(self, x, candidates_s=None, candidates_o=None, use_filter=False, ranking_strategy="worst", verbose=False):
+        """evaluate() against PER-TRIPLE candidate lists (the reference has none): int32 ranks (n, number of sides given), 1-based,
+        columns in the order s, o -- sampled negatives (ogbl-wikikg2's 500 heads and 500 tails per test triple), re-ranking the
+        output of a first stage, type-constrained evaluation.  They feed mrr_score / hits_at_n_score as they are.
+
+        candidates_s / candidates_o: the entities that replace the subject / the object, as a 2-D array [n, C] of entity labels or
+        a sequence of n 1-D label arrays (ragged; a list may be empty); at least one side must be given.  Row i of `x` is
+        ranked against list i alone, with entities_subset's semantics: the true triple's score is compared with its
+        candidates', whether or not its own entity is listed (listed, it competes with itself as in evaluate()).  Ties and filters
+        as in evaluate(): `ranking_strategy` worst / best / middle over the quantised scores; `use_filter` False, True (the
+        evaluated data filters itself) or a dict of datasets -- a candidate that is a KNOWN positive of the triple's (p, o) /
+        (s, p) is not a competitor.  On duplicate-free lists the rank is evaluate(x[i:i+1], entities_subset=list_i, ...)'s.
+        DUPLICATES: every occurrence of an entity in a list is a candidate of its own, so a repeated entity is counted each
+        time (the reference's subset is a set), and a repeated known positive is likewise filtered each time.
+
+        Lists and rows must stay aligned, so nothing is dropped silently: an unknown candidate label, or a row of `x` with an
+        unseen label, raises ValueError.  One gather of the listed rows per side (amdkge_rank_lists): the cost is the
+        candidates', not the entity table's.  Needs the whole table on one GPU: row- / column-sharded models raise
+        NotImplementedError."""
+        from ..evaluation.candidates import csr_of, list_lengths
+
+        if ranking_strategy not in ("best", "middle", "worst"):
+            raise ValueError("`ranking_strategy` must be 'worst', 'best' or 'middle', got {!r}.".format(ranking_strategy))
+        if not self.is_fitted:
+            raise ValueError("Model is not fitted.")
+        if use_filter is None:
+            use_filter = False
+        if not isinstance(use_filter, (bool, dict)):
+            raise ValueError("`use_filter` must be False, True or a dict of datasets.")
+        given = [(sd, c) for sd, c in (("s", candidates_s), ("o", candidates_o)) if c is not None]
+        if not given:
+            raise ValueError("evaluate_candidates needs `candidates_s`, `candidates_o` or both.")
+        X = _load_triples(x)
+        Xi = self._index_test(X)
+        if Xi.shape[0] != X.shape[0]:
+            raise ValueError("{} of the {} rows of `x` have unseen labels: candidate lists and rows must stay aligned, remove "
+                             "them (and their lists) first.".format(X.shape[0] - Xi.shape[0], X.shape[0]))
+        n = Xi.shape[0]
+        sides = []
+        for sd, c in given:
+            lens, labels = list_lengths(c if isinstance(c, np.ndarray) else list(c), n)
+            ids = np.asarray(self.data_indexer.get_indexes(labels, "e")) if labels.shape[0] else np.zeros(0, dtype=np.int32)
+            if ids.shape[0] != labels.shape[0]:
+                raise ValueError("candidates_{}: {} of the {} candidate labels are unknown to the model.".format(
+                    sd, labels.shape[0] - ids.shape[0], labels.shape[0]))
+            sides.append((sd, csr_of(lens, ids)))
+        if n == 0:
+            return np.zeros((0, len(sides)), dtype=np.int32)
+        fi = self._filter_index(use_filter, Xi)
+        return self._placement.rank_candidates(Xi, sides, fi, ranking_strategy).cpu().numpy()
+
     # ------------------------------------------------------------------------------------ accessors
     def is_fit(self):
         return self.is_fitted

@@ -20,6 +20,10 @@ from .sharded import RowExchange, ShardedStepLoop, ShardSpec, sharded_rank_count
 from .trainer import StepLoop, shard_bounds
 
 
+_LISTS_NEED_WHOLE_TABLE = ("evaluate_candidates gathers each triple's candidate rows from the whole entity table on one GPU: row- and "
+                           "column-sharded tables (entity_sharding) are out of its scope; evaluate(entities_subset=...) works there")
+
+
 def shard_file(filepath, rank, world):
     return "{}.shard{:03d}-of-{:03d}.npz".format(filepath, rank, world)
 
@@ -135,6 +139,50 @@ class Replicated:
                 flt = fi.device_filter(eng, xs, sd) if fi is not None else None   # range lookup on the device
                 jobs.append((_ffi.SIDE_S if sd == "s" else _ffi.SIDE_O, flt, ranks[c0:c0 + CH, col], len(sides)))
             eng.rank_sides(xs, jobs, strategy, ent_ids, subset_pos)   # the sides run beside each other
+        return ranks
+
+    # ---- ranks against per-triple candidate lists (evaluate_candidates)
+    LIST_CHUNK_BYTES = 256 << 20   # bound of the candidate ids of one side that are on the device at a time
+
+    def rank_candidates(self, Xi, sides_with_lists, fi, strategy):
+        """int32 device ranks (n, len(sides_with_lists)) of the test triples Xi (global ids), each against its own candidates:
+        sides_with_lists = [(side "s" | "o", (offsets int64 [n + 1], ids int32, max_len)), ...] (evaluation.candidates.as_csr, host
+        arrays of global ids); fi: FilterIndex or None.  Several ranks share the triples exactly as rank() does."""
+        d, n = self.dist, Xi.shape[0]
+        if d is None or n < d.get_world_size():
+            return self._rank_candidates(Xi, sides_with_lists, fi, strategy, 0, n)
+        W = d.get_world_size()
+        bounds = [shard_bounds(n, W, q) for q in range(W)]
+        lo, hi = bounds[d.get_rank()]
+        buf = torch.zeros(-(-n // W), len(sides_with_lists), dtype=torch.int32, device=self.engine.device)
+        buf[:hi - lo] = self._rank_candidates(Xi, sides_with_lists, fi, strategy, lo, hi)
+        parts = [torch.empty_like(buf) for _ in range(W)]
+        d.all_gather(parts, buf)
+        return torch.cat([p[:b - a] for p, (a, b) in zip(parts, bounds)])
+
+    def _rank_candidates(self, Xi, sides_with_lists, fi, strategy, a, b):
+        """rank_candidates for the triples [a, b): chunks of at most 65 536 queries (as _rank) whose id lists stay under
+        LIST_CHUNK_BYTES per side (a single longer list is a chunk of its own)."""
+        eng = self.engine
+        dev = eng.device
+        Xd = torch.as_tensor(Xi[a:b]).to(dev)
+        ranks = torch.empty(b - a, len(sides_with_lists), dtype=torch.int32, device=dev)
+        CH, cap = 1 << 16, self.LIST_CHUNK_BYTES // 4
+        c0 = a
+        while c0 < b:
+            c1 = min(b, c0 + CH)
+            for _, (off, _, _) in sides_with_lists:
+                c1 = min(c1, max(c0 + 1, int(np.searchsorted(off, off[c0] + cap, side="right")) - 1))
+            xs = Xd[c0 - a:c1 - a]
+            for col, (sd, (off, ids, _)) in enumerate(sides_with_lists):
+                rel_off = off[c0:c1 + 1] - off[c0]
+                lens = np.diff(rel_off)
+                cand = (torch.as_tensor(rel_off[:-1].copy()).to(dev), torch.as_tensor(rel_off[1:].copy()).to(dev),
+                        torch.as_tensor(ids[off[c0]:off[c1]]).to(dev), int(lens.max()) if lens.size else 0)
+                flt = fi.device_filter(eng, xs, sd) if fi is not None else None   # range lookup on the device
+                eng.rank_lists(xs, _ffi.SIDE_S if sd == "s" else _ffi.SIDE_O, cand, strategy, flt,
+                               out=ranks[c0 - a:c1 - a, col], out_stride=len(sides_with_lists))
+            c0 = c1
         return ranks
 
     # ---- relation prediction: the relation table is whole in every placement, so every rank computes every query
@@ -317,6 +365,9 @@ class Rows(Replicated):
                 eng.compose_ranks(counts, sub, strategy, out=ranks[c0:c0 + CH, col], out_stride=len(sides))
         return ranks
 
+    def rank_candidates(self, Xi, sides_with_lists, fi, strategy):
+        raise NotImplementedError(_LISTS_NEED_WHOLE_TABLE)
+
     def save(self, filepath, loop):
         """Rank r writes ITS rows of the entity table and of the optimizer slots to <filepath>.shardRRR-of-WWW.npz; rank 0
         gets the replicated part (relation table + slots, `shard_world`).  Nothing is gathered, so it works at C5 scale."""
@@ -400,3 +451,6 @@ class Columns(Replicated):
         # callbacks (publish() is a collective); callback-free fits skip the host round trip.
         if self.callbacks_anywhere:
             self.publish()
+
+    def rank_candidates(self, Xi, sides_with_lists, fi, strategy):
+        raise NotImplementedError(_LISTS_NEED_WHOLE_TABLE)

@@ -745,4 +745,5 @@ int amdkge_session_group_rank(amdkge_session_group* g, const int32_t* triples, i
 #ifdef __cplusplus
 }
 #endif
+#include "amdkge_lists.h"
 #endif /* AMDKGE_H */
