@@ -57,6 +57,7 @@ __global__ __launch_bounds__(GW * 64) void tile_direct_kernel(TileArgs a) {
     const int tile = blockIdx.x;
     if (tile >= a.n_tiles) {   // relation table: ordinary dense sweep (its gradient was completed by the forward kernel's atomics)
         const int64_t first = (int64_t)(tile - a.n_tiles) * THREADS + tid, stride = (int64_t)a.rel_blocks * THREADS;
+        if (tile == a.n_tiles && wg == 0) fold_loss_parts(a.loss_parts, a.loss_sum, lane);   // the forward kernel's loss partials (see tile_backward_kernel)
         float racc;
 #define KGE_REL_SWEEP(KIND) racc = opt_sweep<KIND>(a.rel_opt, first, stride)
         KGE_OPT_DISPATCH(a.rel_opt.kind, KGE_REL_SWEEP)
@@ -69,12 +70,7 @@ __global__ __launch_bounds__(GW * 64) void tile_direct_kernel(TileArgs a) {
     }
     const int cnt = min(a.counters[tile * 32], a.cap);
     const int on = min(a.counters[a.n_tiles * 32], a.ovf_cap);
-    if (tid == 0)   // the forward kernel's loss partials: folded by the first LOSS_PARTS tiles (see tile_backward_kernel)
-        for (int sl = tile; sl < LOSS_PARTS; sl += a.n_tiles) {
-            const unsigned long long old = atomicExch(reinterpret_cast<unsigned long long*>(a.loss_parts + (size_t)sl * LOSS_PART_STRIDE), 0ull);
-            const double v = __longlong_as_double((long long)old);
-            if (v != 0.0) atomicAdd(a.loss_sum, v);
-        }
+    const bool reg_fold = a.apply_update && a.reg_loss && a.opt.lam != 0.f;   // (the regulariser's partials: folded by the last tile to FINISH)
     const uint32_t NT = (uint32_t)a.n_tiles, RB = (uint32_t)a.rb;
     const int nrow = a.tile_rows;
     auto row_of = [&](int r) KGE_TILE_INLINE -> int64_t { return row_of_tile((uint32_t)tile, (uint32_t)r, NT, RB); };
@@ -90,7 +86,15 @@ __global__ __launch_bounds__(GW * 64) void tile_direct_kernel(TileArgs a) {
     if (tid == 0) { s_total = cnt; s_nact = 0; }
     for (int r = tid; r <= nrow; r += THREADS) { rstart[r] = 0; rfill[r] = 0; }
     for (int i = tid; i < cnt; i += THREADS) ents[i] = reinterpret_cast<const uint4*>(list)[i];
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"(cnt), "v"(on) : "memory");   // (every wave HOLDS cnt and on at the barrier: a barrier alone does not wait for loads; a hardware-ordering argument, see tile_backward_kernel)
     __syncthreads();
+    // bookkeeping up front, as in tile_backward_kernel: no wave reads a counter again, so the bucket fill is zeroed and the tile's
+    // ticket ("this tile has read the overflow count") drawn here; the ticket is looked at behind the rows
+    int ticket = -1;
+    if (!reg_fold && tid == 0) {
+        a.counters[tile * 32] = 0;
+        ticket = atomicAdd(a.counters + (size_t)(a.n_tiles + 1) * 32, 1);
+    }
     // Entries of buckets that were full (the shared overflow list): this tile's share joins the LDS list.  Should it not fit
     // (a pathologically hot tile: thousands of positives on one row without the hot-row replicas) the list keeps the bucket
     // only and every row also scans the overflow list in memory (ovf_slow below): slow, but complete.
@@ -313,7 +317,26 @@ __global__ __launch_bounds__(GW * 64) void tile_direct_kernel(TileArgs a) {
         const float w = wave_sum(reg_acc);
         if (lane == 0) atomicAdd(a.loss_parts + (size_t)((tile * GW + wg) & (LOSS_PARTS - 1)) * LOSS_PART_STRIDE + 1, (double)a.opt.lam * (double)w);
     }
+    // no sweep workgroup in this launch: the loss partials are folded by the first LOSS_PARTS tiles, behind their rows
+    if (a.rel_blocks == 0 && tid == 0)
+        for (int sl = tile; sl < LOSS_PARTS; sl += a.n_tiles) {
+            const unsigned long long old = atomicExch(reinterpret_cast<unsigned long long*>(a.loss_parts + (size_t)sl * LOSS_PART_STRIDE), 0ull);
+            const double v = __longlong_as_double((long long)old);
+            if (v != 0.0) atomicAdd(a.loss_sum, v);
+        }
     // ---- 3. bookkeeping left zeroed for the next step (as tile_backward_kernel) -----------------------------------------
+    if (!reg_fold) {
+        if (a.touched) {   // the rows' marks are read while the rows are visited: every wave is through with them behind this barrier
+            __syncthreads();
+            for (int r = tid; r < nrow; r += THREADS)
+                if (row_of(r) < a.n_rows) a.touched[row_of(r)] = 0;
+        }
+        if (tid == 0 && ticket == a.n_tiles - 1) {   // the last ticket: every tile has read the overflow count
+            a.counters[a.n_tiles * 32] = 0;
+            a.counters[(a.n_tiles + 1) * 32] = 0;
+        }
+        return;
+    }
     __syncthreads();
     if (a.touched)
         for (int r = tid; r < nrow; r += THREADS)
@@ -329,7 +352,7 @@ __global__ __launch_bounds__(GW * 64) void tile_direct_kernel(TileArgs a) {
         }
     }
     __syncthreads();
-    if (s_last && wg == 0 && a.apply_update && a.reg_loss && a.opt.lam != 0.f) fold_loss_parts(a.loss_parts, a.reg_loss, lane, 1);
+    if (s_last && wg == 0) fold_loss_parts(a.loss_parts, a.reg_loss, lane, 1);
 }
 
 template <int MODEL>

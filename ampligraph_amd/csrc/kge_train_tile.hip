@@ -25,6 +25,9 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_backward_kernel(TileArgs a)
     if (tile >= a.n_tiles) {
         // relation table: ordinary dense sweep (its gradient was completed by the forward kernel's atomics)
         const int64_t first = (int64_t)(tile - a.n_tiles) * TILE_THREADS + tid, stride = (int64_t)a.rel_blocks * TILE_THREADS;
+        // The forward kernel's per-block loss partials (complete: it finished before this launch started) are folded into the
+        // caller's accumulator here, by one wave of the first sweep workgroup: no tile waits for the exchange.
+        if (tile == a.n_tiles && wv == 0) fold_loss_parts(a.loss_parts, a.loss_sum, lane);
         float racc;
 #define KGE_REL_SWEEP(KIND) racc = opt_sweep<KIND>(a.rel_opt, first, stride)
         KGE_OPT_DISPATCH(a.rel_opt.kind, KGE_REL_SWEEP)
@@ -35,25 +38,18 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_backward_kernel(TileArgs a)
         }
         return;
     }
-    // bucket fill + overflow count are read by every wave up front: the counters are reset behind the
-    // workgroup barrier at the end of the kernel (the library keeps them zero between steps)
+    // bucket fill + overflow count are read by every wave up front; the library keeps the counters zero between steps (see the
+    // ticket below the accumulator zeroing, and the end of the kernel)
     const int cnt = KGE_DBG(a, 4096) ? 0 : min(a.counters[tile * 32], a.cap);
     const int on = KGE_DBG(a, 4096) ? 0 : min(a.counters[a.n_tiles * 32], a.ovf_cap);
+    // the entity regulariser's partials are folded by the last tile to FINISH: only then does the bookkeeping wait for the end
+    const bool reg_fold = a.apply_update && a.reg_loss && a.opt.lam != 0.f;
     // BLOCK-INTERLEAVED ownership: the table is cut into blocks of TILE_RB consecutive rows and block b belongs to tile
     // b % n_tiles (local row r <-> table row row_of_tile(tile, r)).  Real graphs number their hubs first (ids are handed out
     // first-seen), so contiguous row ranges give the first tiles several times the entries of the others and the tile pass is
     // as slow as its busiest tile (zipf graph); dealing the blocks round the tiles spreads every popularity class.  Blocks
     // rather than single rows keep the optimizer's streams (x, m, v of a tile) in runs of TILE_RB rows: with single rows a
     // large table (C4: 123 k rows) lost 12 % to page locality.  Rows beyond the table in a tile's last block are skipped.
-    // The forward kernel's per-block loss partials (complete: it finished before this launch started) are folded into the
-    // caller's accumulator by the first LOSS_PARTS tiles, one slot each, while they start up.  A fold by the LAST tile -- a
-    // returning exchange, a butterfly and an add behind everyone else's work -- sat on the critical path of every step.
-    if (tid == 0)
-        for (int sl = tile; sl < LOSS_PARTS; sl += a.n_tiles) {
-            const unsigned long long old = atomicExch(reinterpret_cast<unsigned long long*>(a.loss_parts + (size_t)sl * LOSS_PART_STRIDE), 0ull);
-            const double v = __longlong_as_double((long long)old);
-            if (v != 0.0) atomicAdd(a.loss_sum, v);
-        }
     const uint32_t NT = (uint32_t)a.n_tiles;
     const int nrow = a.tile_rows;
     const uint32_t RB = (uint32_t)a.rb;
@@ -64,7 +60,7 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_backward_kernel(TileArgs a)
     // Long rows (gw > 1): a GROUP of gw waves owns the row and each wave covers its 64-quad slice, so that the few entries
     // of a tile with few, long rows (C5: 18 rows of 8 KB) are spread over all lanes instead of over at most 16 owners.
     const int gw = a.gw, grp = wv / gw, wg = wv % gw, G = TILE_WAVES / gw;
-    // an owner zeroes the rows it owns: no workgroup barrier is needed anywhere in this kernel
+    // an owner zeroes the rows it owns: the accumulators need no workgroup barrier anywhere in this kernel
     bool qok[CH];
     int qoff[CH];
 #pragma unroll
@@ -96,6 +92,32 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_backward_kernel(TileArgs a)
     if (a.lazy)
         for (int r = grp + G * lane; r < nrow; r += G * 64)
             tflag[r * gw + wg] = (a.touched && row_ok(r) && a.touched[row_of(r)]) ? 1 : 0;
+
+    // ---- bookkeeping, up front: own bucket fill zeroed and the tile's ticket taken as soon as every wave HOLDS cnt and on ----
+    // Behind the barrier below no wave of this tile reads a counter again, so the bucket fill can be zeroed at once, and a
+    // ticket drawn now says "this tile has read the overflow count".  The holder of the last ticket therefore knows that every
+    // tile of the launch -- of every round, when there are more tiles than CUs: a tile draws its ticket when it starts -- has
+    // read the overflow count, and zeroes it together with the ticket word.  It looks at its ticket only after the flush: the
+    // atomic's round trip is covered by the tile's work, and the end of a tile is no fence, no returning atomic and no barrier.
+    // (The wait on cnt / on is explicit -- s_waitcnt with the two values as operands: a barrier alone does not wait for the loads of
+    // the waves that meet at it.  That the last holder's plain store of 0 comes behind every other tile's LOAD of the overflow
+    // count is a hardware-ordering argument, not one of the language's memory model: every wave's load has returned before its
+    // barrier, the relaxed ticket atomic is issued behind that barrier, and the store behind the ticket's return.)
+    // Nothing here is host state: a captured graph replays it as it is.
+    int ticket = -1;
+    if (!reg_fold) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::"v"(cnt), "v"(on) : "memory");
+        __syncthreads();
+        if (tid == 0) {
+            a.counters[tile * 32] = 0;
+            ticket = atomicAdd(a.counters + (size_t)(a.n_tiles + 1) * 32, 1);
+        }
+        // the forward kernel's touched-rows marks: every wave copied its flags to LDS before the barrier (a wave's store of a
+        // flag has the loaded mark in hand), so they are cleared for the next step here instead of behind a barrier at the end
+        if (a.touched)
+            for (int r = tid; r < nrow; r += TILE_THREADS)
+                if (row_ok(r)) a.touched[row_of(r)] = 0;
+    }
 
     // Operand loads of one staged entry (all arguments wave-uniform): the staged side row and, for TransE / RotatE
     // corruption entries, the relation row (RotatE: its cos / sin from the per-step table) and the tile's own live row.
@@ -691,9 +713,28 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_backward_kernel(TileArgs a)
         const float w = wave_sum(reg_acc);
         if (lane == 0) atomicAdd(a.loss_parts + (size_t)((tile * TILE_WAVES + wv) & (LOSS_PARTS - 1)) * LOSS_PART_STRIDE + 1, (double)a.opt.lam * (double)w);
     }
-    // ---- leave the bookkeeping zeroed for the next step: own bucket now, overflow count by the last tile ----
+    // no sweep workgroup in this launch (TransE, touched-rows mode, gradient-only steps): the loss partials are folded by the
+    // first LOSS_PARTS tiles, one slot each (tiny launches: several), by their LAST wave once its rows are flushed -- the wave
+    // with the fewest rows when the tile's rows do not divide evenly.  (In front of the bucket walk, as it was, the exchange
+    // and the add were two dependent round trips added to one wave of 64 tiles.)
+    if (a.rel_blocks == 0 && tid == TILE_THREADS - 64)
+        for (int sl = tile; sl < LOSS_PARTS; sl += a.n_tiles) {
+            const unsigned long long old = atomicExch(reinterpret_cast<unsigned long long*>(a.loss_parts + (size_t)sl * LOSS_PART_STRIDE), 0ull);
+            const double v = __longlong_as_double((long long)old);
+            if (v != 0.0) atomicAdd(a.loss_sum, v);
+        }
+    // ---- leave the bookkeeping zeroed for the next step ----
+    if (!reg_fold) {
+        // (own bucket fill and the touched-rows marks: cleared up front.)  The last ticket: every tile has read the overflow count
+        if (tid == 0 && ticket == a.n_tiles - 1) {
+            a.counters[a.n_tiles * 32] = 0;
+            a.counters[(a.n_tiles + 1) * 32] = 0;
+        }
+        return;
+    }
+    // entity regulariser: its partials must be complete before they are folded, so the ticket is drawn at the END of a tile here
     __syncthreads();
-    if (a.touched)   // every wave has read its flags: clear the forward kernel's marks for the next step
+    if (a.touched)
         for (int r = tid; r < nrow; r += TILE_THREADS)
             if (row_ok(r)) a.touched[row_of(r)] = 0;
     if (tid == 0) {
@@ -707,9 +748,8 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_backward_kernel(TileArgs a)
         }
     }
     __syncthreads();
-    // the regulariser partials (added by every tile's waves before the ticket) are folded by the last tile to finish; the data
-    // loss was folded when the kernel started (below the fill counts)
-    if (s_last && wv == 0 && a.apply_update && a.reg_loss && a.opt.lam != 0.f) fold_loss_parts(a.loss_parts, a.reg_loss, lane, 1);
+    // the regulariser partials (added by every tile's waves before the ticket) are folded by the last tile to finish
+    if (s_last && wv == 0) fold_loss_parts(a.loss_parts, a.reg_loss, lane, 1);
 }
 
 template <int MODEL, int CH, int UNROLL, bool DET = false>

@@ -58,9 +58,9 @@ struct TileArgs {
     const float* stage_rows;  // [B][4][K]
     const StageEntry* lists;  // [n_tiles][cap]
     const StageEntry* ovf;    // overflow entries
-    int* counters;            // [(n_tiles + 2) * 32]: bucket fills, overflow count, finished-tiles ticket
+    int* counters;            // [(n_tiles + 2) * 32]: bucket fills, overflow count, tile ticket (all zero between steps)
     int* status_flag;         // det-sort overflow flag: at a workspace offset that does not depend on the plan (sticky until queried)
-    double* loss_parts;       // the forward kernel's per-block loss partials, folded into loss_sum by the last tile
+    double* loss_parts;       // the forward kernel's per-block loss partials, folded into loss_sum by the first sweep workgroup (without one: by the first LOSS_PARTS tiles)
     double* loss_sum;
     double* reg_loss;
     OptArgs rel_opt;          // fused relation-table sweep (rel_blocks > 0): blocks [n_tiles, n_tiles + rel_blocks)
