@@ -16,8 +16,9 @@
 // half), so a positive is handled by a GROUP of G = 16 / 32 / 64 lanes (one quad of each half per lane), four / two / one positives
 // per wave -- a whole wave per 13-quad row would idle 80 % of its lanes.  The slice table (C2 at W = 8: 14 505 x 416 B = 6 MB) is
 // L2-resident on every XCD, which is where the design gets its speed from (scripts/xcd_slice_bench.hip: 15.1 TB/s of gathers).
-// Shares TrainArgs / StageEntry / tile_of_row with the forward kernel (kge_train_common.h); kge_train_tiled.hip launches C through
-// run_cols_stage (kge_train_tiled.h), A and B have their own entry points below.
+// Shared with the forward kernel: TrainArgs and the writers of the staging protocol -- stage_draws, stage_side_rows, stage_append
+// (kge_train_common.h) --, and Loss.__call__ itself (loss_call, kge_loss.h; B walks it with one thread per positive).
+// kge_train_tiled.hip launches C through run_cols_stage (kge_train_tiled.h), A and B have their own entry points below.
 #include "kge_train_tiled.h"
 
 namespace kge {
@@ -58,25 +59,6 @@ __device__ __forceinline__ void cols_load_spo(const TrainArgs& a, int ps, int pp
     for (int u = 0; u < 4; ++u) prep_rel<MODEL>(a.mc, p[u]);
 }
 
-// the corruption draws of one positive into the group's LDS arrays (CorruptionGenerationLayerTrain.py:35-94; the same Philox rows
-// as one GPU: keyed by the global corruption row)
-template <int G>
-__device__ __forceinline__ void cols_draws(const TrainArgs& a, int64_t i, int ps, int gl, int* sh_keep, int* sh_repl) {
-    for (int j = gl; j < a.eta; j += G) {
-        int keep, repl;
-        if (a.neg_override) {
-            const int64_t r = (int64_t)j * a.B + i;
-            const int ns = a.neg_override[3 * r + 0], no = a.neg_override[3 * r + 2];
-            keep = (ns == ps) ? 1 : 0;
-            repl = keep ? no : ns;
-        } else {
-            draw_corruption(a.sc, i, j, keep, repl);
-        }
-        sh_keep[j] = keep;
-        sh_repl[j] = repl;
-    }
-}
-
 // ---- A: partial scores ---------------------------------------------------------------------------------------------------------
 template <int MODEL, int G>
 __global__ __launch_bounds__(256) void cols_scores_kernel(ColsArgs ca) {
@@ -91,7 +73,7 @@ __global__ __launch_bounds__(256) void cols_scores_kernel(ColsArgs ca) {
     int* sh_keep = reinterpret_cast<int*>(smem) + (size_t)grp * 2 * a.eta;
     int* sh_repl = sh_keep + a.eta;
     const int ps = a.triples[3 * i + 0], pp = a.triples[3 * i + 1], po = a.triples[3 * i + 2];
-    cols_draws<G>(a, i, ps, gl, sh_keep, sh_repl);
+    stage_draws(a, i, ps, gl, G, sh_keep, sh_repl);
     const bool qok = gl < a.nq;
     const int qoff = (qok ? gl : 0) * 4;
     float s[4][NC], p[4][NC], o[4][NC];
@@ -131,92 +113,19 @@ __global__ __launch_bounds__(256) void cols_scores_kernel(ColsArgs ca) {
 
 // ---- B: loss on the complete scores ----------------------------------------------------------------------------------------------
 // One THREAD per positive: its 1 + eta scores sit B floats apart (layout j * B + i), so the lanes of a wave read and write
-// consecutive floats, and every lane evaluates a whole Loss.__call__ (loss_functions.py:285-308,359-382,441-464,539-574,629-654; the
-// arithmetic of loss_and_dscore, kge_train_kernel.h, with the sums taken serially) -- the first version gave a positive a whole wave
+// consecutive floats, and every lane evaluates a whole Loss.__call__ (loss_call over SerialWalk, kge_loss.h: the forward kernel's
+// operations with the sums taken serially) -- the first version gave a positive a whole wave
 // and used 21 of its 64 lanes: 82 us at B = 80 000, eta = 20 (profiles/r05c_cols8_kernel_stats.csv) for 6.7 MB of data.
 // scores <- dL/dscore in place; the loss value into ONE atomic per block.
 __global__ __launch_bounds__(256) void cols_loss_kernel(float* __restrict__ scores, int64_t B, int eta, amdkge_loss L, float sgn_scale, double* loss_sum) {
     __shared__ double s_loss[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float* neg = scores + B;
-    const float feta = (float)eta;
     double tot = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < B; i += (int64_t)gridDim.x * 256) {
         const float P = sgn_scale * scores[i];   // the reference's rounding: reduce_sum, then negate (TransE / RotatE) or scale (HolE)
-        float* nj = neg + i;                      // corruption j at nj[j * B]
-        float red = L.reduction_mean ? feta : 1.f, per, dP;
-        switch (L.kind) {
-            case AMDKGE_LOSS_PAIRWISE: {
-                float acc = 0.f, cnt = 0.f;
-                for (int j = 0; j < eta; ++j) {
-                    const float h = L.margin - P + sgn_scale * nj[(int64_t)j * B];
-                    const bool act = h >= 0.f;
-                    acc += hinge_nan(h);
-                    cnt += act ? 1.f : 0.f;
-                    nj[(int64_t)j * B] = act ? 1.f / red : masked_zero(h);
-                }
-                per = acc / red;
-                dP = -cnt / red;
-            } break;
-            case AMDKGE_LOSS_NLL: {
-                if (L.reduction_mean) red = 2.f * feta;
-                const bool inP = (P >= -75.f) && (P <= 75.f);
-                const float Pc = clip_exp(P);
-                float acc = 0.f;
-                for (int j = 0; j < eta; ++j) {
-                    const float n = sgn_scale * nj[(int64_t)j * B];
-                    const bool in = (n >= -75.f) && (n <= 75.f);
-                    const float nc = clip_exp(n);
-                    acc += logf(1.f + expf(nc));
-                    nj[(int64_t)j * B] = in ? sigmoidf(nc) / red : masked_zero(n);
-                }
-                per = (feta * logf(1.f + expf(-Pc)) + acc) / red;
-                dP = inP ? -feta * sigmoidf(-Pc) / red : 0.f;
-            } break;
-            case AMDKGE_LOSS_ABSOLUTE_MARGIN: {
-                float acc = 0.f;
-                for (int j = 0; j < eta; ++j) {
-                    const float h = L.margin + sgn_scale * nj[(int64_t)j * B];
-                    acc += hinge_nan(h);
-                    nj[(int64_t)j * B] = (h >= 0.f) ? 1.f / red : masked_zero(h);
-                }
-                per = (acc - feta * P) / red;
-                dP = -feta / red;
-            } break;
-            case AMDKGE_LOSS_SELF_ADVERSARIAL: {
-                float mx = -INFINITY;
-                for (int j = 0; j < eta; ++j) mx = fmaxf(mx, L.alpha * (sgn_scale * nj[(int64_t)j * B]));
-                float se = 0.f;
-                for (int j = 0; j < eta; ++j) se += expf(L.alpha * (sgn_scale * nj[(int64_t)j * B]) - mx);
-                float lbar = 0.f;
-                for (int j = 0; j < eta; ++j) {
-                    const float n = sgn_scale * nj[(int64_t)j * B];
-                    lbar += expf(L.alpha * n - mx) / se * log_sigmoid(-n - L.margin);
-                }
-                for (int j = 0; j < eta; ++j) {
-                    const float n = sgn_scale * nj[(int64_t)j * B];
-                    const float w = expf(L.alpha * n - mx) / se;
-                    const float ell = log_sigmoid(-n - L.margin);
-                    nj[(int64_t)j * B] = computed_zero((w * sigmoidf(n + L.margin) - L.alpha * w * (ell - lbar)) / red, n);
-                }
-                per = -log_sigmoid(L.margin + P) - lbar / red;
-                dP = -sigmoidf(-(L.margin + P));
-            } break;
-            default: {   // AMDKGE_LOSS_MULTICLASS_NLL
-                const bool inP = (P >= -75.f) && (P <= 75.f);
-                const float eP = expf(clip_exp(P));
-                float acc = 0.f;
-                for (int j = 0; j < eta; ++j) acc += expf(clip_exp(sgn_scale * nj[(int64_t)j * B]));
-                const float Z = acc / red + eP;
-                for (int j = 0; j < eta; ++j) {
-                    const float n = sgn_scale * nj[(int64_t)j * B];
-                    const bool in = (n >= -75.f) && (n <= 75.f);
-                    nj[(int64_t)j * B] = in ? expf(clip_exp(n)) / Z / red : masked_zero(n);
-                }
-                per = -logf(eP / Z);
-                dP = inP ? -1.f + eP / Z : 0.f;
-            } break;
-        }
+        float per, dP;
+        loss_call(L, P, eta, SerialWalk{neg + i, B, sgn_scale}, per, dP);
         scores[i] = dP;
         tot += (double)per;
     }
@@ -236,7 +145,6 @@ __global__ __launch_bounds__(256) void cols_stage_kernel(ColsArgs ca) {
     const TrainArgs& a = ca.t;
     constexpr int NC = ModelTraits<MODEL>::NC;
     constexpr int GPB = 256 / G;
-    constexpr bool TRILINEAR = (MODEL == AMDKGE_DISTMULT || MODEL == AMDKGE_COMPLEX);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, grp = tid / G, gl = tid % G, lane = tid & 63;
     const int eta = a.eta;
@@ -248,7 +156,7 @@ __global__ __launch_bounds__(256) void cols_stage_kernel(ColsArgs ca) {
     float* sh_row = reinterpret_cast<float*>(smem + (size_t)GPB * 2 * eta * 4) + (size_t)grp * a.K;   // the group's relation-gradient row, transposed
     int* sh_rel = reinterpret_cast<int*>(smem + (size_t)GPB * 2 * eta * 4 + (size_t)GPB * a.K * 4);     // [GPB] relation id (-1: inactive)
     const int ps = a.triples[3 * i + 0], pp = a.triples[3 * i + 1], po = a.triples[3 * i + 2];
-    cols_draws<G>(a, i, ps, gl, sh_keep, sh_repl);
+    stage_draws(a, i, ps, gl, G, sh_keep, sh_repl);
     if (gl == 0) sh_rel[grp] = active ? pp : -1;
     const bool qok = gl < a.nq;
     const int qoff = (qok ? gl : 0) * 4;
@@ -258,33 +166,9 @@ __global__ __launch_bounds__(256) void cols_stage_kernel(ColsArgs ca) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) pad1[u] = (MODEL == AMDKGE_ROTATE && qoff + u >= a.k_live) ? 1.f : 0.f;
     const float sgn_scale = a.mc.score_sign * a.mc.score_scale;
-    // side rows for the owner kernel: the staging protocol of train_fwdbwd_kernel<STAGE> (kge_train_kernel.h)
-    if (active && qok) {
-        float va[NC][4], vb[NC][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if constexpr (TRILINEAR) {
-                float ds[NC], dp[NC], dd[NC];
-                grad_unit<MODEL>(s[u], p[u], o[u], 1.f, ds, dp, dd);
-#pragma unroll
-                for (int h = 0; h < NC; ++h) { va[h][u] = dd[h]; vb[h][u] = ds[h]; }
-            } else if constexpr (MODEL == AMDKGE_ROTATE) {
-                const float cs = p[u][0], sn = p[u][1];   // A = s o r, B = o o conj(r)
-                va[0][u] = s[u][0] * cs - s[u][1] * sn; va[1][u] = s[u][0] * sn + s[u][1] * cs;
-                vb[0][u] = o[u][0] * cs + o[u][1] * sn; vb[1][u] = o[u][1] * cs - o[u][0] * sn;
-            } else {
-#pragma unroll
-                for (int h = 0; h < NC; ++h) { va[h][u] = s[u][h]; vb[h][u] = o[u][h]; }
-            }
-        }
-        float* qa = a.stage_rows + ((int64_t)i * a.ns + 2) * a.K + qoff;
-        float* qb = a.stage_rows + ((int64_t)i * a.ns + 3) * a.K + qoff;
-#pragma unroll
-        for (int h = 0; h < NC; ++h) {
-            *reinterpret_cast<float4*>(qa + h * a.k) = make_float4(va[h][0], va[h][1], va[h][2], va[h][3]);
-            *reinterpret_cast<float4*>(qb + h * a.k) = make_float4(vb[h][0], vb[h][1], vb[h][2], vb[h][3]);
-        }
-    }
+    // side rows A, B for the owner kernel
+    if (active && qok)
+        stage_side_rows<MODEL>(s, p, o, a.stage_rows + ((int64_t)i * a.ns + 2) * a.K + qoff, a.stage_rows + ((int64_t)i * a.ns + 3) * a.K + qoff, a.k);
     wave_lds_sync();
     // ---- gradients of the positive's own rows: the positive, then every corruption, coefficients as given ----
     const float* cneg = ca.scores + a.B;
@@ -337,16 +221,7 @@ __global__ __launch_bounds__(256) void cols_stage_kernel(ColsArgs ca) {
             if (j < eta) { dest = (uint32_t)sh_repl[j]; role = sh_keep[j] ? 0u : 1u; coeff = cneg[(int64_t)j * a.B + i]; g = coeff * sgn_scale; }
             else { dest = (uint32_t)(j == eta ? ps : po); role = (j == eta) ? 2u : 3u; g = 1.f; }
             if (!entry_wanted(coeff, g)) continue;   // (no entry below the smallest normal number, masked zeros of non-finite scores kept: see the forward kernel)
-            uint32_t tile, local;
-            tile_of_row(dest, (uint32_t)a.st_n_tiles, (uint32_t)a.st_rb, tile, local);
-            StageEntry en{(uint32_t)i, role | (local << 2), g, dest};
-            const int slotpos = atomicAdd(a.st_counters + (size_t)tile * 32, 1);
-            if (slotpos < a.st_cap) {
-                a.st_lists[(size_t)tile * a.st_cap + slotpos] = en;
-            } else {
-                const int op = atomicAdd(a.st_counters + (size_t)a.st_n_tiles * 32, 1);
-                if (op < a.st_ovf_cap) a.st_ovf[op] = en;
-            }
+            stage_append(a, i, role, g, dest);
         }
     // ---- the positive's own s / o gradient rows: staged (roles 2, 3) ----
     if (active && qok) {

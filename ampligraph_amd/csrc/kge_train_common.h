@@ -1,7 +1,9 @@
 // What the training units share (kge_train.hip; the owner-computes step: kge_train_tiled.hip, kge_train_stage.hip, kge_train_tile.hip,
 // kge_train_direct.hip, kge_train_cols.hip): the staging protocol between the forward kernels and the tile passes (StageEntry,
-// block-interleaved row ownership, loss partials, hot rows), the forward kernels' arguments, the loss helpers the forward kernel
-// shares with the column-sharded kernels, and the LDS sizes the host plans with.
+// block-interleaved row ownership, loss partials, hot rows) with its ONE set of writers (stage_draws, stage_side_rows, stage_append:
+// used by train_fwdbwd_kernel and by the column-sharded kernels), the forward kernels' arguments, the wave's walk of Loss.__call__
+// (WaveWalk; the losses themselves and their NaN / inf rules are in kge_loss.h, which g++ compiles too), and the LDS sizes the host
+// plans with.
 // A training unit includes this header (or one that starts with it) FIRST: see KGE_FAST_ROTATE.
 #pragma once
 
@@ -16,6 +18,7 @@
 
 #include "kge_device.h"
 #include "kge_host.h"
+#include "kge_loss.h"
 
 static_assert(kge::ROTATE_FAST_FORMS, "kge_device.h was included before kge_train_common.h: this unit would train RotatE with the exact sqrt / division forms");
 
@@ -131,42 +134,97 @@ __device__ __forceinline__ void fold_loss_parts(double* parts, double* loss_sum,
     if (lane == 0 && loss_sum && t != 0.0) atomicAdd(loss_sum, t);
 }
 
-__device__ __forceinline__ float log_sigmoid(float x) {
-    // -softplus(-x), stable on both tails
-    return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
-}
-__device__ __forceinline__ float sigmoidf(float x) {
-    return 1.f / (1.f + expf(-x));
-}
+// The forward kernel's walk of Loss.__call__ (loss_call, kge_loss.h): one whole wave per positive, lane l takes the scores
+// sn[l], sn[l + 64], ... (LDS, sign and scale already applied) and the lanes' partial results meet in wave reductions.
+struct WaveWalk {
+    float* sn;
+    int lane;
+    __device__ __forceinline__ int first() const { return lane; }
+    __device__ __forceinline__ int stride() const { return KGE_WAVE; }
+    __device__ __forceinline__ float load(int j) const { return sn[j]; }
+    __device__ __forceinline__ void store(int j, float v) const { sn[j] = v; }
+    __device__ __forceinline__ float sum(float v) const { return wave_sum(v); }
+    __device__ __forceinline__ float max(float v) const { return wave_max(v); }
+};
 
-// clip_before_exp (loss_functions.py:60-66) = tf.clip_by_value = maximum(minimum(x, 75), -75) built from TensorFlow's NaN-PROPAGATING
-// minimum / maximum: a NaN score stays NaN in the loss VALUE.  C's fminf / fmaxf return the other operand instead, which made a NaN
-// positive cost a finite eta * log(1 + e^75) = 375 eta.  The GRADIENT through the clip is the exact zero of the
-// minimum / maximum masks (less_equal / greater_equal are false for NaN) -- what the `in` range tests beside every clip give.
-__device__ __forceinline__ float clip_exp(float x) {
-    return (x != x) ? x : fminf(fmaxf(x, -75.f), 75.f);
-}
-// tf.maximum(h, 0) of the two margin losses (:302-308, :458-464): NaN in the value, zero gradient (greater_equal(NaN, 0) is false)
-__device__ __forceinline__ float hinge_nan(float h) {
-    return (h != h) ? h : fmaxf(h, 0.f);
-}
-// A coefficient dL/dscore that a clip or hinge MASK sets to zero.  "Zero coefficient -> no bucket entry for the replaced row" (below,
-// STAGE) is valid only while the score's Jacobian is finite: TensorFlow multiplies the exact zero by it, so a positive whose own rows
-// hold a NaN hands 0 * NaN = NaN to the replacement rows of its corruptions.  The masked coefficient of a NON-FINITE score (x: the score,
-// or the hinge argument it enters) is therefore written as -0.0f: the entry test keeps it (entry_wanted), the tile pass adds (-0) * A --
-// NaN exactly where the side row is NaN, nothing elsewhere.  No loss produces -0.0f as a live coefficient.
-__device__ __forceinline__ float masked_zero(float x) {
-    return (fabsf(x) < INFINITY) ? 0.f : -0.f;
-}
-// The self-adversarial loss has no mask: its coefficient is COMPUTED, and for a score of -inf (a distance model's corruption that keeps a
-// row holding an inf) it is an exact zero -- softmax weight 0 times sigma(-inf) = 0 -- which TensorFlow again multiplies by the Jacobian.
-__device__ __forceinline__ float computed_zero(float c, float x) {
-    return (c == 0.f) ? masked_zero(x) : c;
-}
 // coeff: dL/dscore as the loss code left it; g = coeff * score_sign * score_scale.  No entry below fp32's smallest NORMAL number
 // (see the forward kernel) unless the coefficient is masked_zero's marker; a NaN coefficient is an entry.
 __device__ __forceinline__ bool entry_wanted(float coeff, float g) {
     return !(fabsf(g) < 1.17549435e-38f) || __float_as_uint(coeff) == 0x80000000u;
+}
+
+// ---- the writers of the staging protocol: what a forward kernel (train_fwdbwd_kernel<STAGE>, cols_scores_kernel / cols_stage_kernel)
+//      hands to tile_backward_kernel, written once ----
+
+// The corruption draws of positive i into LDS (CorruptionGenerationLayerTrain.py:35-94; Philox rows keyed by the global corruption
+// row, so every kernel and every GPU of a group draws the same), or the caller's own corruptions.  The threads that share the
+// positive take j = first, first + stride, ...
+__device__ __forceinline__ void stage_draws(const TrainArgs& a, int64_t i, int ps, int first, int stride, int* sh_keep, int* sh_repl) {
+    for (int j = first; j < a.eta; j += stride) {
+        int keep, repl;
+        if (a.neg_override) {
+            const int64_t r = (int64_t)j * a.B + i;
+            const int ns = a.neg_override[3 * r + 0], no = a.neg_override[3 * r + 2];
+            keep = (ns == ps) ? 1 : 0;
+            repl = keep ? no : ns;
+        } else {
+            draw_corruption(a.sc, i, j, keep, repl);
+        }
+        sh_keep[j] = keep;
+        sh_repl[j] = repl;
+    }
+}
+
+// The side rows A, B of one quad of a positive (staged rows 2, 3; qa / qb point at the quad, k floats between the halves).
+// Trilinear models: d(score)/d(replaced row) does not depend on the replaced row, so the owner only needs g * A (A = d/do (s,p)) or
+// g * B (B = d/ds (p,o)).  TransE: copies of s and o (the owner recomputes grad_unit with its own row).
+// RotatE: A = s o r (the reference's own first step of s o r - e, RotatE.py:100-101: the object-side entries of the tile pass are
+// bit-identical to grad_unit), B = o o conj(r): |e o r - o| = |e - B| as |r| = 1, and d|e o r - o| / de = (e - B) / |e - B| -- one
+// side row and the tile's own row per entry, no relation row.  (p holds cos, sin: prep_rel.)
+template <int MODEL>
+__device__ __forceinline__ void stage_side_rows(const float (&s)[4][ModelTraits<MODEL>::NC], const float (&p)[4][ModelTraits<MODEL>::NC],
+                                                const float (&o)[4][ModelTraits<MODEL>::NC], float* qa, float* qb, int k) {
+    constexpr int NC = ModelTraits<MODEL>::NC;
+    float va[NC][4], vb[NC][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if constexpr (MODEL == AMDKGE_DISTMULT || MODEL == AMDKGE_COMPLEX) {
+            float ds[NC], dp[NC], dd[NC];
+            grad_unit<MODEL>(s[u], p[u], o[u], 1.f, ds, dp, dd);
+#pragma unroll
+            for (int h = 0; h < NC; ++h) { va[h][u] = dd[h]; vb[h][u] = ds[h]; }
+        } else if constexpr (MODEL == AMDKGE_ROTATE) {
+            const float cs = p[u][0], sn = p[u][1];
+            va[0][u] = s[u][0] * cs - s[u][1] * sn; va[1][u] = s[u][0] * sn + s[u][1] * cs;
+            vb[0][u] = o[u][0] * cs + o[u][1] * sn; vb[1][u] = o[u][1] * cs - o[u][0] * sn;
+        } else {
+#pragma unroll
+            for (int h = 0; h < NC; ++h) { va[h][u] = s[u][h]; vb[h][u] = o[u][h]; }
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < NC; ++h) {
+        *reinterpret_cast<float4*>(qa + h * k) = make_float4(va[h][0], va[h][1], va[h][2], va[h][3]);
+        *reinterpret_cast<float4*>(qb + h * k) = make_float4(vb[h][0], vb[h][1], vb[h][2], vb[h][3]);
+    }
+}
+
+// One row-gradient entry into the bucket of the tile that owns row `dest` (block-interleaved ownership, see tile_backward_kernel);
+// a full bucket spills into the overflow list.  `role`: the StageEntry role, with whatever the caller keeps above the local row
+// (local < 4096: below the corruption index of ENTRY_J_SHIFT).
+__device__ __forceinline__ void stage_append(const TrainArgs& a, int64_t i, uint32_t role, float g, uint32_t dest) {
+    uint32_t tile, local;
+    tile_of_row(dest, (uint32_t)a.st_n_tiles, (uint32_t)a.st_rb, tile, local);
+    StageEntry* where;
+    const int slotpos = atomicAdd(a.st_counters + (size_t)tile * 32, 1);
+    if (slotpos < a.st_cap) {
+        where = a.st_lists + (size_t)tile * a.st_cap + slotpos;
+    } else {
+        const int op = atomicAdd(a.st_counters + (size_t)a.st_n_tiles * 32, 1);
+        if (op >= a.st_ovf_cap) return;
+        where = a.st_ovf + op;
+    }
+    *where = StageEntry{(uint32_t)i, role | (local << 2), g, dest};   // (one 16-byte store)
 }
 
 // TransE keeps, per corruption and unit, only sign(s + p - o) for its backward pass (the gradient of |x|): 2 bits per unit,

@@ -1,7 +1,8 @@
-// The fused forward(+backward) training kernel template and the loss code only it uses, instantiated by the atomic-scatter path
-// (kge_train.hip, STAGE = false) and by the forward unit of the owner-computes path (kge_train_stage.hip, STAGE = true).  See
-// kge_train.hip for the description of the slot mapping; its arguments and what it shares with the other training kernels are in
-// kge_train_common.h.
+// The fused forward(+backward) training kernel template and the loss code only it uses (FocusE, the single-pass forms), instantiated
+// by the atomic-scatter path (kge_train.hip, STAGE = false) and by the forward unit of the owner-computes path (kge_train_stage.hip,
+// STAGE = true).  See kge_train.hip for the description of the slot mapping.  Shared with the column-sharded kernels and defined
+// elsewhere: Loss.__call__ (loss_call, kge_loss.h, walked here by WaveWalk), the kernel's arguments and the writers of the staging
+// protocol (stage_draws, stage_side_rows, stage_append: kge_train_common.h).
 #pragma once
 #include "kge_train_common.h"
 
@@ -19,89 +20,6 @@ __device__ __forceinline__ void focus_apply(int nl, float x, float wgt, float& y
     }
     y = f * wgt;
     dfac = fp * wgt;
-}
-
-// Loss.__call__ for one positive: neg scores in `sn[0..eta)` (LDS) are replaced by dL/dneg.
-// Returns per-sample loss and dL/dpos.  Executed by one whole wave (all lanes get the results).
-__device__ __forceinline__ void loss_and_dscore(const amdkge_loss& L, float P, float* sn, int eta, int lane,
-                                                float& per, float& dP) {
-    const float feta = (float)eta;
-    float red = L.reduction_mean ? feta : 1.f;
-    switch (L.kind) {
-        case AMDKGE_LOSS_PAIRWISE: {  // loss_functions.py:302-308
-            float acc = 0.f, cnt = 0.f;
-            for (int j = lane; j < eta; j += KGE_WAVE) {
-                const float h = L.margin - P + sn[j];
-                const bool act = h >= 0.f;
-                acc += hinge_nan(h);
-                cnt += act ? 1.f : 0.f;
-                sn[j] = act ? 1.f / red : masked_zero(h);
-            }
-            per = wave_sum(acc) / red;
-            dP = -wave_sum(cnt) / red;
-        } break;
-        case AMDKGE_LOSS_NLL: {  // :376-382 (clip at :60-66)
-            if (L.reduction_mean) red = 2.f * feta;
-            const bool inP = (P >= -75.f) && (P <= 75.f);
-            const float Pc = clip_exp(P);
-            float acc = 0.f;
-            for (int j = lane; j < eta; j += KGE_WAVE) {
-                const float n = sn[j];
-                const bool in = (n >= -75.f) && (n <= 75.f);
-                const float nc = clip_exp(n);
-                acc += logf(1.f + expf(nc));
-                sn[j] = in ? sigmoidf(nc) / red : masked_zero(n);
-            }
-            per = (feta * logf(1.f + expf(-Pc)) + wave_sum(acc)) / red;
-            dP = inP ? -feta * sigmoidf(-Pc) / red : 0.f;
-        } break;
-        case AMDKGE_LOSS_ABSOLUTE_MARGIN: {  // :458-464
-            float acc = 0.f;
-            for (int j = lane; j < eta; j += KGE_WAVE) {
-                const float h = L.margin + sn[j];
-                acc += hinge_nan(h);
-                sn[j] = (h >= 0.f) ? 1.f / red : masked_zero(h);
-            }
-            per = (wave_sum(acc) - feta * P) / red;
-            dP = -feta / red;
-        } break;
-        case AMDKGE_LOSS_SELF_ADVERSARIAL: {  // :556-574 (softmax NOT stop-gradiented)
-            float mx = -INFINITY;
-            for (int j = lane; j < eta; j += KGE_WAVE) mx = fmaxf(mx, L.alpha * sn[j]);
-            mx = wave_max(mx);
-            float se = 0.f;
-            for (int j = lane; j < eta; j += KGE_WAVE) se += expf(L.alpha * sn[j] - mx);
-            se = wave_sum(se);
-            float lb = 0.f;
-            for (int j = lane; j < eta; j += KGE_WAVE) {
-                const float w = expf(L.alpha * sn[j] - mx) / se;
-                lb += w * log_sigmoid(-sn[j] - L.margin);
-            }
-            const float lbar = wave_sum(lb);
-            for (int j = lane; j < eta; j += KGE_WAVE) {
-                const float n = sn[j];
-                const float w = expf(L.alpha * n - mx) / se;
-                const float ell = log_sigmoid(-n - L.margin);
-                sn[j] = computed_zero((w * sigmoidf(n + L.margin) - L.alpha * w * (ell - lbar)) / red, n);
-            }
-            per = -log_sigmoid(L.margin + P) - lbar / red;
-            dP = -sigmoidf(-(L.margin + P));
-        } break;
-        default: {  // AMDKGE_LOSS_MULTICLASS_NLL :647-654
-            const bool inP = (P >= -75.f) && (P <= 75.f);
-            const float eP = expf(clip_exp(P));
-            float acc = 0.f;
-            for (int j = lane; j < eta; j += KGE_WAVE) acc += expf(clip_exp(sn[j]));
-            const float Z = wave_sum(acc) / red + eP;
-            for (int j = lane; j < eta; j += KGE_WAVE) {
-                const float n = sn[j];
-                const bool in = (n >= -75.f) && (n <= 75.f);
-                sn[j] = in ? expf(clip_exp(n)) / Z / red : masked_zero(n);
-            }
-            per = -logf(eP / Z);
-            dP = inP ? -1.f + eP / Z : 0.f;
-        } break;
-    }
 }
 
 // Single-pass backward for the trilinear models (DistMult / ComplEx / HolE).  There d(score)/d(s,p,o) is LINEAR in
@@ -204,7 +122,7 @@ __device__ __forceinline__ float onepass_coeff(const amdkge_loss& L, float P, fl
     switch (L.kind) {
         case AMDKGE_LOSS_PAIRWISE: c1 = (valid && (L.margin - P + n >= 0.f)) ? 1.f : 0.f; break;
         case AMDKGE_LOSS_NLL: {
-            const bool in = valid && (n >= -75.f) && (n <= 75.f);
+            const bool in = valid && in_clip(n);
             float sg, lsn;
             sig_logsig(det, clip_exp(n), sg, lsn);
             st.Lw += valid ? -lsn : 0.f;   // softplus(clip n) = log(1 + exp(clip n))
@@ -226,7 +144,7 @@ __device__ __forceinline__ float onepass_coeff(const amdkge_loss& L, float P, fl
             c2 = u;
         } break;
         default: {
-            const bool in = valid && (n >= -75.f) && (n <= 75.f);
+            const bool in = valid && in_clip(n);
             const float ex = valid ? exp_any(det, clip_exp(n)) : 0.f;
             st.Zs += ex;
             c1 = in ? ex : 0.f;
@@ -238,10 +156,10 @@ __device__ __forceinline__ float onepass_coeff(const amdkge_loss& L, float P, fl
 // st holds the wave totals here (wave_sum of the per-lane partials)
 __device__ __forceinline__ void onepass_kappa(const amdkge_loss& L, float P, int eta, const OnePassState& st, float& k1, float& k2, bool det = false) {
     const float feta = (float)eta;
-    float red = L.reduction_mean ? feta : 1.f;
+    const float red = loss_red(L, feta);
     k2 = 0.f;
     switch (L.kind) {
-        case AMDKGE_LOSS_NLL: if (L.reduction_mean) red = 2.f * feta; k1 = 1.f / red; break;
+        case AMDKGE_LOSS_NLL: k1 = 1.f / loss_red(L, feta, 2.f); break;
         case AMDKGE_LOSS_SELF_ADVERSARIAL: k1 = 1.f / (st.S * red); k2 = L.alpha * (st.Lw / st.S) / (st.S * red); break;
         case AMDKGE_LOSS_MULTICLASS_NLL: {
             const float eP = exp_any(det, clip_exp(P));
@@ -251,23 +169,23 @@ __device__ __forceinline__ void onepass_kappa(const amdkge_loss& L, float P, int
     }
 }
 
-// Loss.__call__ for one positive on the single-pass path: same outputs as loss_and_dscore (per-sample loss, dL/dpos,
+// Loss.__call__ for one positive on the single-pass path: same outputs as loss_call (per-sample loss, dL/dpos,
 // sn[j] <- dL/dneg_j) from the statistics the row loop already gathered (st = wave totals).
 __device__ __forceinline__ void onepass_finish(const amdkge_loss& L, float P, float* sn, int eta, int lane,
                                                const OnePassState& st, float& per, float& dP, bool det = false) {
     const float feta = (float)eta;
-    float red = L.reduction_mean ? feta : 1.f;
+    float red = loss_red(L, feta);
     switch (L.kind) {
         case AMDKGE_LOSS_NLL: {   // loss_functions.py:376-382
-            if (L.reduction_mean) red = 2.f * feta;
-            const bool inP = (P >= -75.f) && (P <= 75.f);
+            red = loss_red(L, feta, 2.f);
+            const bool inP = in_clip(P);
             float sgP, lsP;
             sig_logsig(det, -clip_exp(P), sgP, lsP);   // sigma(-Pc), log sigma(Pc)
             for (int j = lane; j < eta; j += KGE_WAVE) {
                 const float n = sn[j];
                 float sg, ls;
                 sig_logsig(det, clip_exp(n), sg, ls);
-                sn[j] = ((n >= -75.f) && (n <= 75.f)) ? sg / red : masked_zero(n);
+                sn[j] = in_clip(n) ? sg / red : masked_zero(n);
             }
             per = (feta * -lsP + st.Lw) / red;   // log(1+exp(-Pc)) = -log sigma(Pc)
             dP = inP ? -feta * sgP / red : 0.f;
@@ -287,13 +205,13 @@ __device__ __forceinline__ void onepass_finish(const amdkge_loss& L, float P, fl
             dP = -sgP;
         } break;
         default: {   // AMDKGE_LOSS_MULTICLASS_NLL :647-654
-            const bool inP = (P >= -75.f) && (P <= 75.f);
+            const bool inP = in_clip(P);
             const float Pc = clip_exp(P);
             const float eP = exp_any(det, Pc);
             const float Z = st.Zs / red + eP;
             for (int j = lane; j < eta; j += KGE_WAVE) {
                 const float n = sn[j];
-                sn[j] = ((n >= -75.f) && (n <= 75.f)) ? exp_any(det, clip_exp(n)) / Z / red : masked_zero(n);
+                sn[j] = in_clip(n) ? exp_any(det, clip_exp(n)) / Z / red : masked_zero(n);
             }
             per = (det ? logf(Z) : __builtin_amdgcn_logf(Z) * 0.6931471805599453f) - Pc;   // -log(eP / Z)  (the loss VALUE only: nothing feeds back)
             dP = inP ? -1.f + eP / Z : 0.f;
@@ -356,19 +274,7 @@ __global__ __launch_bounds__(256) void train_fwdbwd_kernel(TrainArgs a) {
     const int ps = a.triples[3 * i + 0], pp = a.triples[3 * i + 1], po = a.triples[3 * i + 2];
 
     // ---- negatives of this positive (a3) ------------------------------------------------------
-    for (int j = ts; j < eta; j += TS) {
-        int keep, repl;
-        if (a.neg_override) {
-            const int64_t r = (int64_t)j * a.B + i;
-            const int ns = a.neg_override[3 * r + 0], no = a.neg_override[3 * r + 2];
-            keep = (ns == ps) ? 1 : 0;
-            repl = keep ? no : ns;
-        } else {
-            draw_corruption(a.sc, i, j, keep, repl);
-        }
-        sh_keep[j] = keep;
-        sh_repl[j] = repl;
-    }
+    stage_draws(a, i, ps, ts, TS, sh_keep, sh_repl);
 
     // ---- resident quads of s, p, o ------------------------------------------------------------
     const float* rs = a.ent + (int64_t)ps * a.K;
@@ -408,43 +314,14 @@ __global__ __launch_bounds__(256) void train_fwdbwd_kernel(TrainArgs a) {
 #pragma unroll
         for (int u = 0; u < VEC; ++u) pad1[c][u] = (MODEL == AMDKGE_ROTATE && qoff[c] + u >= a.k_live) ? 1.f : 0.f;
     if constexpr (STAGE) {
-        // side rows for the owner kernel.  Trilinear models: d(score)/d(replaced row) does not depend on the
-        // replaced row, so the owner only needs g * A (A = d/do (s,p)) or g * B (B = d/ds (p,o)).
-        // TransE: copies of s and o (the owner recomputes grad_unit with its own row); RotatE: s and o rotated onto the replaced row.
+        // side rows A, B for the owner kernel (stage_side_rows)
         static_assert(!STAGE || VEC == 4, "staging uses the 16-byte layout");
-        constexpr bool TRILINEAR = (MODEL == AMDKGE_DISTMULT || MODEL == AMDKGE_COMPLEX);
         if (active && !KGE_DBG(a, 64)) {
             float* qa = a.stage_rows + ((int64_t)i * a.ns + 2) * a.K;
             float* qb = a.stage_rows + ((int64_t)i * a.ns + 3) * a.K;
 #pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                if (!qok[c]) continue;
-                float va[NC][4], vb[NC][4];
-#pragma unroll
-                for (int u = 0; u < VEC; ++u) {
-                    if constexpr (TRILINEAR) {
-                        float ds[NC], dp[NC], dd[NC];
-                        grad_unit<MODEL>(s[c][u], p[c][u], o[c][u], 1.f, ds, dp, dd);
-#pragma unroll
-                        for (int h = 0; h < NC; ++h) { va[h][u] = dd[h]; vb[h][u] = ds[h]; }
-                    } else if constexpr (MODEL == AMDKGE_ROTATE) {
-                        // A = s o r (the reference's own first step of s o r - e, RotatE.py:100-101: the object-side entries of
-                        // the tile pass are bit-identical to grad_unit), B = o o conj(r): |e o r - o| = |e - B| as |r| = 1, and
-                        // d|e o r - o| / de = (e - B) / |e - B| -- one side row and the tile's own row per entry, no relation row
-                        const float cs = p[c][u][0], sn = p[c][u][1];
-                        va[0][u] = s[c][u][0] * cs - s[c][u][1] * sn; va[1][u] = s[c][u][0] * sn + s[c][u][1] * cs;
-                        vb[0][u] = o[c][u][0] * cs + o[c][u][1] * sn; vb[1][u] = o[c][u][1] * cs - o[c][u][0] * sn;
-                    } else {
-#pragma unroll
-                        for (int h = 0; h < NC; ++h) { va[h][u] = s[c][u][h]; vb[h][u] = o[c][u][h]; }
-                    }
-                }
-#pragma unroll
-                for (int h = 0; h < NC; ++h) {
-                    *reinterpret_cast<float4*>(qa + qoff[c] + h * a.k) = make_float4(va[h][0], va[h][1], va[h][2], va[h][3]);
-                    *reinterpret_cast<float4*>(qb + qoff[c] + h * a.k) = make_float4(vb[h][0], vb[h][1], vb[h][2], vb[h][3]);
-                }
-            }
+            for (int c = 0; c < CH; ++c)
+                if (qok[c]) stage_side_rows<MODEL>(s[c], p[c], o[c], qa + qoff[c], qb + qoff[c], a.k);
         }
     }
     slot_sync<W>();
@@ -864,9 +741,9 @@ __global__ __launch_bounds__(256) void train_fwdbwd_kernel(TrainArgs a) {
     float per = 0.f, dP = 0.f;
     if constexpr (ONEPASS) {
         // pairwise / absolute_margin have no transcendental and keep the generic evaluation
-        if (a.loss.kind == AMDKGE_LOSS_PAIRWISE || a.loss.kind == AMDKGE_LOSS_ABSOLUTE_MARGIN) { if (W == 1 || wv == 0) loss_and_dscore(a.loss, P, sh_neg, eta, lane, per, dP); }
+        if (a.loss.kind == AMDKGE_LOSS_PAIRWISE || a.loss.kind == AMDKGE_LOSS_ABSOLUTE_MARGIN) { if (W == 1 || wv == 0) loss_call(a.loss, P, eta, WaveWalk{sh_neg, lane}, per, dP); }
         else if (W == 1 || wv == 0) onepass_finish(a.loss, P, sh_neg, eta, lane, ops, per, dP, DET);   // (rewrites sh_neg in place: one wave)
-    } else if (W == 1 || wv == 0) loss_and_dscore(a.loss, P, sh_neg, eta, lane, per, dP);
+    } else if (W == 1 || wv == 0) loss_call(a.loss, P, eta, WaveWalk{sh_neg, lane}, per, dP);
     if constexpr (W > 1) {
         if (wv == 0 && lane == 0) sh_part[0] = dP;
         __syncthreads();
@@ -897,16 +774,7 @@ __global__ __launch_bounds__(256) void train_fwdbwd_kernel(TrainArgs a) {
                 // Kept: NaN coefficients and the masked zeros of non-finite scores (masked_zero above).
                 if (!entry_wanted(coeff, g)) continue;
                 if (j >= eta && a.hot_map && a.hot_map[dest]) continue;   // hot row: went to its replicas (below), no entry
-                uint32_t tile, local;
-                tile_of_row(dest, (uint32_t)a.st_n_tiles, (uint32_t)a.st_rb, tile, local);   // block-interleaved ownership, see tile_backward_kernel
-                StageEntry en{(uint32_t)i, role | (local << 2), g, dest};   // local < 4096: below the corruption index
-                const int slotpos = atomicAdd(a.st_counters + (size_t)tile * 32, 1);
-                if (slotpos < a.st_cap) {
-                    a.st_lists[(size_t)tile * a.st_cap + slotpos] = en;
-                } else {
-                    const int op = atomicAdd(a.st_counters + (size_t)a.st_n_tiles * 32, 1);
-                    if (op < a.st_ovf_cap) a.st_ovf[op] = en;
-                }
+                stage_append(a, i, role, g, dest);
             }
     }
 

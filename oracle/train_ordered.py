@@ -219,7 +219,7 @@ def transe_pairwise_step(state, pos, eta, seed, step, margin=1.0, n_ents=None, r
     np.add.at(Gr, pos[:, 1], sgp)
     np.add.at(Ge, pos[:, 2], -sgp)
     per = wave_sum(h_lanes)
-    if loss == "absolute_margin":   # per = (wave_sum(acc) - feta * P) / red, red = 1 (kge_train_kernel.h loss_and_dscore)
+    if loss == "absolute_margin":   # per = (wave_sum(acc) - feta * P) / red, red = 1 (kge_loss.h loss_call over WaveWalk)
         per = (per - (F32(eta) * P).astype(F32)).astype(F32)
     assert np.abs(Ge).max() < 2 ** 24 and np.abs(Gr).max() < 2 ** 24
     if return_grads:   # (tests: the step's ingredients, nothing applied)

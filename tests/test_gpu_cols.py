@@ -88,6 +88,41 @@ def test_cols_phases_against_oracle(gpu_lib, model, k, W, loss):
         assert_grads_close(dense(e, e.g_rel), col_slice(Tr, model, k, W, r), tol=1e-4)
 
 
+@pytest.mark.parametrize("loss", ["self_adversarial", "nll", "pairwise", "multiclass_nll", "absolute_margin"])
+def test_cols_loss_second_grid_stride_trip(gpu_lib, loss):
+    """cols_loss at the smallest batch whose positives do not fit one trip of the kernel's grid-stride loop (1024 blocks of 256
+    threads): the 77 positives of the second trip walk their scores from the same base and with the same B stride as everyone else.
+    Against the same positives evaluated in two calls of at most 1024 * 256 each (re-laid-out to j * B + i): the coefficients are the
+    same bits, and the loss is the sum of the two calls' losses (fp64 sums that differ in block order only)."""
+    from ampligraph_amd.engine import KgeEngine
+
+    trip, eta = 1024 * 256, 3
+    B = trip + 77
+    eng = KgeEngine("TransE", 8, 16, 2)        # (score sign -1: the walk applies it)
+    rng = np.random.default_rng(11)
+    want = (rng.normal(size=(1 + eta, B)) * 3).astype(np.float32)   # row 0: the positives; row 1 + j: corruption j of every positive
+    far = rng.random((1 + eta, B)) < 0.01
+    want = np.where(far, np.where(rng.random((1 + eta, B)) < 0.5, 80.0, -80.0), want).astype(np.float32)   # both sides of the clip
+    want[0] = np.abs(want[0]) * np.where(far[0], 1.0, np.sign(want[0]))   # (no positive below -75: e^P / Z stays inside fp32)
+    raw = -want
+    ld = loss_desc(loss, "sum")
+
+    def call(block):
+        b = block.shape[1]
+        t = dev(block.reshape(-1))
+        eng.loss_acc.zero_()
+        eng.cols_loss(ld, t, b, eta)
+        torch.cuda.synchronize()
+        return t.cpu().numpy().reshape(1 + eta, b), float(eng.loss_acc[0].item())
+
+    whole, lw = call(raw)
+    first, l1 = call(raw[:, :trip])
+    second, l2 = call(raw[:, trip:])
+    assert np.isfinite(lw) and lw != 0.0
+    assert np.array_equal(whole.view(np.uint32), np.concatenate([first, second], 1).view(np.uint32))
+    assert abs(lw - (l1 + l2)) <= 1e-12 * abs(lw), (lw, l1, l2)
+
+
 @pytest.mark.parametrize("model,k,W,opt", [("ComplEx", 200, 8, "adam"), ("DistMult", 64, 2, "adagrad"), ("TransE", 48, 4, "sgd"), ("RotatE", 100, 2, "adam"),
                                            ("HolE", 96, 4, "rmsprop")])
 def test_cols_whole_steps_match_oracle(gpu_lib, model, k, W, opt):
