@@ -6,8 +6,8 @@
 
 namespace kge {
 
-// One workgroup per row: the streaming selection of topk_rows_kernel (kge_discovery.hip; same key, same merges, so the same order)
-// with a membership test in front of the staging buffer.  Only a column whose key beats the current k-th best is looked up: after
+// One workgroup per row: the streaming selection (TopkStream, kge_topk.h) with topk_rows_kernel's key (kge_discovery.hip), so the same
+// order, and a membership test in front of the staging buffer.  Only a column whose key beats the current k-th best is looked up: after
 // the first merge that is a handful of columns per row, the known facts among them (they score highest), so the usual column costs
 // one compare as before.
 __global__ __launch_bounds__(256) void topk_rows_excluding_kernel(const float* __restrict__ vals, int64_t m, int64_t ld, const int32_t* __restrict__ col_ids,
@@ -22,33 +22,21 @@ __global__ __launch_bounds__(256) void topk_rows_excluding_kernel(const float* _
     const int64_t lo = ex_lo ? ex_lo[r] : 0, hi = ex_lo ? ex_hi[r] : 0;
     const bool has_own = own != nullptr;
     const int64_t own_id = has_own ? (int64_t)own[r] : 0;
-    for (int i = tid; i < TOPK_BUF; i += 256) buf[i] = 0ull;
-    if (tid == 0) n_stage = 0;
-    __syncthreads();
-    unsigned long long kth = 0ull;   // key of the current k-th best (0: fewer than k candidates so far)
+    TopkStream sel{buf, &n_stage};
+    sel.reset(tid);
     for (int64_t c0 = 0; c0 < m; c0 += 256) {
         const int64_t c = c0 + tid;
-        if (c < m) {
-            const unsigned long long key = ((unsigned long long)sortable(row[c]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
-            if (key > kth) {
+        if (c < m)
+            sel.offer(topk_key(sortable(row[c]), c), [&] {
                 const int64_t id = col_ids ? (int64_t)col_ids[c] : id_base + c;
-                if (!(has_own && id == own_id) && !sorted_contains(ex_ids, lo, hi, id)) buf[TOPK_MAX + atomicAdd(&n_stage, 1)] = key;
-            }
-        }
-        __syncthreads();
-        if (n_stage > TOPK_MAX - 256 || c0 + 256 >= m) {   // staging (nearly) full, or end of the row: merge
-            sort_desc(buf, tid);
-            if (tid == 0) n_stage = 0;
-            kth = buf[k - 1];
-            __syncthreads();
-            for (int i = TOPK_MAX + tid; i < TOPK_BUF; i += 256) buf[i] = 0ull;
-            __syncthreads();
-        }
+                return !(has_own && id == own_id) && !sorted_contains(ex_ids, lo, hi, id);
+            });
+        sel.end_of_block(k, c0 + 256 >= m);
     }
     for (int i = tid; i < k; i += 256) {
         const unsigned long long key = buf[i];
         const bool have = key != 0ull;
-        out_idx[r * k + i] = have ? (int32_t)(0xFFFFFFFFu - (uint32_t)key) : -1;
+        out_idx[r * k + i] = have ? topk_col(key) : -1;
         out_val[r * k + i] = have ? unsortable((uint32_t)(key >> 32)) : -INFINITY;
     }
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/amdkge.h"
+#include "kge_order.h"   // sortable / unsortable, sorted_contains
 
 #define KGE_WAVE 64
 
@@ -136,6 +137,13 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     return v;
 }
 
+// inclusive prefix sum over the wave's lanes (lane = this thread's); lane 63 holds the wave total
+__device__ __forceinline__ int wave_incl_sum_i(int v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int up = __shfl_up(v, o, 64); if (lane >= o) v += up; }
+    return v;
+}
+
 // ----------------------------------------------------------------------------------------------
 // small fixed vectors with 16/8/4-byte global accesses
 // ----------------------------------------------------------------------------------------------
@@ -166,17 +174,6 @@ __device__ __forceinline__ void atomic_add_f32(float* p, float v) {
 
 __device__ __forceinline__ void atomic_add_f32_wg(float* p, float v) {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// is `id` in the ascending range ids[lo .. hi)?  (the id order inside a group of amdkge_filter_build / amdkge_pair_filter_build)
-__device__ __forceinline__ bool sorted_contains(const int32_t* __restrict__ ids, int64_t lo, int64_t hi, int64_t id) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const int64_t v = ids[mid];
-        if (v == id) return true;
-        if (v < id) lo = mid + 1; else hi = mid;
-    }
-    return false;
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -20,8 +20,8 @@ __device__ __forceinline__ bool select_masked(const uint32_t* bitmap, bool use_b
     return sorted_contains(ids, lo, hi, c);
 }
 
-// One workgroup per query row.  Sweep one: streaming top-R of the quantised keys of the counted columns (the selection of
-// topk_rows_kernel; key = quantised score << 32 | ~column, so the R-th key holds the R-th largest value WITH multiplicity).
+// One workgroup per query row.  Sweep one: streaming top-R of the quantised keys of the counted columns (TopkStream, kge_topk.h;
+// key = quantised score << 32 | ~column, so the R-th key holds the R-th largest value WITH multiplicity).
 // Sweep two: emission, one vector atomic per wave (ballot + popcount); the row was just read, so this pass is served by the caches.
 __global__ __launch_bounds__(256) void discover_select_kernel(const float* __restrict__ scores, int64_t m, int64_t ld, const int32_t* __restrict__ queries,
                                                               int own_col, const int64_t* __restrict__ flt_lo, const int64_t* __restrict__ flt_hi,
@@ -51,31 +51,18 @@ __global__ __launch_bounds__(256) void discover_select_kernel(const float* __res
         T = thr[r];
         __syncthreads();
     } else {
-        for (int i = tid; i < TOPK_BUF; i += 256) buf[i] = 0ull;
-        if (tid == 0) { n_stage = 0; any_bad = 0; }
-        __syncthreads();
-        unsigned long long kth = 0ull;   // key of the current R-th best (0: fewer than R counted columns so far)
+        if (tid == 0) any_bad = 0;
+        TopkStream sel{buf, &n_stage};
+        sel.reset(tid);
         bool bad = false;
         for (int64_t c0 = 0; c0 < m; c0 += 256) {
             const int64_t c = c0 + tid;
             if (c < m) {
                 const float v = row[c];
                 bad |= select_non_finite(v);
-                if (!select_masked(bitmap, use_bitmap, flt_ids, lo, hi, c)) {
-                    const uint32_t qk = (uint32_t)quantise(v) ^ 0x80000000u;
-                    const unsigned long long key = ((unsigned long long)qk << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
-                    if (key > kth) buf[TOPK_MAX + atomicAdd(&n_stage, 1)] = key;
-                }
+                if (!select_masked(bitmap, use_bitmap, flt_ids, lo, hi, c)) sel.offer(topk_key((uint32_t)quantise(v) ^ 0x80000000u, c));
             }
-            __syncthreads();
-            if (n_stage > TOPK_MAX - 256 || c0 + 256 >= m) {   // staging (nearly) full, or end of the row: merge
-                sort_desc(buf, tid);
-                if (tid == 0) n_stage = 0;
-                kth = buf[R - 1];
-                __syncthreads();
-                for (int i = TOPK_MAX + tid; i < TOPK_BUF; i += 256) buf[i] = 0ull;
-                __syncthreads();
-            }
+            sel.end_of_block(R, c0 + 256 >= m);
         }
         if (bad) any_bad = 1;
         __syncthreads();

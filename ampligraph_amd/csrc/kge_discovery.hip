@@ -6,9 +6,7 @@
 
 namespace kge {
 
-// One workgroup per row: streaming top-k.  key = sortable(value) << 32 | ~column, so equal values are ordered by
-// LOWER column first and the result is deterministic.  Values at or below the current k-th best are dropped as they
-// stream by; survivors collect in the staging half and are merged (one bitonic sort) whenever it fills.
+// One workgroup per row: streaming top-k (TopkStream, kge_topk.h) of key = sortable(value) << 32 | ~column.
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ vals, int64_t m, int64_t ld, const float* __restrict__ col_scale,
                                                         const float* __restrict__ col_bias, const int32_t* __restrict__ payload, int k, int largest,
                                                         int32_t* __restrict__ out_idx, float* __restrict__ out_val) {
@@ -16,10 +14,8 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     __shared__ int n_stage;
     const int tid = threadIdx.x;
     const float* row = vals + (int64_t)blockIdx.x * ld;
-    for (int i = tid; i < TOPK_BUF; i += 256) buf[i] = 0ull;
-    if (tid == 0) n_stage = 0;
-    __syncthreads();
-    unsigned long long kth = 0ull;   // key of the current k-th best (0: fewer than k candidates so far)
+    TopkStream sel{buf, &n_stage};
+    sel.reset(tid);
     for (int64_t c0 = 0; c0 < m; c0 += 256) {
         const int64_t c = c0 + tid;
         if (c < m) {
@@ -27,24 +23,15 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
             if (col_scale) v *= col_scale[c];
             if (col_bias) v += col_bias[c];
             if (!largest) v = -v;
-            const unsigned long long key = ((unsigned long long)sortable(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
-            if (key > kth) buf[TOPK_MAX + atomicAdd(&n_stage, 1)] = key;
+            sel.offer(topk_key(sortable(v), c));
         }
-        __syncthreads();
-        if (n_stage > TOPK_MAX - 256 || c0 + 256 >= m) {   // staging (nearly) full, or end of the row: merge
-            sort_desc(buf, tid);
-            if (tid == 0) n_stage = 0;
-            kth = buf[k - 1];
-            __syncthreads();
-            for (int i = TOPK_MAX + tid; i < TOPK_BUF; i += 256) buf[i] = 0ull;
-            __syncthreads();
-        }
+        sel.end_of_block(k, c0 + 256 >= m);
     }
     for (int i = tid; i < k; i += 256) {
         const unsigned long long key = buf[i];
         const bool have = key != 0ull;
         float v = unsortable((uint32_t)(key >> 32));
-        const int32_t col = (int32_t)(0xFFFFFFFFu - (uint32_t)key);
+        const int32_t col = topk_col(key);
         out_idx[(int64_t)blockIdx.x * k + i] = have ? (payload ? payload[(int64_t)blockIdx.x * ld + col] : col) : -1;
         out_val[(int64_t)blockIdx.x * k + i] = have ? (largest ? v : -v) : (largest ? -INFINITY : INFINITY);
     }

@@ -333,12 +333,7 @@ __global__ __launch_bounds__(1024) void join_rank_kernel(const int32_t* __restri
             f[u] = (i < n && core[i] && parent[i] == (int32_t)i) ? 1 : 0;
             s += f[u];
         }
-        int inc = s;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += up;
-        }
+        const int inc = wave_incl_sum_i(s, lane);
         if (lane == 63) wsum[w] = inc;
         __syncthreads();
         int below = 0, all = 0;

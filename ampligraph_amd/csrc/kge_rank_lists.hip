@@ -40,17 +40,6 @@ struct ListArgs {
     float sgn_scale;
 };
 
-// is `id` among the ascending ids[lo .. hi) ?
-template <typename I>
-__device__ __forceinline__ bool list_known(const int32_t* ids, I lo, I hi, int32_t id) {
-    const I end = hi;
-    while (lo < hi) {
-        const I mid = lo + ((hi - lo) >> 1);
-        if (ids[mid] < id) lo = mid + 1; else hi = mid;
-    }
-    return lo < end && ids[lo] == id;
-}
-
 // A triple's known positives, as the wave that ranks it sees them.  Every candidate that outranks the positive is looked up among
 // them -- on untrained tables that is half of all candidates --, and a lookup in global memory is a chain of dependent loads at
 // the end of each group of 64.  Ranges of up to FLT_STAGE ids (all but a few: a (p, o) key has a handful of subjects) are
@@ -75,7 +64,7 @@ struct KnownIds {
     __device__ __forceinline__ bool active() const { return glob != nullptr; }
     __device__ __forceinline__ bool has(int32_t id) const {
         if (hi <= lo) return false;
-        return lds ? list_known<int>(lds, 0, (int)(hi - lo), id) : list_known<int64_t>(glob, lo, hi, id);
+        return lds ? sorted_contains<int>(lds, 0, (int)(hi - lo), id) : sorted_contains<int64_t>(glob, lo, hi, id);
     }
 };
 

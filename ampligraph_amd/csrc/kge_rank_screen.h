@@ -238,6 +238,67 @@ struct ScreenArgs {
     int nblk;              // rank_screen_kernel_v1_wild: virtual blocks of the ordinary launch
 };
 
+// A wave's undecided outputs on their way to the recheck list: parked in the wave's LDS region (CAP pairs), handed to the list when it
+// is full -- one returning atomic and coalesced stores per flush: one atomic per wave and tile on the single counter (145 000 of them
+// at C2) serialised at the L2 and cost more than the matrix work.  An output is a bit of a lane's mark mask: output 2 r + ni (accumulator
+// register r, entity block ni) is bit 2 r + ni, or bit 31 - (2 r + ni) with MSB_FIRST (the order kernel r's slices shift the marks in).
+template <int CAP, bool MSB_FIRST>
+struct PendList {
+    int* counter;      // ScreenBufs: [0] pairs appended, [1] overflow flag
+    int2* pairs;
+    int64_t cap;
+    int2* pend;        // this wave's CAP pairs of LDS
+    int lane, l31;
+    int64_t row0;      // the lane's first query row: q0 + wq + 4 lh (C/D map: row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), col = lane & 31).
+                       // 64-bit as q0 is: narrowed here, the base costs rank_screen_kernel_v1 ten registers and 64 bytes of scratch
+    int npend = 0;     // pairs parked (wave-uniform)
+
+    // (query, candidate position) of mark bit `bit` of this lane in the tile whose first candidate is et
+    __device__ __forceinline__ int2 pair_of(int bit, int64_t et) const {
+        const int idx = MSB_FIRST ? 31 - bit : bit, r = idx >> 1, ni = idx & 1;
+        return make_int2((int)(row0 + (r & 3) + 8 * (r >> 2)), (int)(et + ni * 32 + l31));
+    }
+    // The list writes are issued as inline assembly and end with their own vmcnt(0): a store (or returning atomic) the compiler
+    // knows about, pending next to the stage loop's prefetch loads, makes it give up counting vmcnt -- the first wait of every
+    // stage became a vmcnt(0) on loads issued a moment earlier.  Memory operations it does not know about only make its waits
+    // stricter (vmcnt retires in order), never wrong.  (In kernel r the wait also drains the wave's DMA pieces: rare, and only stricter.)
+    __device__ __forceinline__ void flush() {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        int b0 = 0;
+        if (lane == 63) asm volatile("global_atomic_add %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)" : "=&v"(b0) : "v"(counter), "v"(npend) : "memory");
+        const int64_t base = __shfl(b0, 63, 64);
+        for (int i = lane; i < npend; i += 64) {
+            if (base + i < cap) {
+                const uint64_t v = *reinterpret_cast<const uint64_t*>(pend + i);
+                asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(pairs + base + i), "v"(v) : "memory");
+            } else {   // the list is full: the call falls back to the exact kernel
+                const int one = 1;
+                asm volatile("global_store_dword %0, %1, off" :: "v"(counter + 1), "v"(one) : "memory");
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        npend = 0;
+    }
+    // park the marked outputs of tile et of this wave; <= CAP of them
+    __device__ __forceinline__ void append(uint32_t msk, int64_t et) {
+        const int mine = __popc(msk);
+        const int incl = wave_incl_sum_i(mine, lane);
+        const int total = __shfl(incl, 63, 64);
+        if (!total) return;
+        if (npend + total > CAP) flush();
+        int at = npend + incl - mine;
+        while (msk) {
+            const int bit = __builtin_ctz(msk);
+            msk &= msk - 1;
+            pend[at++] = pair_of(bit, et);
+        }
+        npend += total;
+    }
+};
+
 constexpr int SCR_THREADS = 256;   // 4 waves, each a 32-query block against the workgroup's 64-entity tile; TWO workgroups per CU
 constexpr int SCR_ET = 64;         // entities per tile
 constexpr int SCR_PEND = 512;      // undecided pairs a wave parks in LDS before they go to the list
@@ -378,49 +439,7 @@ __device__ __forceinline__ void rank_screen_v1_body(const ScreenArgs& a, const i
     __syncthreads();
     int st = 0;
     int t = 0;   // tile of the current position
-    int npend = 0;   // pairs parked in this wave's LDS buffer (wave-uniform)
-    int2* const pend = reinterpret_cast<int2*>(em_s + SCR_ET) + wv * SCR_PEND;
-    // The list writes are issued as inline assembly and end with their own vmcnt(0): a store (or returning atomic) the compiler
-    // knows about, pending next to the stage loop's prefetch loads, makes it give up counting vmcnt -- the first wait of every
-    // stage became a vmcnt(0) on loads issued a moment earlier.  Memory operations it does not know about only make its waits
-    // stricter (vmcnt retires in order), never wrong.
-    auto flush = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        int b0 = 0;
-        if (lane == 63) asm volatile("global_atomic_add %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)" : "=&v"(b0) : "v"(a.b.counter), "v"(npend) : "memory");
-        const int64_t base = __shfl(b0, 63, 64);
-        for (int i = lane; i < npend; i += 64) {
-            if (base + i < a.b.cap) {
-                const uint64_t v = *reinterpret_cast<const uint64_t*>(pend + i);
-                asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(a.b.pairs + base + i), "v"(v) : "memory");
-            } else {   // the list is full: the call falls back to the exact kernel
-                const int one = 1;
-                asm volatile("global_store_dword %0, %1, off" :: "v"(a.b.counter + 1), "v"(one) : "memory");
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        npend = 0;
-    };
-    auto append = [&](uint32_t msk, int64_t et) {   // park the marked outputs (bit 2 r + ni of a lane) of this wave; <= SCR_PEND of them
-        const int mine = __popc(msk);
-        int incl = mine;   // inclusive prefix over the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int tt = __shfl_up(incl, o, 64); if (lane >= o) incl += tt; }
-        const int total = __shfl(incl, 63, 64);
-        if (!total) return;
-        if (npend + total > SCR_PEND) flush();
-        int at = npend + incl - mine;
-        while (msk) {
-            const int bit = __builtin_ctz(msk);
-            msk &= msk - 1;
-            const int r = bit >> 1, ni = bit & 1;
-            pend[at++] = make_int2((int)(q0 + wq + (r & 3) + 8 * (r >> 2) + 4 * lh), (int)(et + ni * 32 + l31));
-        }
-        npend += total;
-    };
+    PendList<SCR_PEND, false> pl{a.b.counter, a.b.pairs, a.b.cap, reinterpret_cast<int2*>(em_s + SCR_ET) + wv * SCR_PEND, lane, l31, q0 + wq + 4 * lh};
     auto stage = [&](auto par_c) __attribute__((always_inline)) {
         constexpr int P = decltype(par_c)::value;   // g % 2: this position's LDS buffer and query set, the register set free for g + 2
         const int64_t et = e_begin + t * SCR_ET;
@@ -498,11 +517,8 @@ __device__ __forceinline__ void rank_screen_v1_body(const ScreenArgs& a, const i
             undm &= rowmask;
             if (et + l31 >= e_end) undm &= 0xAAAAAAAAu;        // candidate of block 0 beyond the range
             if (et + 32 + l31 >= e_end) undm &= 0x55555555u;   // candidate of block 1 beyond the range
-            // Undecided pairs are parked in this wave's LDS buffer and go to the list when it is full (one returning atomic and
-            // coalesced stores per flush): one atomic per wave and tile on the single counter -- 145 000 of them at C2 --
-            // serialised at the L2 and cost more than the matrix work.
-            if (__popcll(__ballot(undm != 0u)) <= SCR_PEND / 32) append(undm, et);   // (<= 32 outputs per lane)
-            else for (int ps = 0; ps < 4; ++ps) append(undm & (0xFFu << (8 * ps)), et);   // (<= 8 per lane: 512 per wave)
+            if (__popcll(__ballot(undm != 0u)) <= SCR_PEND / 32) pl.append(undm, et);   // (<= 32 outputs per lane)
+            else for (int ps = 0; ps < 4; ++ps) pl.append(undm & (0xFFu << (8 * ps)), et);   // (<= 8 per lane: 512 per wave)
 #pragma unroll
             for (int lv = 0; lv < 3; ++lv)
 #pragma unroll
@@ -522,7 +538,7 @@ __device__ __forceinline__ void rank_screen_v1_body(const ScreenArgs& a, const i
         stage(std::integral_constant<int, 0>{});
         stage(std::integral_constant<int, 1>{});
     }
-    if (npend) flush();
+    if (pl.npend) pl.flush();
     // ---- per query row: sum over the 32 lanes that share it ----
 #pragma unroll
     for (int r = 0; r < 16; ++r) {

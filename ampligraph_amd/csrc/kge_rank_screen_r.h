@@ -199,52 +199,15 @@ __global__ __launch_bounds__(SCR_THREADS) __attribute__((amdgpu_waves_per_eu(1, 
     for (int r = 0; r < 16; ++r) { cntg[r] = 0; cnte[r] = 0; gmask[r] = 0u; emask[r] = 0u; }
     v16i32 acc[3][2];   // [level][entity block]: level 0 = l0 l0', 1 = l0 l1' + l1 l0', 2 = l0 l2' + l1 l1' + l2 l0'
 
-    int npend = 0;   // pairs parked in this wave's LDS buffer (wave-uniform)
-    int2* const pend = reinterpret_cast<int2*>(thr_s + 2 * 128) + wv * SCRR_PEND;
-    auto flush = [&]() {   // (inline assembly with its own vmcnt(0): it also drains this wave's DMA pieces -- rare, and only stricter)
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        int b0 = 0;
-        if (lane == 63) asm volatile("global_atomic_add %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)" : "=&v"(b0) : "v"(a.b.counter), "v"(npend) : "memory");
-        const int64_t base = __shfl(b0, 63, 64);
-        for (int i = lane; i < npend; i += 64) {
-            if (base + i < a.b.cap) {
-                const uint64_t v = *reinterpret_cast<const uint64_t*>(pend + i);
-                asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(a.b.pairs + base + i), "v"(v) : "memory");
-            } else {   // the list is full: the call falls back to the exact kernel
-                const int one = 1;
-                asm volatile("global_store_dword %0, %1, off" :: "v"(a.b.counter + 1), "v"(one) : "memory");
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        npend = 0;
-    };
-    auto append = [&](uint32_t msk, int64_t et) {   // park the marked outputs (bit 2 r + ni of a lane) of this wave; <= SCRR_PEND of them
-        const int mine = __popc(msk);
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int tt = __shfl_up(incl, o, 64); if (lane >= o) incl += tt; }
-        const int total = __shfl(incl, 63, 64);
-        if (!total) return;
-        if (npend + total > SCRR_PEND) flush();
-        int at = npend + incl - mine;
-        while (msk) {
-            const int bit = __builtin_ctz(msk);
-            msk &= msk - 1;
-            const int idx = 31 - bit, r = idx >> 1, ni = idx & 1;
-            pend[at++] = make_int2((int)(q0 + wq + (r & 3) + 8 * (r >> 2) + 4 * lh), (int)(et + ni * 32 + l31));
-        }
-        npend += total;
-    };
+    // the wave's undecided-pair list (kge_rank_screen.h; mark bit 31 - (2 r + ni))
+    PendList<SCRR_PEND, true> pl{a.b.counter, a.b.pairs, a.b.cap, reinterpret_cast<int2*>(thr_s + 2 * 128) + wv * SCRR_PEND, lane, l31, q0 + wq + 4 * lh};
 
     // The usual tile marks one or two outputs per WAVE (0.09 % of them at C2), and handing them over tile by tile -- a prefix sum over the
     // lanes (six dependent cross-lane steps) and a divergent loop, or a scalar walk over the marked lanes: either way a handful of VALU ->
     // SGPR round trips -- cost ~650 cycles per tile with the matrix pipe idle (profiles/r06y12_*: 51 us of the kernel's 712).  So a thread
     // parks its tile mask in LDS (one ds_write) and the wave hands over SCRR_UB tiles at a time: one prefix sum over the lanes' totals,
     // then every lane walks ITS marks (a handful of iterations for the wave).  A batch with more marks than the wave's parking buffer holds
-    // (wild rows, non-finite values) goes tile by tile through the compacting path above.
+    // (wild rows, non-finite values) goes tile by tile through PendList::append.
     uint32_t* const und_s = reinterpret_cast<uint32_t*>(smem_scr + SCRR_LDS_UND) + tid;   // [slot][thread]
     auto hand_over = [&](const int t0, const int cnt) {   // the marks of tiles t0 .. t0 + cnt - 1 of this block (slots 0 .. cnt - 1)
         int mine = 0;
@@ -255,22 +218,20 @@ __global__ __launch_bounds__(SCR_THREADS) __attribute__((amdgpu_waves_per_eu(1, 
             mine += __popc(v);
             nz |= v ? (1u << i) : 0u;
         }
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int tt = __shfl_up(incl, o, 64); if (lane >= o) incl += tt; }
+        const int incl = wave_incl_sum_i(mine, lane);
         const int total = __shfl(incl, 63, 64);
         if (!total) return;
         if (total > SCRR_PEND) {
             for (int i = 0; i < cnt; ++i) {
                 const uint32_t msk = und_s[i * 256];
                 const int64_t et = e_begin + (int64_t)(t0 + i) * SCR_ET;
-                if (__popcll(__ballot(msk != 0u)) <= SCRR_PEND / 32) append(msk, et);   // (<= 32 outputs per lane)
-                else for (int ps = 0; ps < 8; ++ps) append(msk & (0xFu << (4 * ps)), et);   // (<= 4 per lane: 256 per wave)
+                if (__popcll(__ballot(msk != 0u)) <= SCRR_PEND / 32) pl.append(msk, et);   // (<= 32 outputs per lane)
+                else for (int ps = 0; ps < 8; ++ps) pl.append(msk & (0xFu << (4 * ps)), et);   // (<= 4 per lane: 256 per wave)
             }
             return;
         }
-        if (npend + total > SCRR_PEND) flush();
-        int at = npend + incl - mine;
+        if (pl.npend + total > SCRR_PEND) pl.flush();
+        int at = pl.npend + incl - mine;
         uint32_t msk = 0u;
         int ti = 0;
         for (int left = mine; left > 0; --left) {   // (divergent: one mark of the lane per iteration, the next marked slot fetched when a mask runs out)
@@ -282,10 +243,9 @@ __global__ __launch_bounds__(SCR_THREADS) __attribute__((amdgpu_waves_per_eu(1, 
             msk = fresh ? ld : msk;
             const int bit = __builtin_ctz(msk);
             msk &= msk - 1u;
-            const int idx = 31 - bit, r = idx >> 1, ni = idx & 1;
-            pend[at++] = make_int2((int)(q0 + wq + (r & 3) + 8 * (r >> 2) + 4 * lh), (int)(e_begin + (int64_t)(t0 + ti) * SCR_ET + ni * 32 + l31));
+            pl.pend[at++] = pl.pair_of(bit, e_begin + (int64_t)(t0 + ti) * SCR_ET);
         }
-        npend += total;
+        pl.npend += total;
     };
 
     // this lane's 16 bytes inside a 1 KB piece: [half][row]
@@ -506,7 +466,7 @@ __global__ __launch_bounds__(SCR_THREADS) __attribute__((amdgpu_waves_per_eu(1, 
         one_tile(std::integral_constant<int, 1>{}, t + 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the positions requested past the end: their DMA must not outlive the workgroup's LDS
-    if (npend) flush();
+    if (pl.npend) pl.flush();
     // ---- per query row: sum over the 32 lanes that share it ----
     const int nbits = 2 * (((int)ntile + 1) & 15);   // bits gathered since the last count (the masks start at zero: the upper bits are clear)
 #pragma unroll

@@ -116,9 +116,7 @@ __global__ __launch_bounds__(GW * 64) void tile_direct_kernel(TileArgs a) {
         int carry = 0;
         for (int b = 0; b <= nrow; b += 64) {
             const int r = b + lane;
-            int v = (r <= nrow) ? rstart[r] : 0, s = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(s, o, 64); if (lane >= o) s += t; }
+            const int s = wave_incl_sum_i((r <= nrow) ? rstart[r] : 0, lane);
             if (r <= nrow) rstart[r] = carry + s;   // inclusive sum of the counts shifted by one == exclusive start
             carry += __shfl(s, 63, 64);
         }

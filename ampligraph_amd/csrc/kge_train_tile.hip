@@ -373,9 +373,7 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_backward_kernel(TileArgs a)
                 for (int c0 = 0; c0 < nchunk; c0 += 64) {
                     const int c = c0 + lane;
                     const int v = c < nchunk ? ccnt[c] : 0;
-                    int incl = v;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+                    const int incl = wave_incl_sum_i(v, lane);
                     if (c < nchunk) ccnt[c] = carry + incl - v;
                     carry += __shfl(incl, 63, 64);
                 }
