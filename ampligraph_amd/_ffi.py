@@ -171,6 +171,14 @@ EXT_SIGNATURES = {
     "amdkge_rank_lists": (C.c_int, [C.POINTER(Model), P, P, I64, P, I64, I32, P, P, P, I64, P, P, P, P, P, P, P, P]),
 }
 
+# the same for include/amdkge_negatives.h (training negative samplers): a table of its own, EXT_SIGNATURES stays what it was
+NEG_SIDE_MODES = {"uniform": 0, "bernoulli": 1, "s": 2, "o": 3}
+NEG_MAX_TRIES = 32
+NEG_SIGNATURES = {
+    "amdkge_sample_negatives": (C.c_int, [P, I64, I32, I64, I64, U64, U64, I64, I64, I32, P, P, I64, P, P, P, P, P, P, I32, P, P, P]),
+    "amdkge_negatives_side_thresholds": (C.c_int, [P, I64, P, I64, I64, I64, P, P]),
+}
+
 _lib = None
 
 
@@ -187,7 +195,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -140,6 +140,13 @@ class FilterIndex(_CsrIndex):
         evaluate() call does no per-triple host work.  triples_dev: (n,3) int32 device tensor; side "s" | "o"."""
         return self._device_filter(engine, triples_dev, "s" if side == "s" else "o")
 
+    def device_keys(self, engine):
+        """(po_keys, sp_keys) int64 device tensors of an index built on `engine`'s device: what the Bernoulli thresholds of the
+        training negative sampler count (amdkge_negatives_side_thresholds)."""
+        if self.__dict__.get("_dev", {}).get("device") != str(engine.device):
+            raise ValueError("FilterIndex.device_keys: the index was not built on this engine's device")
+        return self._dev["po_keys"], self._dev["sp_keys"]
+
     def as_lists(self, triples):
         """Materialise per-triple id arrays (what the reference yields as a RaggedTensor); tests only."""
         slo, shi = self.subject_ranges(triples)

@@ -410,6 +410,34 @@ class KgeEngine:
             int(step), int(row_offset), int(b_global), _ptr(out), _stream()))
         return out
 
+    def sample_negatives(self, triples, eta, seed, step, sample_base=0, sample_range=None, row_offset=0, b_global=0,
+                         side="uniform", side_thr=None, pool=None, s_filter=None, o_filter=None, max_tries=8, stats=None):
+        """amdkge_sample_negatives (include/amdkge_negatives.h has the draw): int32 [(B * eta), 3] corruptions of the int32 device
+        triples [B, 3], row j * B + i -- the neg_override of train_fwdbwd / train_step_tiled / cols_partial_scores.  side: "uniform" |
+        "bernoulli" (side_thr: uint32 thresholds per relation, held as an int32 tensor) | "s" | "o"; pool: int32 device ids the
+        replacements come from (validated by the caller) or None; s_filter / o_filter: (lo, hi, ids) of the B positives, both or
+        neither (FilterIndex.device_filter's form); stats: int64 [2] device tensor, += (redraws, exhausted).  The result lives in
+        the engine's buffer cache: the next call overwrites it."""
+        B = int(triples.shape[0])
+        if (s_filter is None) != (o_filter is None):
+            raise ValueError("sample_negatives: s_filter and o_filter are given together or not at all")
+        out = self._buf("negatives", (B * int(eta), 3), torch.int32)
+        sf, of = s_filter or (None, None, None), o_filter or (None, None, None)
+        check(self.lib.amdkge_sample_negatives(
+            _ptr(triples), B, int(eta), int(sample_base), int(sample_range or self.n_ents), int(seed), int(step), int(row_offset),
+            int(b_global), _ffi.NEG_SIDE_MODES[side], _ptr(side_thr), _ptr(pool), 0 if pool is None else int(pool.numel()),
+            _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]), int(max_tries), _ptr(stats), _ptr(out), _stream()))
+        return out
+
+    def negatives_side_thresholds(self, po_keys, sp_keys, n_ents=None, n_rels=None):
+        """amdkge_negatives_side_thresholds: the Bernoulli thresholds floor(2^32 G_po / (G_sp + G_po)) per relation from a
+        FilterIndex's two int64 device key arrays -> int32 device tensor [n_rels] holding the uint32 bit patterns."""
+        n_rels = self.n_rels if n_rels is None else int(n_rels)
+        thr = torch.empty(n_rels, dtype=torch.int32, device=self.device)
+        check(self.lib.amdkge_negatives_side_thresholds(_ptr(po_keys), int(po_keys.numel()), _ptr(sp_keys), int(sp_keys.numel()),
+                                                        int(self.n_ents if n_ents is None else n_ents), n_rels, _ptr(thr), _stream()))
+        return thr
+
     def _filter_build(self, triples, side, n_ents, n_rels):
         """One CSR filter index from the concatenated id triples (int32 [m,3] device tensor) -> (keys int64 [n_groups], start
         int64 [n_groups + 1], ids int32 [n_unique]) device tensors.  side "s" | "o": amdkge_filter_build; None: the (s, o) pair

@@ -75,6 +75,7 @@ class ScoringBasedEmbeddingModel:
         self._sharding = "replicated"
         self._sharded_negatives = "local"
         self._deterministic = False
+        self._negatives = None       # compile(negatives=...): latent_features/negatives.py
         self._dist_override = None   # tests: an object with the torch.distributed collective surface
 
     @property
@@ -110,7 +111,10 @@ class ScoringBasedEmbeddingModel:
         [entity_init, relation_init]; regularizer: None | 'LP'/'l1'/'l2'/'l3' | LPRegularizer | pair.
 
         Extra keywords of this engine: optimizer_mode="dense" (default, the reference's semantics) | "lazy" (touched rows
-        only; see amdkge_opt.lazy); deterministic=True: bitwise reproducible training (AMDKGE_TILED_DETERMINISTIC).  Multi-GPU, one process per GPU under torch.distributed:
+        only; see amdkge_opt.lazy); deterministic=True: bitwise reproducible training (AMDKGE_TILED_DETERMINISTIC);
+        negatives=None (the train kernels' own draw: a fair coin for the side, a uniform entity) | NegativeSampling | a dict of its
+        keywords {"filter", "side", "entities", "max_tries"} (latent_features/negatives.py: rejection of known statements, Bernoulli
+        side choice, an entity pool; replicated tables only; model.negative_sampling_stats_ after fit()).  Multi-GPU, one process per GPU under torch.distributed:
         entity_sharding="replicated" (default: tables replicated, gradient all-reduce) | "rows" (entity table
         row-sharded over the ranks, ampligraph_amd/sharded.py; sharded_negatives="local" | "global" chooses where its corruptions
         are drawn from) | "columns" (tables that fit every GPU: rank r TRAINS on k / W units of every row and the whole batch, one
@@ -128,6 +132,12 @@ class ScoringBasedEmbeddingModel:
             raise ValueError("entity_sharding must be 'replicated', 'rows' or 'columns'")
         if self._sharded_negatives not in ("local", "global"):
             raise ValueError("sharded_negatives must be 'local' or 'global'")
+        from .negatives import NegativeSampling
+
+        self._negatives = NegativeSampling.get(kwargs.pop("negatives", None))
+        if self._negatives is not None and self._sharding != "replicated":
+            raise NotImplementedError("negatives: the row- and column-sharded step loops (entity_sharding='rows' / 'columns') build "
+                                      "their own corruption overrides and do not take a negative sampler; use replicated tables")
         self.optimizer = optimizers.get(optimizer)
         if optimizer_mode == "lazy":
             # DEVIATION from the reference (its optimizer is dense, optimizers.py:136-168): only rows that received a
@@ -252,6 +262,16 @@ class ScoringBasedEmbeddingModel:
             loop.configure_for_data(Xi, batch_size)
         train = torch.as_tensor(np.ascontiguousarray(Xi, dtype=np.int32)).to(eng.device)
         n = int(train.shape[0])
+        # the negative sampler is bound here, where the id map and the training tensor exist: filter index, the ranges of all n
+        # rows, thresholds and pool are made once; a step slices them (negatives.BoundNegatives).  Only trainer.StepLoop has the
+        # sampler attribute: ShardedStepLoop.negatives is that loop's own "local" | "global" setting and is never touched here
+        # (compile() refuses a sampler on sharded tables)
+        from ..trainer import StepLoop
+
+        if type(loop) is StepLoop:
+            loop.negatives = None if self._negatives is None else self._negatives.bind(self, eng, train)
+        elif self._negatives is not None:
+            raise NotImplementedError("negatives: only the replicated step loop takes a negative sampler")
         focus_dev = None
         if focus_w is not None:
             if focus_w.shape[0] != n:
@@ -317,6 +337,8 @@ class ScoringBasedEmbeddingModel:
             if self.stop_training:
                 break
         self._placement.publish()
+        if hasattr(getattr(loop, "negatives", None), "stats"):
+            self.negative_sampling_stats_ = loop.negatives.stats()   # {"redraws", "exhausted"} of this fit(): one read-back
         for cb in cbs:
             if hasattr(cb, "on_train_end"):
                 cb.on_train_end()

@@ -1,0 +1,123 @@
+"""Training negative samplers: compile(negatives=...).
+
+Without the setting every corruption is drawn inside the train kernels: a fair coin for the side, a uniform entity id
+(draw_corruption, kge_device.h).  `NegativeSampling` describes the three things that rule lacks -- rejection of KNOWN statements
+(PyKEEN / LibKGE / DGL-KE's filtered negatives), the per-relation Bernoulli side choice of TransH, and a caller's pool of
+replacement entities (AmpliGraph 1.x's negative_corruption_entities) -- and `bind()` turns it, once per fit(), into a
+`BoundNegatives`: the object trainer.StepLoop calls each step.  It runs amdkge_sample_negatives (kge_negatives.hip; the draw is
+defined in include/amdkge_negatives.h) and hands the rows to the train step as its neg_override: the train kernels and the loss are
+the ones of the default path.
+"""
+import numpy as np
+
+from .. import _ffi
+from ..datasets.filters import FilterIndex
+
+
+class NegativeSampling:
+    """filter: False (no rejection) | True (a corruption that is a TRAINING triple is redrawn) | dict of datasets, in the form
+    evaluate(use_filter=...) takes (their triples are known statements too, next to the training set; rows with labels the
+    training set does not hold are dropped).
+    side: "uniform" (a fair coin per corruption) | "bernoulli" (the subject with probability tph / (tph + hpt) of the
+    positive's relation, Wang et al. 2014) | "s" | "o" (always that side).
+    entities: None (every entity) or the labels of the entities replacements are drawn from.
+    max_tries: draws per corruption before the last rejected one is kept (1 .. 32; 1 with a filter only counts)."""
+
+    def __init__(self, filter=False, side="uniform", entities=None, max_tries=8):
+        if not (isinstance(filter, (bool, np.bool_)) or (isinstance(filter, dict) and len(filter) > 0)):
+            raise ValueError("negatives: `filter` must be False, True or a non-empty dict of datasets")
+        if not isinstance(side, str) or side not in _ffi.NEG_SIDE_MODES:
+            raise ValueError("negatives: `side` must be 'uniform', 'bernoulli', 's' or 'o', got {!r}".format(side))
+        if isinstance(max_tries, bool) or not isinstance(max_tries, (int, np.integer)) or not 1 <= int(max_tries) <= _ffi.NEG_MAX_TRIES:
+            raise ValueError("negatives: `max_tries` must be an integer in [1, {}]".format(_ffi.NEG_MAX_TRIES))
+        if entities is not None:
+            if isinstance(entities, (str, bytes)) or np.ndim(entities) != 1 or len(entities) < 1:
+                raise ValueError("negatives: `entities` must be None or a non-empty 1-D sequence of entity labels")
+            entities = np.asarray(entities)
+        self.filter = filter if isinstance(filter, dict) else bool(filter)
+        self.side, self.entities, self.max_tries = side, entities, int(max_tries)
+
+    @classmethod
+    def get(cls, spec):
+        """compile()'s `negatives` argument -> None or a sampler: None, a NegativeSampling (or anything with .bind()), a dict of its keywords."""
+        if spec is None or hasattr(spec, "bind"):
+            return spec
+        if isinstance(spec, dict):
+            unknown = set(spec) - {"filter", "side", "entities", "max_tries"}
+            if unknown:
+                raise ValueError("negatives: unknown keys {}".format(sorted(unknown)))
+            return cls(**spec)
+        raise ValueError("negatives must be None, a dict or a NegativeSampling")
+
+    def get_config(self):
+        """The constructor arguments (datasets and labels as given)."""
+        return {"filter": self.filter, "side": self.side, "entities": self.entities, "max_tries": self.max_tries}
+
+    def bind(self, model, engine, train):
+        """train: the int32 device tensor [n, 3] of id triples fit() slices its batches from -> BoundNegatives."""
+        import torch
+
+        N, R = int(model._n_ents), int(model._n_rels)
+        pool = None
+        if self.entities is not None:
+            ids = np.asarray(model.data_indexer.get_indexes(self.entities, "e"), dtype=np.int64)
+            if ids.shape[0] != self.entities.shape[0]:
+                raise ValueError("negatives: {} of the `entities` are not in the training set".format(self.entities.shape[0] - ids.shape[0]))
+            if ids.min() < 0 or ids.max() >= N:   # the train kernels do not check override ids
+                raise ValueError("negatives: entity ids outside [0, {})".format(N))
+            pool = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32)).to(engine.device)
+        index = None
+        if self.filter is not False or self.side == "bernoulli":
+            extra = []
+            if isinstance(self.filter, dict):
+                from .models import _load_triples
+
+                extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in self.filter.values()]
+            index = FilterIndex([train] + extra, N, R, engine=engine)
+        return BoundNegatives(engine, train, index, self.side, pool, self.max_tries, reject=self.filter is not False)
+
+
+class BoundNegatives:
+    """A sampler bound to one fit(): the FilterIndex over the training set (and the filter datasets), the four range arrays of ALL
+    training rows -- two range lookups at bind time; a batch is then a slice of them, no lookup kernel runs per step --, the
+    Bernoulli thresholds, the pool tensor and the stats tensor.
+
+    Called by trainer.StepLoop.step as negatives(global_batch, lo, hi, eta, seed, step) -> int32 device rows [(hi - lo) * eta, 3],
+    the corruptions of rows [lo, hi) of the global batch, keyed by the GLOBAL row (row_offset = lo, b_global = the batch's size):
+    every rank of a data-parallel run draws its own slice of the same rows."""
+
+    def __init__(self, engine, train, index, side, pool, max_tries, reject):
+        self.engine, self.train, self.index = engine, train, index
+        self.side, self.pool, self.max_tries = side, pool, int(max_tries)
+        import torch
+
+        self.stats_dev = torch.zeros(2, dtype=torch.int64, device=engine.device)
+        self.s_filter = self.o_filter = self.side_thr = None
+        if index is not None and reject:
+            self.s_filter = index.device_filter(engine, train, "s")
+            self.o_filter = index.device_filter(engine, train, "o")
+        if side == "bernoulli":
+            self.side_thr = engine.negatives_side_thresholds(*index.device_keys(engine), index.n_ents, index.n_rels)
+
+    def _first_row(self, batch):
+        """the training row `batch` starts at: fit()'s batches are row slices of the tensor this sampler was bound to"""
+        t = self.train
+        if batch.untyped_storage().data_ptr() != t.untyped_storage().data_ptr() or batch.dtype != t.dtype or not batch.is_contiguous():
+            raise ValueError("negatives: the batch is not a row slice of the training tensor this sampler was bound to")
+        off = batch.storage_offset() - t.storage_offset()
+        if off < 0 or off % 3 or off // 3 + int(batch.shape[0]) > int(t.shape[0]):
+            raise ValueError("negatives: the batch is not a row slice of the training tensor this sampler was bound to")
+        return off // 3
+
+    def __call__(self, global_batch, lo, hi, eta, seed, step):
+        r0 = self._first_row(global_batch) + int(lo)
+        r1 = r0 + int(hi) - int(lo)
+        cut = lambda f: None if f is None else (f[0][r0:r1], f[1][r0:r1], f[2])   # noqa: E731
+        return self.engine.sample_negatives(global_batch[lo:hi], eta, seed, step, row_offset=lo, b_global=int(global_batch.shape[0]),
+                                            side=self.side, side_thr=self.side_thr, pool=self.pool, s_filter=cut(self.s_filter),
+                                            o_filter=cut(self.o_filter), max_tries=self.max_tries, stats=self.stats_dev)
+
+    def stats(self):
+        """{"redraws", "exhausted"} since the bind: one device read (synchronises the stream)."""
+        rd, ex = (int(v) for v in self.stats_dev.tolist())
+        return {"redraws": rd, "exhausted": ex}

@@ -123,6 +123,10 @@ class StepLoop:
         # read once here.  Needs the owner-computes path (any k <= 2048); the merged DP sweep already sums in rank order.
         self.deterministic = os.environ.get("AMDKGE_DETERMINISTIC", "0") == "1"
         self.kernel_hook = None   # bench.py: callable(i) recording HIP events at the phase boundaries (PHASES)
+        # compile(negatives=...): None (the train kernels draw their own corruptions) or a callable(global_batch, lo, hi, eta, seed,
+        # rng_step) -> int32 device rows [(hi - lo) * eta, 3], the corruptions of rows [lo, hi) of the global batch drawn by GLOBAL
+        # row (latent_features/negatives.py: BoundNegatives), which the step hands to the train kernels as their override
+        self.negatives = None
         engine.prepare_training(optimizer.name)
         if hasattr(optimizer, "bind"):
             optimizer.bind(engine)   # get_weights() / set_weights() of the wrapper read and write the engine's state tensors
@@ -175,14 +179,16 @@ class StepLoop:
             raise ValueError("deterministic mode needs the owner-computes train path (k <= 2048)")
         if self.kernel_hook is not None:
             self.kernel_hook(0)
+        # (the override keyword is only passed when a sampler is set: backends without it keep working)
+        neg = {"neg_override": self.negatives(global_batch, lo, hi, self.eta, self.seed, rng_step)} if self.negatives is not None and hi > lo else {}
         if tiled:
             eng.train_step_tiled(global_batch[lo:hi], self.eta, self.loss_ffi, opt_ffi, self.seed, rng_step,
                                  reg_e=lam, reg_r=lam_r, row_offset=lo, b_global=bg, grad_only=self.multi,
-                                 pos_atomic=self.pos_atomic,
+                                 pos_atomic=self.pos_atomic, **neg,
                                  **({"deterministic": True, **({"det_wide": True} if getattr(self, "det_wide", False) else {})} if self.deterministic else {}))
         elif hi > lo:
             eng.train_fwdbwd(global_batch[lo:hi], self.eta, self.loss_ffi, self.seed, rng_step,
-                             row_offset=lo, b_global=bg)
+                             row_offset=lo, b_global=bg, **neg)
         if self.kernel_hook is not None:
             self.kernel_hook(1)
         if self.multi and self.merge == "sharded":
