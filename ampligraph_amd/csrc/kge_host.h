@@ -37,6 +37,46 @@ inline int ensure_dynamic_lds(PerDeviceOnce& once, std::initializer_list<const v
     return set_error_hip(err, where);
 }
 
+// How many blocks of a PERSISTENT kernel the calling thread's current device holds at once: compute units x
+// hipOccupancyMaxActiveBlocksPerMultiprocessor at the launch's dynamic LDS size.  One object per kernel instantiation; the answers are
+// kept per device ordinal (mod 64, as PerDeviceOnce) and LDS size, RESIDENT_SIZES sizes per device (a process that trains two models,
+// or one with two values of eta, alternates between two), each in one 64-bit word next to the size it belongs to -- threads on
+// different devices share the object, and a step whose shape was seen before asks nothing.  A fifth size takes the place of an older
+// one (and is asked again when that one returns).  Neither query touches a stream: both are safe while a graph is being captured.
+constexpr int RESIDENT_SIZES = 4;
+struct ResidentBlocks {
+    unsigned long long slot[64][RESIDENT_SIZES] = {};   // (dynamic LDS bytes + 1) << 32 | blocks; 0: free
+};
+inline int resident_blocks(ResidentBlocks& r, const void* kernel, int block_threads, size_t dyn_lds, const char* what, int& blocks) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    unsigned long long* words = r.slot[dev & 63];
+    int put = (int)((dyn_lds >> 3) % RESIDENT_SIZES);   // (all taken: the size's own place)
+    for (int e = RESIDENT_SIZES - 1; e >= 0; --e) {
+        const unsigned long long have = __atomic_load_n(&words[e], __ATOMIC_ACQUIRE);
+        if ((have >> 32) == (unsigned long long)dyn_lds + 1) { blocks = (int)(have & 0xFFFFFFFFull); return AMDKGE_OK; }
+        if (have == 0) put = e;
+    }
+    unsigned long long& word = words[put];
+    int per_cu = 0, cus = 0;
+    char where[96];
+    if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, dyn_lds); e != hipSuccess) {
+        snprintf(where, sizeof(where), "hipOccupancyMaxActiveBlocksPerMultiprocessor(%s)", what);
+        return set_error_hip(e, where);
+    }
+    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) {
+        snprintf(where, sizeof(where), "hipDeviceGetAttribute(%s)", what);
+        return set_error_hip(e, where);
+    }
+    if (per_cu < 1 || cus < 1) {
+        snprintf(where, sizeof(where), "%s: the device holds no block of this kernel with %zu bytes of LDS", what, dyn_lds);
+        return set_error(AMDKGE_EINVAL, where);
+    }
+    blocks = per_cu * cus;
+    __atomic_store_n(&word, ((unsigned long long)dyn_lds + 1) << 32 | (unsigned)blocks, __ATOMIC_RELEASE);
+    return AMDKGE_OK;
+}
+
 // The session layers allocate on the host (staging vectors, the per-device threads of a group, the registries): those can throw,
 // the C ABI cannot.  Their entry points are function-try-blocks closed by KGE_CATCH("name").
 #define KGE_CATCH(NAME)                                                                                              \

@@ -13,11 +13,19 @@ static int launch_forward_v(TrainArgs& f, hipStream_t st) {
     size_t shmem = (size_t)slots * slot_lds_bytes(f.eta, W) + slots * sizeof(double) + (W == 1 ? 4 : 1) * (size_t)f.K * 4;
     f.sign_off = (int)shmem;
     if (W != 1 || CHF != 1) shmem += sign_stash_bytes(MODEL, f.eta, CHF);   // (one wave per positive, one quad per lane: TransE takes the single-pass form, no stash)
+    if (forward_spo_lds(MODEL, true, W, CHF)) shmem += (size_t)FWD_WAVES * 3 * f.K * 4;   // the waves' copies of s, p, o (behind the transpose rows: no stash in this geometry)
     if (shmem > 64 * 1024) {
         static PerDeviceOnce attr;
         if (int rc = ensure_dynamic_lds(attr, {(const void*)train_fwdbwd_kernel<MODEL, 4, W, CHF, true, DET>}, 160 * 1024, "train_forward_stage")) return rc;
     }
-    const unsigned grid = KGE_DBG(f, 8192) ? 0u : (unsigned)((f.B + slots - 1) / slots);   // (ablation 8192: no forward launch)
+    unsigned grid = KGE_DBG(f, 8192) ? 0u : (unsigned)((f.B + slots - 1) / slots);   // (ablation 8192: no forward launch)
+    if (forward_persistent(MODEL, true, W)) {
+        // persistent waves: no more blocks than the device holds at once
+        static ResidentBlocks resident;
+        int cap = 0;
+        if (int rc = resident_blocks(resident, (const void*)train_fwdbwd_kernel<MODEL, 4, W, CHF, true, DET>, 256, shmem, "train_forward_stage", cap)) return rc;
+        if (grid > (unsigned)cap) grid = (unsigned)cap;
+    }
     if (grid) hipLaunchKernelGGL((train_fwdbwd_kernel<MODEL, 4, W, CHF, true, DET>), dim3(grid), dim3(256), shmem, st, f);
     return check_launch("train_forward_stage");
 }
