@@ -179,6 +179,14 @@ NEG_SIGNATURES = {
     "amdkge_negatives_side_thresholds": (C.c_int, [P, I64, P, I64, I64, I64, P, P]),
 }
 
+# include/amdkge_shared.h (shared-negative training): again a table of its own.  The side modes are NEG_SIDE_MODES.
+SHARED_MAX_NEGS = (1 << 24) - 1
+SHARED_SIGNATURES = {
+    "amdkge_sample_shared": (C.c_int, [P, I64, I64, I32, I64, I64, U64, U64, I32, P, P, I64, P, P, P]),
+    "amdkge_train_shared_workspace_bytes": (I64, [C.POINTER(Model), I64, I64, I32]),
+    "amdkge_train_shared_fwdbwd": (C.c_int, [C.POINTER(Model), C.POINTER(Loss), P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P, P]),
+}
+
 _lib = None
 
 
@@ -195,7 +203,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(SHARED_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

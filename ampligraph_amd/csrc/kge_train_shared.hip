@@ -1,0 +1,431 @@
+// Shared-negative training (include/amdkge_shared.h): the G positives of a group share one list of M replacement entities, so the
+// group's G x M corruption scores are ONE fp32 matrix product of its query vectors with the M gathered rows, and both gradients are
+// matrix products too.  The step is DEFINED in the header as amdkge_train_fwdbwd's on the equivalent override rows; tests/shared_ref.py
+// restates the draw and that equivalence in numpy.
+//   shared_draw_kernel  : ids [n_groups, M] and sides [B], one Philox block per value (the draw of the header).
+//   shared_query_kernel : a wave per positive.  q_i = s*p or p*o (DistMult), the a|b halves of survey row a9 (ComplEx / HolE), built
+//                         for the positive's OWN side; the positive's raw score <q_i, own_i> falls out of the same pass.
+//   shared_gemm_kernel  : v_mfma_f32_32x32x2_f32 (exact fp32), a 64 x 64 tile per workgroup, a 32 x 32 accumulator per wave, operands
+//                         staged through LDS in chunks of 32 along the contraction.  Three MODES share the tile loop and differ in
+//                         where an operand element comes from and where a result goes:
+//                           FWD : S_g  = Q_g E^T     (G x K by K x M)   E gathered by id          -> the score buffer [rows, M]
+//                           DQ  : dQ_g = C_g E       (G x M by M x K)   E gathered by id          -> dQ [B, K]
+//                           DE  : dE   = C_g^T Q_g   (M x G by G x K)   C read transposed         -> atomic row-adds into d_grad_ent
+//                         Elements past a matrix edge are staged as zeros, so every tile shape is one code path.
+//   shared_loss_kernel  : a wave per positive walks loss_call (kge_loss.h) over its row of the score buffer: scores -> dL/dscore in
+//                         place.  The buffer holds the plain sums; HolE's 2/k is applied where a score is loaded (the reference's
+//                         rounding: reduce_sum, then scale) and again where a coefficient is stored (the chain rule through it).
+//   shared_chain_kernel : a wave per positive.  With t_i = dQ_i + c_pos own_i = dL/dq_i, the gradients of the two kept rows are the
+//                         transpose of the query map applied to t_i, that of the replaced row's original is c_pos q_i; three
+//                         atomic row-adds per positive.
+// Groups are processed in chunks of at most CHUNK_SCORES scores, so the score buffer is bounded whatever B * M is.
+#include "kge_host.h"
+#include "kge_loss.h"
+#include "../../include/amdkge_shared.h"
+
+namespace kge {
+
+constexpr uint32_t SHARED_TAG_IDS = 0xF0u << 24, SHARED_TAG_SIDE = 0xF1u << 24;
+constexpr int64_t CHUNK_SCORES = 1ll << 24;
+
+struct SharedDrawArgs {
+    const int32_t* triples;
+    int64_t B, G, n_groups;
+    int M;
+    int64_t base;
+    uint32_t range, seed_lo, seed_hi, step_lo, step_hi;
+    int side_mode;
+    const uint32_t* side_thr;
+    const int32_t* pool;
+    uint32_t pool_n;
+    int32_t* ids;
+    int32_t* side;
+};
+
+__global__ __launch_bounds__(256) void shared_draw_kernel(SharedDrawArgs a) {
+    const int64_t n_ids = a.n_groups * a.M;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n_ids) {
+        const uint32_t g = (uint32_t)(t / a.M), j = (uint32_t)(t % a.M);
+        const u32x4 r = philox4x32_10(g, j | SHARED_TAG_IDS, a.step_lo, a.step_hi, a.seed_lo, a.seed_hi);
+        a.ids[t] = a.pool ? a.pool[__umulhi(r.x, a.pool_n)] : (int)(a.base + (int64_t)__umulhi(r.x, a.range));
+    } else if (t < n_ids + a.B) {
+        const uint64_t i = (uint64_t)(t - n_ids);
+        bool subj;
+        if (a.side_mode == AMDKGE_NEG_SIDE_S_ONLY) subj = true;
+        else if (a.side_mode == AMDKGE_NEG_SIDE_O_ONLY) subj = false;
+        else {
+            const u32x4 r = philox4x32_10((uint32_t)i, (uint32_t)(i >> 32) | SHARED_TAG_SIDE, a.step_lo, a.step_hi, a.seed_lo, a.seed_hi);
+            subj = a.side_mode == AMDKGE_NEG_SIDE_BERNOULLI ? r.x < a.side_thr[a.triples[3 * i + 1]] : (r.x & 1u) == 0u;
+        }
+        a.side[i] = subj ? 1 : 0;
+    }
+}
+
+// ---- query vectors ------------------------------------------------------------------------------------------------------------------
+template <bool CPLX>
+__global__ __launch_bounds__(256) void shared_query_kernel(const float* __restrict__ ent, const float* __restrict__ rel, const int32_t* __restrict__ triples,
+                                                           const int32_t* __restrict__ side, int64_t B, int ks, float* __restrict__ Q, float* __restrict__ pos_raw) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= B) return;   // (wave-uniform; the kernel has no barrier)
+    const int K = CPLX ? 2 * ks : ks;
+    const bool subj = side[i] != 0;
+    const float* S = ent + (int64_t)triples[3 * i] * K;
+    const float* P = rel + (int64_t)triples[3 * i + 1] * K;
+    const float* O = ent + (int64_t)triples[3 * i + 2] * K;
+    const float* own = subj ? S : O;
+    float* q = Q + i * K;
+    float acc = 0.f;
+    for (int u = lane; u < ks; u += 64) {
+        if constexpr (CPLX) {
+            const float p0 = P[u], p1 = P[ks + u];
+            float q0, q1;
+            if (subj) {   // score = <(p0 o0 + p1 o1, p0 o1 - p1 o0), s>
+                const float o0 = O[u], o1 = O[ks + u];
+                q0 = p0 * o0 + p1 * o1; q1 = p0 * o1 - p1 * o0;
+            } else {      // score = <(s0 p0 - s1 p1, s0 p1 + s1 p0), o>
+                const float s0 = S[u], s1 = S[ks + u];
+                q0 = s0 * p0 - s1 * p1; q1 = s0 * p1 + s1 * p0;
+            }
+            q[u] = q0; q[ks + u] = q1;
+            acc += q0 * own[u] + q1 * own[ks + u];
+        } else {
+            const float qq = P[u] * (subj ? O[u] : S[u]);
+            q[u] = qq;
+            acc += qq * own[u];
+        }
+    }
+    acc = wave_sum_shfl(acc);
+    if (lane == 0) pos_raw[i] = acc;
+}
+
+// ---- the three matrix products ------------------------------------------------------------------------------------------------------
+enum { GEMM_FWD = 0, GEMM_DQ = 1, GEMM_DE = 2 };
+constexpr int GT = 64;        // tile edge
+constexpr int GKC = 32;       // contraction chunk
+constexpr int GLD = GT + 1;   // LDS row stride: a chunk staged along the contraction lands on distinct banks
+
+struct SharedGemmArgs {
+    const float* ent;
+    const int32_t* ids;   // [n_groups, M]
+    float* Q;             // [B, K]
+    float* S;             // [rows of the chunk, M]: scores, then dL/dscore
+    float* dQ;            // [B, K]
+    float* g_ent;
+    int64_t B, G;
+    int M, K;
+    int64_t g0;           // first group of the chunk (row0 = g0 * G)
+    int tiles_m, tiles_n;
+};
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+template <int MODE>
+__global__ __launch_bounds__(256) void shared_gemm_kernel(SharedGemmArgs a) {
+    __shared__ float As[GKC][GLD];
+    __shared__ float Bs[GKC][GLD];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int per_group = a.tiles_m * a.tiles_n;
+    const int64_t g = a.g0 + blockIdx.x / per_group;
+    const int tile = blockIdx.x % per_group;
+    const int m0 = (tile / a.tiles_n) * GT, n0 = (tile % a.tiles_n) * GT;
+    const int64_t row_first = g * a.G;                                         // the group's first positive
+    const int Gg = (int)((a.B - row_first) < a.G ? (a.B - row_first) : a.G);   // its positives
+    const int64_t srow = row_first - a.g0 * a.G;                               // its first row in the score buffer
+    const int mdim = MODE == GEMM_DE ? a.M : Gg;
+    const int ndim = MODE == GEMM_FWD ? a.M : a.K;
+    const int kdim = MODE == GEMM_FWD ? a.K : (MODE == GEMM_DQ ? a.M : Gg);
+    if (m0 >= mdim) return;   // (the last, short group: uniform over the workgroup)
+    const int32_t* gid = a.ids + g * a.M;
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+    for (int k0 = 0; k0 < kdim; k0 += GKC) {
+        // ---- stage A[m][kk] ----
+        if (MODE == GEMM_DE) {   // contiguous along m: C[kk][m]
+            const int mm = tid & 63;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int kk = (tid >> 6) + 4 * r;
+                float v = 0.f;
+                if (m0 + mm < mdim && k0 + kk < kdim) v = a.S[(srow + k0 + kk) * a.M + (m0 + mm)];
+                As[kk][mm] = v;
+            }
+        } else {                 // contiguous along the contraction: Q[m][kk] / C[m][kk]
+            const int kk = tid & 31;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int mm = (tid >> 5) + 8 * r;
+                float v = 0.f;
+                if (m0 + mm < mdim && k0 + kk < kdim)
+                    v = MODE == GEMM_FWD ? a.Q[(row_first + m0 + mm) * a.K + (k0 + kk)] : a.S[(srow + m0 + mm) * a.M + (k0 + kk)];
+                As[kk][mm] = v;
+            }
+        }
+        // ---- stage B[kk][n] ----
+        if (MODE == GEMM_FWD) {  // contiguous along the contraction: E[id_n][kk]
+            const int kk = tid & 31;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int nn = (tid >> 5) + 8 * r;
+                float v = 0.f;
+                if (n0 + nn < ndim && k0 + kk < kdim) v = a.ent[(int64_t)gid[n0 + nn] * a.K + (k0 + kk)];
+                Bs[kk][nn] = v;
+            }
+        } else {                 // contiguous along n: E[id_kk][n] / Q[kk][n]
+            const int nn = tid & 63;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int kk = (tid >> 6) + 4 * r;
+                float v = 0.f;
+                if (n0 + nn < ndim && k0 + kk < kdim)
+                    v = MODE == GEMM_DQ ? a.ent[(int64_t)gid[k0 + kk] * a.K + (n0 + nn)] : a.Q[(row_first + k0 + kk) * a.K + (n0 + nn)];
+                Bs[kk][nn] = v;
+            }
+        }
+        __syncthreads();
+        const int wm = (wv & 1) * 32 + (lane & 31), wn = (wv >> 1) * 32 + (lane & 31), kh = lane >> 5;
+#pragma unroll
+        for (int kk = 0; kk < GKC; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + kh][wm], Bs[kk + kh][wn], acc, 0, 0, 0);
+        __syncthreads();
+    }
+    // ---- results: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31 of the wave's 32 x 32 ----
+    const int col = n0 + (wv >> 1) * 32 + (lane & 31);
+    if (col >= ndim) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = m0 + (wv & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (row >= mdim) continue;
+        const float v = acc[r];
+        if (MODE == GEMM_FWD) a.S[(srow + row) * a.M + col] = v;
+        else if (MODE == GEMM_DQ) a.dQ[(row_first + row) * a.K + col] = v;
+        else if (v != 0.f) atomic_add_f32(a.g_ent + (int64_t)gid[row] * a.K + col, v);   // (true for NaN; zeros -- the padding units -- add nothing)
+    }
+}
+
+// ---- Loss.__call__ on a positive's row of the score buffer --------------------------------------------------------------------------
+struct SharedWalk {
+    float* s;
+    int lane;
+    float scale;
+    __device__ __forceinline__ int first() const { return lane; }
+    __device__ __forceinline__ int stride() const { return KGE_WAVE; }
+    __device__ __forceinline__ float load(int j) const { return scale * s[j]; }
+    __device__ __forceinline__ void store(int j, float v) const { s[j] = v * scale; }
+    __device__ __forceinline__ float sum(float v) const { return wave_sum(v); }
+    __device__ __forceinline__ float max(float v) const { return wave_max(v); }
+};
+
+__global__ __launch_bounds__(256) void shared_loss_kernel(float* __restrict__ S, const float* __restrict__ pos_raw, float* __restrict__ cpos, int64_t row0, int64_t rows,
+                                                          int64_t B, int M, amdkge_loss L, float scale, double* loss_sum, float* pos_scores, float* neg_scores) {
+    __shared__ double s_loss[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    double tot = 0.0;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wv; r < rows; r += (int64_t)gridDim.x * 4) {   // (wave-uniform)
+        const int64_t i = row0 + r;
+        float* s = S + r * M;
+        const float P = scale * pos_raw[i];
+        if (neg_scores)
+            for (int j = lane; j < M; j += 64) neg_scores[(int64_t)j * B + i] = scale * s[j];
+        float per, dP;
+        loss_call(L, P, M, SharedWalk{s, lane, scale}, per, dP);
+        if (lane == 0) {
+            cpos[i] = dP * scale;
+            if (pos_scores) pos_scores[i] = P;
+            tot += (double)per;
+        }
+    }
+    if (lane == 0) s_loss[wv] = tot;
+    __syncthreads();
+    if (tid == 0) {
+        const double t = s_loss[0] + s_loss[1] + s_loss[2] + s_loss[3];
+        if (t != 0.0) atomicAdd(loss_sum, t);
+    }
+}
+
+// ---- the transpose of the query map -------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void add_nz(float* p, float v) {
+    if (v != 0.f) atomic_add_f32(p, v);
+}
+
+template <bool CPLX>
+__global__ __launch_bounds__(256) void shared_chain_kernel(const float* __restrict__ ent, const float* __restrict__ rel, const int32_t* __restrict__ triples,
+                                                           const int32_t* __restrict__ side, int64_t B, int ks, const float* __restrict__ Q, const float* __restrict__ dQ,
+                                                           const float* __restrict__ cpos, float* g_ent, float* g_rel) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= B) return;
+    const int K = CPLX ? 2 * ks : ks;
+    const bool subj = side[i] != 0;
+    const int64_t so = (int64_t)triples[3 * i] * K, po = (int64_t)triples[3 * i + 1] * K, oo = (int64_t)triples[3 * i + 2] * K;
+    const float* S = ent + so;
+    const float* P = rel + po;
+    const float* O = ent + oo;
+    const float* q = Q + i * K;
+    const float* d = dQ + i * K;
+    const float c = cpos[i];
+    float* g_own = g_ent + (subj ? so : oo);    // the replaced row's original: c_pos q_i
+    float* g_kept = g_ent + (subj ? oo : so);   // the kept entity row
+    float* g_p = g_rel + po;
+    for (int u = lane; u < ks; u += 64) {
+        if constexpr (CPLX) {
+            const float p0 = P[u], p1 = P[ks + u];
+            const float w0 = subj ? S[u] : O[u], w1 = subj ? S[ks + u] : O[ks + u];   // own
+            const float t0 = d[u] + c * w0, t1 = d[ks + u] + c * w1;                  // dL/dq
+            float dp0, dp1, dk0, dk1;
+            if (subj) {   // q = q(p, o); t stands where s does in the score
+                const float o0 = O[u], o1 = O[ks + u];
+                dp0 = t0 * o0 + t1 * o1; dp1 = t0 * o1 - t1 * o0;
+                dk0 = t0 * p0 - t1 * p1; dk1 = t0 * p1 + t1 * p0;
+            } else {      // q = q(s, p); t stands where o does
+                const float s0 = S[u], s1 = S[ks + u];
+                dk0 = p0 * t0 + p1 * t1; dk1 = p0 * t1 - p1 * t0;
+                dp0 = s0 * t0 + s1 * t1; dp1 = s0 * t1 - s1 * t0;
+            }
+            add_nz(g_own + u, c * q[u]); add_nz(g_own + ks + u, c * q[ks + u]);
+            add_nz(g_kept + u, dk0); add_nz(g_kept + ks + u, dk1);
+            add_nz(g_p + u, dp0); add_nz(g_p + ks + u, dp1);
+        } else {
+            const float p = P[u], w = subj ? S[u] : O[u], kept = subj ? O[u] : S[u];
+            const float t = d[u] + c * w;
+            add_nz(g_own + u, c * q[u]);
+            add_nz(g_kept + u, t * p);
+            add_nz(g_p + u, t * kept);
+        }
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+static bool shared_model_ok(const amdkge_model* m) {
+    return m->scoring_type == AMDKGE_DISTMULT || m->scoring_type == AMDKGE_COMPLEX || m->scoring_type == AMDKGE_HOLE;
+}
+static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+// groups per chunk of the score buffer
+static int64_t shared_chunk_groups(int64_t n_groups, int64_t G, int64_t M) {
+    int64_t gpc = CHUNK_SCORES / (G * M);
+    if (gpc < 1) gpc = 1;
+    return gpc < n_groups ? gpc : n_groups;
+}
+struct SharedPlan {
+    int64_t n_groups, gpc, off_q, off_dq, off_pos, off_cpos, off_s, total;
+};
+static bool shared_plan(const amdkge_model* m, int64_t B, int64_t G, int64_t M, SharedPlan& p) {
+    if (B < 1 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return false;
+    if (G > B) G = B;
+    if (G > (1ll << 40) / M) return false;   // (G * M stays far inside 64 bits)
+    const int64_t K = row_floats(m);
+    p.n_groups = (B + G - 1) / G;
+    p.gpc = shared_chunk_groups(p.n_groups, G, M);
+    int64_t rows = p.gpc * G;
+    if (rows > B) rows = B;
+    int64_t off = 0;
+    p.off_q = off; off += align256(B * K * 4);
+    p.off_dq = off; off += align256(B * K * 4);
+    p.off_pos = off; off += align256(B * 4);
+    p.off_cpos = off; off += align256(B * 4);
+    p.off_s = off; off += align256(rows * M * 4);
+    p.total = off;
+    return true;
+}
+
+template <bool CPLX>
+static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int M,
+                      const int32_t* d_ids, const int32_t* d_side, float* g_ent, float* g_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores,
+                      char* work, const SharedPlan& p, hipStream_t st) {
+    const int ks = stored_k(m), K = row_floats(m);
+    const ModelConst mc = model_const(m);
+    float* Q = reinterpret_cast<float*>(work + p.off_q);
+    float* dQ = reinterpret_cast<float*>(work + p.off_dq);
+    float* pos_raw = reinterpret_cast<float*>(work + p.off_pos);
+    float* cpos = reinterpret_cast<float*>(work + p.off_cpos);
+    float* S = reinterpret_cast<float*>(work + p.off_s);
+    const int64_t wave_blocks = (B + 3) / 4;
+    if (wave_blocks > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: too many positives for one launch; split them");
+    hipLaunchKernelGGL(shared_query_kernel<CPLX>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, Q, pos_raw);
+    if (int rc = check_launch("shared_query")) return rc;
+    SharedGemmArgs a{};
+    a.ent = d_ent; a.ids = d_ids; a.Q = Q; a.S = S; a.dQ = dQ; a.g_ent = g_ent; a.B = B; a.G = G; a.M = M; a.K = K;
+    const int tg = (int)((G + GT - 1) / GT), tm = (M + GT - 1) / GT, tk = (K + GT - 1) / GT;
+    for (int64_t g0 = 0; g0 < p.n_groups; g0 += p.gpc) {
+        const int64_t ng = (p.n_groups - g0) < p.gpc ? (p.n_groups - g0) : p.gpc;
+        const int64_t row0 = g0 * G;
+        const int64_t rows = ((g0 + ng) * G < B ? (g0 + ng) * G : B) - row0;
+        a.g0 = g0;
+        const int64_t nb_fwd = ng * tg * tm, nb_dq = ng * tg * tk, nb_de = ng * tm * tk;
+        if (nb_fwd > 0x7FFFFFFFll || nb_dq > 0x7FFFFFFFll || nb_de > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: too many tiles for one launch");
+        a.tiles_m = tg; a.tiles_n = tm;
+        hipLaunchKernelGGL(shared_gemm_kernel<GEMM_FWD>, dim3((unsigned)nb_fwd), dim3(256), 0, st, a);
+        if (int rc = check_launch("shared_gemm_fwd")) return rc;
+        int64_t lb = (rows + 3) / 4;
+        if (lb > 2048) lb = 2048;
+        hipLaunchKernelGGL(shared_loss_kernel, dim3((unsigned)lb), dim3(256), 0, st, S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum,
+                           d_pos_scores, d_neg_scores);
+        if (int rc = check_launch("shared_loss")) return rc;
+        a.tiles_m = tg; a.tiles_n = tk;
+        hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DQ>, dim3((unsigned)nb_dq), dim3(256), 0, st, a);
+        if (int rc = check_launch("shared_gemm_dq")) return rc;
+        a.tiles_m = tm; a.tiles_n = tk;
+        hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DE>, dim3((unsigned)nb_de), dim3(256), 0, st, a);
+        if (int rc = check_launch("shared_gemm_de")) return rc;
+    }
+    hipLaunchKernelGGL(shared_chain_kernel<CPLX>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, Q, dQ, cpos, g_ent, g_rel);
+    return check_launch("shared_chain");
+}
+
+}  // namespace kge
+
+using namespace kge;
+
+extern "C" int amdkge_sample_shared(const int32_t* d_triples, int64_t B, int64_t G, int32_t M, int64_t sample_base, int64_t sample_range, uint64_t seed, uint64_t step,
+                                    int32_t side_mode, const uint32_t* d_side_thr, const int32_t* d_pool, int64_t pool_n, int32_t* d_ids, int32_t* d_side, void* stream) {
+    if (B < 0 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return set_error(AMDKGE_EINVAL, "sample_shared: bad sizes (B >= 0, G >= 1, 1 <= M < 2^24)");
+    if (!d_ids || !d_side) return set_error(AMDKGE_EINVAL, "sample_shared: NULL pointer");
+    if (side_mode < AMDKGE_NEG_SIDE_UNIFORM || side_mode > AMDKGE_NEG_SIDE_O_ONLY) return set_error(AMDKGE_EINVAL, "sample_shared: unknown side_mode");
+    if (side_mode == AMDKGE_NEG_SIDE_BERNOULLI && (!d_side_thr || (B > 0 && !d_triples))) return set_error(AMDKGE_EINVAL, "sample_shared: AMDKGE_NEG_SIDE_BERNOULLI needs d_side_thr and d_triples");
+    if (d_pool && (pool_n < 1 || pool_n > 0xFFFFFFFFll)) return set_error(AMDKGE_EINVAL, "sample_shared: a pool needs pool_n in [1, 2^32)");
+    if (!d_pool && (sample_range <= 0 || sample_range > 0xFFFFFFFFll || sample_base < 0)) return set_error(AMDKGE_EINVAL, "sample_shared: sample_range must be in [1, 2^32), sample_base >= 0");
+    if (B == 0) return AMDKGE_OK;
+    if (G > B) G = B;
+    SharedDrawArgs a{};
+    a.triples = d_triples; a.B = B; a.G = G; a.n_groups = (B + G - 1) / G; a.M = M;
+    a.base = sample_base; a.range = d_pool ? 1u : (uint32_t)sample_range;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.step_lo = (uint32_t)step; a.step_hi = (uint32_t)(step >> 32);
+    a.side_mode = side_mode; a.side_thr = d_side_thr; a.pool = d_pool; a.pool_n = d_pool ? (uint32_t)pool_n : 0u;
+    a.ids = d_ids; a.side = d_side;
+    if (a.n_groups > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "sample_shared: too many groups");
+    const int64_t blocks = (a.n_groups * M + B + 255) / 256;
+    if (blocks > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "sample_shared: too many values for one launch; split them");
+    hipLaunchKernelGGL(shared_draw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("sample_shared");
+}
+
+extern "C" int64_t amdkge_train_shared_workspace_bytes(const amdkge_model* m, int64_t B, int64_t G, int32_t M) {
+    if (validate_model(m) || !shared_model_ok(m)) return 0;
+    SharedPlan p;
+    return shared_plan(m, B, G, M, p) ? p.total : 0;
+}
+
+extern "C" int amdkge_train_shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
+                                          int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum,
+                                          float* d_pos_scores, float* d_neg_scores, void* d_work, void* stream) {
+    if (int rc = validate_model(m)) return rc;
+    if (!shared_model_ok(m)) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: TransE and RotatE score a distance, not a contraction: only DistMult, ComplEx and HolE share negatives");
+    if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_shared: unknown loss kind");
+    if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: FocusE is not offered with shared negatives");
+    if (B < 0 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return set_error(AMDKGE_EINVAL, "train_shared: bad sizes (B >= 0, G >= 1, 1 <= M < 2^24)");
+    if (!d_ent || !d_rel || !d_grad_ent || !d_grad_rel || !d_loss_sum) return set_error(AMDKGE_EINVAL, "train_shared: NULL table / gradient / loss pointer");
+    if (B == 0) return AMDKGE_OK;
+    if (!d_triples || !d_neg_ids || !d_side || !d_work) return set_error(AMDKGE_EINVAL, "train_shared: NULL triples / ids / sides / workspace");
+    if (G > B) G = B;
+    SharedPlan p;
+    if (!shared_plan(m, B, G, M, p)) return set_error(AMDKGE_EINVAL, "train_shared: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    char* work = static_cast<char*>(d_work);
+    if (m->scoring_type != AMDKGE_DISTMULT)   // ComplEx, and HolE on its instantiation (the 2/k scale travels in ModelConst)
+        return run_shared<true>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, st);
+    return run_shared<false>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, st);
+}

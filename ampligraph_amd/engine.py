@@ -429,6 +429,38 @@ class KgeEngine:
             _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]), int(max_tries), _ptr(stats), _ptr(out), _stream()))
         return out
 
+    def sample_shared(self, triples, group_size, num_negs, seed, step, sample_base=0, sample_range=None, side="uniform",
+                      side_thr=None, pool=None):
+        """amdkge_sample_shared (include/amdkge_shared.h has the draw): for the int32 device triples [B, 3] of a whole batch ->
+        (ids int32 [ceil(B / group_size), num_negs], side int32 [B]; 1 = the subject is replaced).  Both live in the engine's
+        buffer cache: the next call overwrites them."""
+        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
+        n_groups = -(-B // min(G, B)) if B > 0 and G > 0 else 0
+        ids = self._buf("shared_ids", (n_groups, M), torch.int32)
+        sd = self._buf("shared_side", (B,), torch.int32)
+        check(self.lib.amdkge_sample_shared(_ptr(triples), B, G, M, int(sample_base), int(sample_range or self.n_ents), int(seed), int(step),
+                                            _ffi.NEG_SIDE_MODES[side], _ptr(side_thr), _ptr(pool), 0 if pool is None else int(pool.numel()),
+                                            _ptr(ids), _ptr(sd), _stream()))
+        return ids, sd
+
+    def shared_supported(self, B, group_size, num_negs):
+        """True when the shared-negative step (amdkge_train_shared_fwdbwd) covers this model and shape."""
+        return int(self.lib.amdkge_train_shared_workspace_bytes(C.byref(self.model), int(B), int(group_size), int(num_negs))) > 0
+
+    def train_shared_fwdbwd(self, triples, group_size, num_negs, ids, side, loss, pos_scores=None, neg_scores=None):
+        """amdkge_train_shared_fwdbwd: the train step of train_fwdbwd with eta = num_negs on the corruptions 'positive i with its
+        side[i] entity replaced by ids[i // group_size][j]', as matrix products.  Accumulates into g_ent / g_rel and loss_acc[0];
+        neg_scores (optional) has row j * B + i."""
+        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
+        need = int(self.lib.amdkge_train_shared_workspace_bytes(C.byref(self.model), B, G, M)) if B > 0 else 0
+        if B > 0 and need <= 0:
+            raise ValueError("train_shared_fwdbwd: shared negatives are not offered for this model / shape "
+                             f"({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
+        work = self._buf("shared_work", (need,), torch.uint8)
+        check(self.lib.amdkge_train_shared_fwdbwd(
+            C.byref(self.model), C.byref(loss), _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M, _ptr(ids), _ptr(side),
+            _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work), _stream()))
+
     def negatives_side_thresholds(self, po_keys, sp_keys, n_ents=None, n_rels=None):
         """amdkge_negatives_side_thresholds: the Bernoulli thresholds floor(2^32 G_po / (G_sp + G_po)) per relation from a
         FilterIndex's two int64 device key arrays -> int32 device tensor [n_rels] holding the uint32 bit patterns."""

@@ -114,7 +114,9 @@ class ScoringBasedEmbeddingModel:
         only; see amdkge_opt.lazy); deterministic=True: bitwise reproducible training (AMDKGE_TILED_DETERMINISTIC);
         negatives=None (the train kernels' own draw: a fair coin for the side, a uniform entity) | NegativeSampling | a dict of its
         keywords {"filter", "side", "entities", "max_tries"} (latent_features/negatives.py: rejection of known statements, Bernoulli
-        side choice, an entity pool; replicated tables only; model.negative_sampling_stats_ after fit()).  Multi-GPU, one process per GPU under torch.distributed:
+        side choice, an entity pool; replicated tables only; model.negative_sampling_stats_ after fit()) | SharedNegatives | its dict
+        form {"shared": num_negs, "group_size", "side", "entities"} (groups of positives share one list of replacements, scored by a
+        matrix product: DistMult / ComplEx / HolE on one GPU, no deterministic, lazy or FocusE mode).  Multi-GPU, one process per GPU under torch.distributed:
         entity_sharding="replicated" (default: tables replicated, gradient all-reduce) | "rows" (entity table
         row-sharded over the ranks, ampligraph_amd/sharded.py; sharded_negatives="local" | "global" chooses where its corruptions
         are drawn from) | "columns" (tables that fit every GPU: rank r TRAINS on k / W units of every row and the whole batch, one
@@ -138,6 +140,8 @@ class ScoringBasedEmbeddingModel:
         if self._negatives is not None and self._sharding != "replicated":
             raise NotImplementedError("negatives: the row- and column-sharded step loops (entity_sharding='rows' / 'columns') build "
                                       "their own corruption overrides and do not take a negative sampler; use replicated tables")
+        if getattr(self._negatives, "shared", False):   # SharedNegatives: what it cannot be combined with
+            self._negatives.check_model(self, optimizer_mode)
         self.optimizer = optimizers.get(optimizer)
         if optimizer_mode == "lazy":
             # DEVIATION from the reference (its optimizer is dense, optimizers.py:136-168): only rows that received a

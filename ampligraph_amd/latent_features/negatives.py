@@ -7,6 +7,9 @@ replacement entities (AmpliGraph 1.x's negative_corruption_entities) -- and `bin
 `BoundNegatives`: the object trainer.StepLoop calls each step.  It runs amdkge_sample_negatives (kge_negatives.hip; the draw is
 defined in include/amdkge_negatives.h) and hands the rows to the train step as its neg_override: the train kernels and the loss are
 the ones of the default path.
+
+`SharedNegatives` is the other kind: one list of replacement entities per GROUP of positives, scored by a matrix product
+(kge_train_shared.hip).  It binds to a `BoundSharedNegatives`, whose step is engine.train_shared_fwdbwd instead of the override.
 """
 import numpy as np
 
@@ -39,9 +42,12 @@ class NegativeSampling:
 
     @classmethod
     def get(cls, spec):
-        """compile()'s `negatives` argument -> None or a sampler: None, a NegativeSampling (or anything with .bind()), a dict of its keywords."""
+        """compile()'s `negatives` argument -> None or a sampler: None, a NegativeSampling or SharedNegatives (or anything with .bind()), a dict of
+        NegativeSampling's keywords, or {"shared": num_negs, ...} for a SharedNegatives."""
         if spec is None or hasattr(spec, "bind"):
             return spec
+        if isinstance(spec, dict) and "shared" in spec:   # {"shared": M, ...}: SharedNegatives(num_negs=M, ...)
+            return SharedNegatives.from_dict(spec)
         if isinstance(spec, dict):
             unknown = set(spec) - {"filter", "side", "entities", "max_tries"}
             if unknown:
@@ -121,3 +127,98 @@ class BoundNegatives:
         """{"redraws", "exhausted"} since the bind: one device read (synchronises the stream)."""
         rd, ex = (int(v) for v in self.stats_dev.tolist())
         return {"redraws": rd, "exhausted": ex}
+
+
+class SharedNegatives:
+    """Shared-negative training (PyTorch-BigGraph's batch negatives, DGL-KE's chunked sampling): the positives of a batch are cut
+    into groups of `group_size` consecutive rows, every group shares ONE list of `num_negs` replacement entities, every positive
+    has one replaced side.  The step is the default one on those corruptions (same losses, `num_negs` takes the place of eta), but
+    the scores of a group are one matrix product on the matrix cores and a positive costs three row reads whatever `num_negs` is
+    (include/amdkge_shared.h, kge_train_shared.hip).  DistMult, ComplEx and HolE only.
+
+    num_negs: corruptions per positive, 1 .. 2^24 - 1.  group_size: None (= num_negs) or the positives per group.
+    side: "uniform" | "bernoulli" | "s" | "o", decided per POSITIVE.  entities: None or the labels replacements are drawn from.
+    There is no `filter`: a rejection per positive would give every positive its own list.
+
+    compile(negatives=SharedNegatives(...)) or compile(negatives={"shared": num_negs, "group_size": ..., "side": ..., "entities": ...})."""
+
+    shared = True   # what trainer.StepLoop.step looks for
+
+    def __init__(self, num_negs, group_size=None, side="uniform", entities=None):
+        def count(v, name, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
+                raise ValueError("negatives: `{}` must be an integer in [1, {}]".format(name, hi))
+            return int(v)
+
+        self.num_negs = count(num_negs, "num_negs", _ffi.SHARED_MAX_NEGS)
+        self.group_size = self.num_negs if group_size is None else count(group_size, "group_size", 2 ** 31 - 1)
+        if not isinstance(side, str) or side not in _ffi.NEG_SIDE_MODES:
+            raise ValueError("negatives: `side` must be 'uniform', 'bernoulli', 's' or 'o', got {!r}".format(side))
+        if entities is not None:
+            if isinstance(entities, (str, bytes)) or np.ndim(entities) != 1 or len(entities) < 1:
+                raise ValueError("negatives: `entities` must be None or a non-empty 1-D sequence of entity labels")
+            entities = np.asarray(entities)
+        self.side, self.entities = side, entities
+
+    @classmethod
+    def from_dict(cls, spec):
+        if "filter" in spec and spec["filter"] is not False:
+            raise ValueError("negatives: shared negatives take no `filter`: a rejection per positive breaks the sharing")
+        unknown = set(spec) - {"shared", "group_size", "side", "entities", "filter"}
+        if unknown:
+            raise ValueError("negatives: unknown keys {} for shared negatives".format(sorted(unknown)))
+        return cls(spec["shared"], spec.get("group_size"), spec.get("side", "uniform"), spec.get("entities"))
+
+    def get_config(self):
+        """The dict form compile(negatives=...) takes (labels as given)."""
+        return {"shared": self.num_negs, "group_size": self.group_size, "side": self.side, "entities": self.entities}
+
+    def check_model(self, model, optimizer_mode="dense"):
+        """compile()'s refusals: everything that is known before a GPU is touched."""
+        if model.scoring_type not in ("DistMult", "ComplEx", "HolE"):
+            raise NotImplementedError("negatives: shared negatives need a score that is a contraction with the replaced row "
+                                      "(DistMult, ComplEx, HolE); {} scores a distance".format(model.scoring_type))
+        if model._deterministic:
+            raise NotImplementedError("negatives: shared negatives accumulate in no fixed order; deterministic=True is not offered")
+        if optimizer_mode == "lazy":
+            raise NotImplementedError("negatives: shared negatives are not offered with optimizer_mode='lazy'")
+
+    def bind(self, model, engine, train):
+        import torch
+
+        loop = getattr(model, "_loop", None)
+        if getattr(model, "use_focusE", False):
+            raise NotImplementedError("negatives: FocusE is not offered with shared negatives")
+        if getattr(loop, "multi", False):
+            raise NotImplementedError("negatives: shared negatives run on one rank only")
+        if getattr(loop, "deterministic", False):
+            raise NotImplementedError("negatives: shared negatives accumulate in no fixed order; deterministic mode is not offered")
+        N, R = int(model._n_ents), int(model._n_rels)
+        pool = None
+        if self.entities is not None:
+            ids = np.asarray(model.data_indexer.get_indexes(self.entities, "e"), dtype=np.int64)
+            if ids.shape[0] != self.entities.shape[0]:
+                raise ValueError("negatives: {} of the `entities` are not in the training set".format(self.entities.shape[0] - ids.shape[0]))
+            if ids.min() < 0 or ids.max() >= N:   # the train kernels do not check the ids
+                raise ValueError("negatives: entity ids outside [0, {})".format(N))
+            pool = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32)).to(engine.device)
+        side_thr = None
+        if self.side == "bernoulli":
+            index = FilterIndex([train], N, R, engine=engine)
+            side_thr = engine.negatives_side_thresholds(*index.device_keys(engine), index.n_ents, index.n_rels)
+        return BoundSharedNegatives(engine, self.num_negs, self.group_size, self.side, side_thr, pool)
+
+
+class BoundSharedNegatives:
+    """A SharedNegatives bound to one fit().  trainer.StepLoop.step calls draw(global_batch, seed, step) -> (ids int32
+    [n_groups, num_negs], side int32 [B]) and hands both to engine.train_shared_fwdbwd."""
+
+    shared = True
+
+    def __init__(self, engine, num_negs, group_size, side, side_thr, pool):
+        self.engine, self.num_negs, self.group_size = engine, int(num_negs), int(group_size)
+        self.side, self.side_thr, self.pool = side, side_thr, pool
+
+    def draw(self, global_batch, seed, step):
+        return self.engine.sample_shared(global_batch, self.group_size, self.num_negs, seed, step, side=self.side,
+                                         side_thr=self.side_thr, pool=self.pool)

@@ -125,7 +125,8 @@ class StepLoop:
         self.kernel_hook = None   # bench.py: callable(i) recording HIP events at the phase boundaries (PHASES)
         # compile(negatives=...): None (the train kernels draw their own corruptions) or a callable(global_batch, lo, hi, eta, seed,
         # rng_step) -> int32 device rows [(hi - lo) * eta, 3], the corruptions of rows [lo, hi) of the global batch drawn by GLOBAL
-        # row (latent_features/negatives.py: BoundNegatives), which the step hands to the train kernels as their override
+        # row (latent_features/negatives.py: BoundNegatives), which the step hands to the train kernels as their override; or an object
+        # with `.shared` set (BoundSharedNegatives: .draw(), .group_size, .num_negs), whose step is engine.train_shared_fwdbwd
         self.negatives = None
         engine.prepare_training(optimizer.name)
         if hasattr(optimizer, "bind"):
@@ -172,6 +173,24 @@ class StepLoop:
         lam = self.reg    # LPRegularizer objects (or None): the engine turns them into the descriptor's (p, lambda) terms
         lam_r = self.reg if isinstance(self.reg_rel, str) else self.reg_rel
         opt_ffi = self.optimizer.to_ffi(self.optimizer.iterations, 2)
+        if getattr(self.negatives, "shared", False):
+            # SharedNegatives: draw -> matrix-product forward / backward (kge_train_shared.hip) -> dense sweep.  Every other
+            # configuration runs the code below.
+            if focus is not None or self.multi or self.deterministic:
+                raise NotImplementedError("shared negatives: no FocusE, no deterministic mode, one rank only")
+            if self.kernel_hook is not None:
+                self.kernel_hook(0)
+            if bg > 0:
+                sh = self.negatives
+                ids, side = sh.draw(global_batch, self.seed, rng_step)
+                eng.train_shared_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi)
+            if self.kernel_hook is not None:
+                self.kernel_hook(1)
+            eng.opt_step(opt_ffi, lam, lam_r)
+            if self.kernel_hook is not None:
+                self.kernel_hook(2)
+            self.n_steps += 1
+            return
         # owner-computes path (kge_train_tiled.hip) whenever the shape allows it: no global atomics, no dense
         # entity gradient; data-parallel runs take its gradient-only form and keep the dense sweep
         tiled = (self.use_tiled or self.deterministic) and hi > lo and eng.tiled_supported(hi - lo, self.eta)
