@@ -26,12 +26,18 @@ namespace kge {
 // third key form (relation prediction, amdkge_pair_filter_build): group key (s * N + o), values p -- the divisor that separates
 // group and value is then R instead of N
 constexpr int FILTER_KEY_PAIR = 4;
+// fourth and fifth key form (relation sets, include/amdkge_types.h): the group is the relation alone, the values are the subjects
+// (a relation's DOMAIN) or the objects (its RANGE) seen with it
+constexpr int FILTER_KEY_DOMAIN = 5;
+constexpr int FILTER_KEY_RANGE = 6;
 
-// THE definition of the three key forms: the group a triple belongs to.  The build sorts by group * divisor + value, the lookup
+// THE definition of the five key forms: the group a triple belongs to.  The build sorts by group * divisor + value, the lookup
 // searches the sorted groups for the query's.
 //   AMDKGE_SIDE_S: group (p, o), value s      AMDKGE_SIDE_O: group (s, p), value o      FILTER_KEY_PAIR: group (s, o), value p
+//   FILTER_KEY_DOMAIN: group p, value s       FILTER_KEY_RANGE: group p, value o
+__host__ __device__ inline bool filter_key_is_relation(int form) { return form == FILTER_KEY_DOMAIN || form == FILTER_KEY_RANGE; }
 __host__ __device__ inline uint64_t filter_group_key(int form, uint64_t s, uint64_t p, uint64_t o, uint64_t N, uint64_t R) {
-    return form == FILTER_KEY_PAIR ? s * N + o : form == AMDKGE_SIDE_S ? p * N + o : s * R + p;
+    return filter_key_is_relation(form) ? p : form == FILTER_KEY_PAIR ? s * N + o : form == AMDKGE_SIDE_S ? p * N + o : s * R + p;
 }
 __host__ __device__ inline uint64_t filter_key_divisor(int form, uint64_t N, uint64_t R) { return form == FILTER_KEY_PAIR ? R : N; }
 
@@ -39,13 +45,16 @@ __global__ void filter_keys_kernel(const int32_t* __restrict__ tri, int64_t m, i
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const uint64_t s = (uint64_t)tri[3 * i], p = (uint64_t)tri[3 * i + 1], o = (uint64_t)tri[3 * i + 2];
-    const uint64_t value = form == FILTER_KEY_PAIR ? p : form == AMDKGE_SIDE_S ? s : o;
+    const uint64_t value = form == FILTER_KEY_PAIR ? p : (form == AMDKGE_SIDE_S || form == FILTER_KEY_DOMAIN) ? s : o;
     keys[i] = filter_group_key(form, s, p, o, N, R) * filter_key_divisor(form, N, R) + value;
 }
 
-// the lookup: one thread per query triple, lower_bound of its group key in the sorted group keys
+// the lookup: one thread per query triple, lower_bound of its group key in the sorted group keys.  A group that is absent, or holds
+// fewer than min_size ids, gives the fallback range (fb_lo, fb_hi): (0, 0) with min_size 0 for the filter lookups, the caller's
+// for the relation sets -- THE place of the min_size rule.
 __global__ void filter_ranges_kernel(const int64_t* keys, const int64_t* start, int64_t n_keys, const int32_t* triples, int64_t n, int form,
-                                     int64_t n_ents, int64_t n_rels, int64_t* lo_out, int64_t* hi_out) {
+                                     int64_t n_ents, int64_t n_rels, int64_t min_size, int64_t fb_lo, int64_t fb_hi, int64_t* lo_out,
+                                     int64_t* hi_out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t q = (int64_t)filter_group_key(form, (uint64_t)triples[3 * i], (uint64_t)triples[3 * i + 1], (uint64_t)triples[3 * i + 2],
@@ -55,9 +64,13 @@ __global__ void filter_ranges_kernel(const int64_t* keys, const int64_t* start, 
         const int64_t m = (a + b) >> 1;
         if (keys[m] < q) a = m + 1; else b = m;
     }
-    const bool hit = a < n_keys && keys[a] == q;
-    lo_out[i] = hit ? start[a] : 0;
-    hi_out[i] = hit ? start[a + 1] : 0;
+    int64_t lo = fb_lo, hi = fb_hi;
+    if (a < n_keys && keys[a] == q) {
+        const int64_t g_lo = start[a], g_hi = start[a + 1];
+        if (g_hi - g_lo >= min_size) { lo = g_lo; hi = g_hi; }
+    }
+    lo_out[i] = lo;
+    hi_out[i] = hi;
 }
 
 // low 32 bits: 1 where a NEW KEY starts (duplicates of a triple across the filter datasets collapse), high 32 bits: 1 where a
@@ -134,7 +147,8 @@ static int filter_error(int code, const char* who, const char* what) {
     return set_error(code, msg);
 }
 
-// the build behind both entry points; form: AMDKGE_SIDE_S / AMDKGE_SIDE_O / FILTER_KEY_PAIR, who: the entry point, for the messages
+// the build behind the three entry points; form: AMDKGE_SIDE_S / AMDKGE_SIDE_O / FILTER_KEY_PAIR / FILTER_KEY_DOMAIN / FILTER_KEY_RANGE,
+// who: the entry point, for the messages
 static int filter_build_run(const char* who, const int32_t* d_triples, int64_t m, int form, int64_t n_ents, int64_t n_rels, int64_t* d_keys,
                             int64_t* d_start, int32_t* d_ids, int64_t* d_counts, void* d_work, hipStream_t st) {
     if (m < 0 || n_ents <= 0 || n_rels <= 0 || m > 0xFFFFFFFFll) return filter_error(AMDKGE_EINVAL, who, "bad sizes (at most 2^32 - 1 filter triples)");
@@ -168,14 +182,16 @@ static int filter_build_run(const char* who, const int32_t* d_triples, int64_t m
     return check_launch("filter_emit");
 }
 
-// the lookup behind both entry points (the pair form's group key has no n_rels in it: its entry point passes 1)
+// the lookup behind the three entry points (the pair form's group key has no n_rels in it: its entry point passes 1; the relation
+// forms' has neither size in it).  min_size, fb_lo, fb_hi: filter_ranges_kernel's; the filter lookups pass (0, 0, 0).
 static int filter_ranges_run(const char* who, const int64_t* d_keys, const int64_t* d_start, int64_t n_keys, const int32_t* d_triples, int64_t n,
-                             int form, int64_t n_ents, int64_t n_rels, int64_t* d_lo, int64_t* d_hi, hipStream_t st) {
-    if (n < 0 || n_keys < 0 || n_ents <= 0 || n_rels <= 0) return filter_error(AMDKGE_EINVAL, who, "bad sizes");
+                             int form, int64_t n_ents, int64_t n_rels, int64_t min_size, int64_t fb_lo, int64_t fb_hi, int64_t* d_lo,
+                             int64_t* d_hi, hipStream_t st) {
+    if (n < 0 || n_keys < 0 || n_ents <= 0 || n_rels <= 0 || min_size < 0 || fb_lo < 0 || fb_hi < fb_lo) return filter_error(AMDKGE_EINVAL, who, "bad sizes");
     if (n == 0) return AMDKGE_OK;
     if (!d_triples || !d_lo || !d_hi || (n_keys > 0 && (!d_keys || !d_start))) return filter_error(AMDKGE_EINVAL, who, "NULL pointer");
     hipLaunchKernelGGL(filter_ranges_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_keys, d_start, n_keys, d_triples, n, form, n_ents,
-                       n_rels, d_lo, d_hi);
+                       n_rels, min_size, fb_lo, fb_hi, d_lo, d_hi);
     return check_launch(who);
 }
 
@@ -196,10 +212,26 @@ extern "C" int amdkge_filter_ranges(const int64_t* d_keys, const int64_t* d_star
                                     int64_t n, int32_t side, int64_t n_ents, int64_t n_rels, int64_t* d_lo, int64_t* d_hi,
                                     void* stream) {
     if (side != AMDKGE_SIDE_S && side != AMDKGE_SIDE_O) return set_error(AMDKGE_EINVAL, "filter_ranges: side must be AMDKGE_SIDE_S or AMDKGE_SIDE_O");
-    return filter_ranges_run("filter_ranges", d_keys, d_start, n_keys, d_triples, n, (int)side, n_ents, n_rels, d_lo, d_hi, (hipStream_t)stream);
+    return filter_ranges_run("filter_ranges", d_keys, d_start, n_keys, d_triples, n, (int)side, n_ents, n_rels, 0, 0, 0, d_lo, d_hi, (hipStream_t)stream);
 }
 
 extern "C" int amdkge_pair_filter_ranges(const int64_t* d_keys, const int64_t* d_start, int64_t n_keys, const int32_t* d_triples, int64_t n,
                                          int64_t n_ents, int64_t* d_lo, int64_t* d_hi, void* stream) {
-    return filter_ranges_run("pair_filter_ranges", d_keys, d_start, n_keys, d_triples, n, FILTER_KEY_PAIR, n_ents, 1, d_lo, d_hi, (hipStream_t)stream);
+    return filter_ranges_run("pair_filter_ranges", d_keys, d_start, n_keys, d_triples, n, FILTER_KEY_PAIR, n_ents, 1, 0, 0, 0, d_lo, d_hi, (hipStream_t)stream);
+}
+
+// Relation sets (include/amdkge_types.h): the same CSR keyed by the relation alone -- the distinct subjects (side S: the DOMAIN) or
+// objects (side O: the RANGE) seen with each relation.  Workspace: amdkge_filter_build_workspace_bytes, the plan is the same.
+extern "C" int amdkge_relation_sets_build(const int32_t* d_triples, int64_t m, int32_t side, int64_t n_ents, int64_t n_rels, int64_t* d_keys,
+                                          int64_t* d_start, int32_t* d_ids, int64_t* d_counts, void* d_work, void* stream) {
+    if (side != AMDKGE_SIDE_S && side != AMDKGE_SIDE_O) return set_error(AMDKGE_EINVAL, "relation_sets_build: side must be AMDKGE_SIDE_S or AMDKGE_SIDE_O");
+    return filter_build_run("relation_sets_build", d_triples, m, side == AMDKGE_SIDE_S ? FILTER_KEY_DOMAIN : FILTER_KEY_RANGE, n_ents, n_rels, d_keys,
+                            d_start, d_ids, d_counts, d_work, (hipStream_t)stream);
+}
+
+// (the domain and the range CSR have the same group key, the relation: the lookup needs no side)
+extern "C" int amdkge_relation_sets_ranges(const int64_t* d_keys, const int64_t* d_start, int64_t n_keys, const int32_t* d_triples, int64_t n,
+                                           int64_t min_size, int64_t fb_lo, int64_t fb_hi, int64_t* d_lo, int64_t* d_hi, void* stream) {
+    return filter_ranges_run("relation_sets_ranges", d_keys, d_start, n_keys, d_triples, n, FILTER_KEY_DOMAIN, 1, 1, min_size, fb_lo, fb_hi, d_lo,
+                             d_hi, (hipStream_t)stream);
 }

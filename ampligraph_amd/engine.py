@@ -429,6 +429,28 @@ class KgeEngine:
             _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]), int(max_tries), _ptr(stats), _ptr(out), _stream()))
         return out
 
+    def sample_negatives_typed(self, triples, eta, seed, step, sample_base=0, sample_range=None, row_offset=0, b_global=0,
+                               side="uniform", side_thr=None, pool=None, s_filter=None, o_filter=None, max_tries=8, stats=None,
+                               s_cand=None, o_cand=None):
+        """amdkge_sample_negatives_typed (include/amdkge_types.h has the draw): sample_negatives with every try's replacement taken from
+        the positive's own candidate range -- s_cand / o_cand: (lo, hi, ids) of the B positives, both or neither (what
+        relation_sets_ranges gives on a relation-set CSR); a positive whose range is empty is corrupted by sample_negatives' rule.
+        stats: int64 [3] device tensor, += (redraws, exhausted, untyped).  The result shares sample_negatives' buffer."""
+        B = int(triples.shape[0])
+        if (s_filter is None) != (o_filter is None):
+            raise ValueError("sample_negatives_typed: s_filter and o_filter are given together or not at all")
+        if (s_cand is None) != (o_cand is None):
+            raise ValueError("sample_negatives_typed: s_cand and o_cand are given together or not at all")
+        out = self._buf("negatives", (B * int(eta), 3), torch.int32)
+        none = (None, None, None)
+        sf, of, sc, oc = s_filter or none, o_filter or none, s_cand or none, o_cand or none
+        check(self.lib.amdkge_sample_negatives_typed(
+            _ptr(triples), B, int(eta), int(sample_base), int(sample_range or self.n_ents), int(seed), int(step), int(row_offset),
+            int(b_global), _ffi.NEG_SIDE_MODES[side], _ptr(side_thr), _ptr(pool), 0 if pool is None else int(pool.numel()),
+            _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]), int(max_tries), _ptr(stats), _ptr(out),
+            _ptr(sc[0]), _ptr(sc[1]), _ptr(sc[2]), _ptr(oc[0]), _ptr(oc[1]), _ptr(oc[2]), _stream()))
+        return out
+
     def sample_shared(self, triples, group_size, num_negs, seed, step, sample_base=0, sample_range=None, side="uniform",
                       side_thr=None, pool=None):
         """amdkge_sample_shared (include/amdkge_shared.h has the draw): for the int32 device triples [B, 3] of a whole batch ->
@@ -470,12 +492,13 @@ class KgeEngine:
                                                         int(self.n_ents if n_ents is None else n_ents), n_rels, _ptr(thr), _stream()))
         return thr
 
-    def _filter_build(self, triples, side, n_ents, n_rels):
+    def _filter_build(self, triples, side, n_ents, n_rels, name=None):
         """One CSR filter index from the concatenated id triples (int32 [m,3] device tensor) -> (keys int64 [n_groups], start
-        int64 [n_groups + 1], ids int32 [n_unique]) device tensors.  side "s" | "o": amdkge_filter_build; None: the (s, o) pair
+        int64 [n_groups + 1], ids int32 [n_unique]) device tensors.  side "s" | "o": amdkge_filter_build (or, with
+        name="relation_sets_build", the relation sets of include/amdkge_types.h: the same protocol); None: the (s, o) pair
         form, amdkge_pair_filter_build.  One stream synchronisation (the two counts come back to size the views); an index is
         built once per evaluate() and cached."""
-        name = "filter_build" if side is not None else "pair_filter_build"
+        name = name or ("filter_build" if side is not None else "pair_filter_build")
         m = int(triples.shape[0])
         keys = torch.empty(max(m, 1), dtype=torch.int64, device=self.device)
         start = torch.empty(m + 1, dtype=torch.int64, device=self.device)
@@ -511,6 +534,21 @@ class KgeEngine:
     def filter_ranges(self, keys, start, triples, side, n_ents, n_rels):
         """(lo, hi) int64 device tensors: each triple's range in a FilterIndex id array (amdkge_filter_ranges; side 1 | 2)."""
         return self._filter_ranges(keys, start, triples, side, n_ents, n_rels)
+
+    def relation_sets_build(self, triples, side, n_ents, n_rels):
+        """amdkge_relation_sets_build: the CSR of the distinct subjects (side "s": the domains) or objects ("o": the ranges) per
+        relation of the int32 device triples -> (keys, start, ids), see _filter_build."""
+        return self._filter_build(triples, "s" if side == "s" else "o", n_ents, n_rels, name="relation_sets_build")
+
+    def relation_sets_ranges(self, keys, start, triples, min_size=0, fallback=(0, 0)):
+        """(lo, hi) int64 device tensors: the range of each triple's RELATION in the id array of a relation-set CSR; `fallback`
+        = (lo, hi) for a relation that is absent or whose set has fewer than min_size ids (amdkge_relation_sets_ranges)."""
+        n = int(triples.shape[0])
+        lo = torch.empty(n, dtype=torch.int64, device=self.device)
+        hi = torch.empty(n, dtype=torch.int64, device=self.device)
+        check(self.lib.amdkge_relation_sets_ranges(_ptr(keys), _ptr(start), int(keys.shape[0]), _ptr(triples), n, int(min_size),
+                                                   int(fallback[0]), int(fallback[1]), _ptr(lo), _ptr(hi), _stream()))
+        return lo, hi
 
     def compose_ranks(self, counts, sub, strategy, out=None, out_stride=1):
         """(greater, equal) counts [+ filter subtraction] -> 1-based ranks (amdkge_rank_compose)."""

@@ -114,7 +114,10 @@ class ScoringBasedEmbeddingModel:
         only; see amdkge_opt.lazy); deterministic=True: bitwise reproducible training (AMDKGE_TILED_DETERMINISTIC);
         negatives=None (the train kernels' own draw: a fair coin for the side, a uniform entity) | NegativeSampling | a dict of its
         keywords {"filter", "side", "entities", "max_tries"} (latent_features/negatives.py: rejection of known statements, Bernoulli
-        side choice, an entity pool; replicated tables only; model.negative_sampling_stats_ after fit()) | SharedNegatives | its dict
+        side choice, an entity pool; replicated tables only; model.negative_sampling_stats_ after fit()) | TypedNegatives | its dict
+        form {"types": "observed" | RelationTypes, "filter", "side", "entities", "max_tries", "min_size"} (type-constrained: a
+        corruption replaces the subject / object by a member of the relation's domain / range set, datasets/types.py; replicated
+        tables only; model.relation_types_ after fit(), which evaluate_typed() ranks against) | SharedNegatives | its dict
         form {"shared": num_negs, "group_size", "side", "entities"} (groups of positives share one list of replacements, scored by a
         matrix product: DistMult / ComplEx / HolE on one GPU, no deterministic, lazy or FocusE mode).  Multi-GPU, one process per GPU under torch.distributed:
         entity_sharding="replicated" (default: tables replicated, gradient all-reduce) | "rows" (entity table
@@ -343,6 +346,8 @@ class ScoringBasedEmbeddingModel:
         self._placement.publish()
         if hasattr(getattr(loop, "negatives", None), "stats"):
             self.negative_sampling_stats_ = loop.negatives.stats()   # {"redraws", "exhausted"} of this fit(): one read-back
+        if hasattr(getattr(loop, "negatives", None), "relation_types"):
+            self.relation_types_ = loop.negatives.relation_types     # TypedNegatives: the bound sets, evaluate_typed()'s default
         for cb in cbs:
             if hasattr(cb, "on_train_end"):
                 cb.on_train_end()
@@ -503,6 +508,58 @@ class ScoringBasedEmbeddingModel:
             return np.zeros((0, len(sides)), dtype=np.int32)
         fi = self._filter_index(use_filter, Xi)
         return self._placement.rank_candidates(Xi, sides, fi, ranking_strategy).cpu().numpy()
+
+    def evaluate_typed(self, x, types=None, use_filter=False, corrupt_side="s,o", ranking_strategy="worst", min_size=1, verbose=False):
+        """TYPE-CONSTRAINED evaluate() (the reference has none; PyKEEN's / LibKGE's / Krompass et al.'s protocol): int32 ranks,
+        1-based, shaped like evaluate()'s ("s+o" included), of row i's subject among the DOMAIN set of its relation and of its
+        object among the RANGE set, with entities_subset's semantics -- the true entity's score is compared with the set's,
+        whether or not it is listed.
+
+        types: a datasets.types.RelationTypes (observed in given datasets, or explicit), an already bound one, or None = the sets
+        the last fit() with TypedNegatives left in model.relation_types_ (ValueError when there are none; observed() without
+        datasets is valid in training only and raises ValueError here).  A relation that is unconstrained on a side, or whose
+        set has fewer than `min_size` ids, is ranked against ALL entities: then the rank is evaluate()'s.  Ties and filters as
+        in evaluate().  Rows with unseen labels are dropped, as evaluate() drops them.
+
+        Nothing per triple is built on the host: a triple's candidates are a [lo, hi) range into the sets' one id array, looked up
+        on the device (amdkge_relation_sets_ranges), and each side is one amdkge_rank_lists pass per chunk of 65 536 triples.  The
+        cost is the sets', not the entity table's -- see DESIGN.md for where per-relation evaluate(entities_subset=) calls win.
+        Needs the whole table on one GPU: row- / column-sharded models raise NotImplementedError."""
+        from ..datasets.types import BoundRelationTypes, RelationTypes
+
+        if corrupt_side not in ("s", "o", "s,o", "s+o"):
+            raise ValueError("Invalid value for corrupt_side")
+        if ranking_strategy not in ("best", "middle", "worst"):
+            raise ValueError("`ranking_strategy` must be 'worst', 'best' or 'middle', got {!r}.".format(ranking_strategy))
+        if not self.is_fitted:
+            raise ValueError("Model is not fitted.")
+        if use_filter is None:
+            use_filter = False
+        if not isinstance(use_filter, (bool, dict)):
+            raise ValueError("`use_filter` must be False, True or a dict of datasets.")
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or int(min_size) < 0:
+            raise ValueError("`min_size` must be a non-negative integer.")
+        if not self._placement.lists_supported:
+            self._placement.rank_typed(None, None, None, None, None, None)   # raises NotImplementedError before any device work
+        if types is None:
+            types = getattr(self, "relation_types_", None)
+            if types is None:
+                raise ValueError("evaluate_typed: no `types` given and the model has no relation_types_ (fit() with TypedNegatives binds them).")
+        if isinstance(types, RelationTypes):
+            types = types.bind(self, self._engine)
+        if not isinstance(types, BoundRelationTypes):
+            raise ValueError("`types` must be None, a RelationTypes or a bound one.")
+        if (types.n_ents, types.n_rels) != (self._n_ents, self._n_rels) or types.engine.device != self._engine.device:
+            raise ValueError("evaluate_typed: the bound relation types belong to another model.")
+        Xi = self._index_test(x)
+        sides = [sd for sd in ("s", "o") if sd in corrupt_side]
+        if Xi.shape[0] == 0:
+            return np.zeros((0, 1 if corrupt_side in ("s", "o", "s+o") else 2), dtype=np.int32)
+        fi = self._filter_index(use_filter, Xi)
+        r = self._placement.rank_typed(Xi, sides, types, fi, ranking_strategy, int(min_size)).cpu().numpy()
+        if corrupt_side == "s+o":
+            r = (r.sum(1, keepdims=True) - 1).astype(np.int32)
+        return r
 
     # ------------------------------------------------------------------------------------ accessors
     def is_fit(self):

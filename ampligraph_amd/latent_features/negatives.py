@@ -8,6 +8,9 @@ replacement entities (AmpliGraph 1.x's negative_corruption_entities) -- and `bin
 defined in include/amdkge_negatives.h) and hands the rows to the train step as its neg_override: the train kernels and the loss are
 the ones of the default path.
 
+`TypedNegatives` is a NegativeSampling whose replacements come from the positive's own relation's domain / range set
+(datasets/types.py; amdkge_sample_negatives_typed, include/amdkge_types.h): it binds to a `BoundTypedNegatives`, the same step.
+
 `SharedNegatives` is the other kind: one list of replacement entities per GROUP of positives, scored by a matrix product
 (kge_train_shared.hip).  It binds to a `BoundSharedNegatives`, whose step is engine.train_shared_fwdbwd instead of the override.
 """
@@ -48,6 +51,8 @@ class NegativeSampling:
             return spec
         if isinstance(spec, dict) and "shared" in spec:   # {"shared": M, ...}: SharedNegatives(num_negs=M, ...)
             return SharedNegatives.from_dict(spec)
+        if isinstance(spec, dict) and "types" in spec:    # {"types": "observed" | RelationTypes, ...}: TypedNegatives
+            return TypedNegatives.from_dict(spec)
         if isinstance(spec, dict):
             unknown = set(spec) - {"filter", "side", "entities", "max_tries"}
             if unknown:
@@ -61,6 +66,11 @@ class NegativeSampling:
 
     def bind(self, model, engine, train):
         """train: the int32 device tensor [n, 3] of id triples fit() slices its batches from -> BoundNegatives."""
+        index, pool = self._bind_parts(model, engine, train)
+        return BoundNegatives(engine, train, index, self.side, pool, self.max_tries, reject=self.filter is not False)
+
+    def _bind_parts(self, model, engine, train):
+        """(the FilterIndex over the known statements or None, the pool's int32 device ids or None)"""
         import torch
 
         N, R = int(model._n_ents), int(model._n_rels)
@@ -80,7 +90,7 @@ class NegativeSampling:
 
                 extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in self.filter.values()]
             index = FilterIndex([train] + extra, N, R, engine=engine)
-        return BoundNegatives(engine, train, index, self.side, pool, self.max_tries, reject=self.filter is not False)
+        return index, pool
 
 
 class BoundNegatives:
@@ -92,12 +102,14 @@ class BoundNegatives:
     the corruptions of rows [lo, hi) of the global batch, keyed by the GLOBAL row (row_offset = lo, b_global = the batch's size):
     every rank of a data-parallel run draws its own slice of the same rows."""
 
+    N_STATS = 2
+
     def __init__(self, engine, train, index, side, pool, max_tries, reject):
         self.engine, self.train, self.index = engine, train, index
         self.side, self.pool, self.max_tries = side, pool, int(max_tries)
         import torch
 
-        self.stats_dev = torch.zeros(2, dtype=torch.int64, device=engine.device)
+        self.stats_dev = torch.zeros(self.N_STATS, dtype=torch.int64, device=engine.device)
         self.s_filter = self.o_filter = self.side_thr = None
         if index is not None and reject:
             self.s_filter = index.device_filter(engine, train, "s")
@@ -115,18 +127,89 @@ class BoundNegatives:
             raise ValueError("negatives: the batch is not a row slice of the training tensor this sampler was bound to")
         return off // 3
 
-    def __call__(self, global_batch, lo, hi, eta, seed, step):
+    def _step_args(self, global_batch, lo, hi):
+        """(the batch rows, the keywords both samplers take, cut): cut slices a (lo, hi, ids) of all training rows to the batch's"""
         r0 = self._first_row(global_batch) + int(lo)
         r1 = r0 + int(hi) - int(lo)
         cut = lambda f: None if f is None else (f[0][r0:r1], f[1][r0:r1], f[2])   # noqa: E731
-        return self.engine.sample_negatives(global_batch[lo:hi], eta, seed, step, row_offset=lo, b_global=int(global_batch.shape[0]),
-                                            side=self.side, side_thr=self.side_thr, pool=self.pool, s_filter=cut(self.s_filter),
-                                            o_filter=cut(self.o_filter), max_tries=self.max_tries, stats=self.stats_dev)
+        kw = dict(row_offset=lo, b_global=int(global_batch.shape[0]), side=self.side, side_thr=self.side_thr, pool=self.pool,
+                  s_filter=cut(self.s_filter), o_filter=cut(self.o_filter), max_tries=self.max_tries, stats=self.stats_dev)
+        return global_batch[lo:hi], kw, cut
+
+    def __call__(self, global_batch, lo, hi, eta, seed, step):
+        rows, kw, _ = self._step_args(global_batch, lo, hi)
+        return self.engine.sample_negatives(rows, eta, seed, step, **kw)
 
     def stats(self):
         """{"redraws", "exhausted"} since the bind: one device read (synchronises the stream)."""
         rd, ex = (int(v) for v in self.stats_dev.tolist())
         return {"redraws": rd, "exhausted": ex}
+
+
+class TypedNegatives(NegativeSampling):
+    """Type-constrained negatives: a corruption of (s, p, o) replaces s by a member of p's DOMAIN or o by a member of p's RANGE
+    (PyKEEN's / LibKGE's type-constrained sampling, AmpliGraph 1.x's corruption_entities per relation, the local closed world of
+    Krompass et al. 2015) -- (s, born_in, ?) gets a place, not a film.
+
+    types: "observed" (the sets are the subjects / objects the training set shows with each relation) or a
+    datasets.types.RelationTypes (observed in more datasets, or explicit sets per relation label).
+    min_size: a relation whose set on the replaced side has fewer ids is corrupted by the untyped rule instead (every entity, or
+    `entities`); 2 by default, because a set of one entity can only reproduce the positive.
+    filter, side, entities, max_tries: NegativeSampling's -- rejection of known statements works inside the set as it does outside.
+
+    compile(negatives=TypedNegatives(...)) or compile(negatives={"types": ..., "filter": ..., "side": ..., "entities": ..., "max_tries": ...,
+    "min_size": ...}).  After fit(): model.relation_types_ (the bound sets, what evaluate_typed() takes by default) and
+    model.negative_sampling_stats_ with a third count, "untyped"."""
+
+    def __init__(self, types, filter=False, side="uniform", entities=None, max_tries=8, min_size=2):
+        from ..datasets.types import RelationTypes
+
+        super().__init__(filter, side, entities, max_tries)
+        if isinstance(types, str) and types == "observed":
+            types = RelationTypes.observed()
+        if not isinstance(types, RelationTypes):
+            raise ValueError("negatives: `types` must be 'observed' or a RelationTypes, got {!r}".format(types))
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or int(min_size) < 1:
+            raise ValueError("negatives: `min_size` must be an integer >= 1")
+        self.types, self.min_size = types, int(min_size)
+
+    @classmethod
+    def from_dict(cls, spec):
+        unknown = set(spec) - {"types", "filter", "side", "entities", "max_tries", "min_size"}
+        if unknown:
+            raise ValueError("negatives: unknown keys {} for typed negatives".format(sorted(unknown)))
+        return cls(**spec)
+
+    def get_config(self):
+        return dict(super().get_config(), types=self.types, min_size=self.min_size)
+
+    def bind(self, model, engine, train):
+        """-> BoundTypedNegatives: BoundNegatives' work plus the candidate ranges of ALL training rows, once"""
+        index, pool = self._bind_parts(model, engine, train)
+        return BoundTypedNegatives(engine, train, index, self.side, pool, self.max_tries, reject=self.filter is not False,
+                                   relation_types=self.types.bind(model, engine, train), min_size=self.min_size)
+
+
+class BoundTypedNegatives(BoundNegatives):
+    """BoundNegatives with the two candidate ranges of every training row (two lookups at bind time; a step slices them) and a
+    third counter.  relation_types: the BoundRelationTypes, which fit() publishes as model.relation_types_."""
+
+    N_STATS = 3
+
+    def __init__(self, engine, train, index, side, pool, max_tries, reject, relation_types, min_size):
+        super().__init__(engine, train, index, side, pool, max_tries, reject)
+        self.relation_types, self.min_size = relation_types, int(min_size)
+        self.s_cand = relation_types.ranges(train, "s", self.min_size, "none")
+        self.o_cand = relation_types.ranges(train, "o", self.min_size, "none")
+
+    def __call__(self, global_batch, lo, hi, eta, seed, step):
+        rows, kw, cut = self._step_args(global_batch, lo, hi)
+        return self.engine.sample_negatives_typed(rows, eta, seed, step, s_cand=cut(self.s_cand), o_cand=cut(self.o_cand), **kw)
+
+    def stats(self):
+        """{"redraws", "exhausted", "untyped"} since the bind: one device read (synchronises the stream)."""
+        rd, ex, ut = (int(v) for v in self.stats_dev.tolist())
+        return {"redraws": rd, "exhausted": ex, "untyped": ut}
 
 
 class SharedNegatives:

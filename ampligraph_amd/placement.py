@@ -31,6 +31,8 @@ def shard_file(filepath, rank, world):
 class Replicated:
     """The whole tables on every rank; evaluate() on several ranks splits the queries."""
 
+    lists_supported = True   # evaluate_candidates / evaluate_typed gather candidate rows from the whole table
+
     def __init__(self, m, dist, n_ents, n_rels, ent_rows, rel, batch_size=None):
         """ent_rows(lo, hi): dense rows [lo, hi) of the whole initial entity table; rel: the relation table."""
         self.m, self.dist, self.n_rels = m, dist, int(n_rels)
@@ -107,16 +109,20 @@ class Replicated:
     def rank(self, Xi, sides, fi, subset, strategy):
         """int32 device ranks (n, len(sides)) of the test triples Xi (global ids); fi: FilterIndex or None; subset: global
         ids of entities_subset or None."""
-        d, n = self.dist, Xi.shape[0]
+        return self._over_ranks(Xi.shape[0], len(sides), lambda a, b: self._rank(Xi[a:b], sides, fi, subset, strategy))
+
+    def _over_ranks(self, n, ncols, ranks_of):
+        """ranks_of(a, b) -> int32 device ranks (b - a, ncols) of the test triples [a, b).  One rank computes them all; several
+        ranks: every rank ranks its contiguous share of the test triples (the filters hold the whole data, so the ranks are
+        those of the single-GPU run) and the shares are gathered."""
+        d = self.dist
         if d is None or n < d.get_world_size():
-            return self._rank(Xi, sides, fi, subset, strategy)
-        # several ranks: every rank ranks its contiguous share of the test triples (the filters hold the whole data, so the
-        # ranks are those of the single-GPU run) and the shares are gathered
+            return ranks_of(0, n)
         W = d.get_world_size()
         bounds = [shard_bounds(n, W, q) for q in range(W)]
         lo, hi = bounds[d.get_rank()]
-        buf = torch.zeros(-(-n // W), len(sides), dtype=torch.int32, device=self.engine.device)
-        buf[:hi - lo] = self._rank(Xi[lo:hi], sides, fi, subset, strategy)
+        buf = torch.zeros(-(-n // W), ncols, dtype=torch.int32, device=self.engine.device)
+        buf[:hi - lo] = ranks_of(lo, hi)
         parts = [torch.empty_like(buf) for _ in range(W)]
         d.all_gather(parts, buf)
         return torch.cat([p[:b - a] for p, (a, b) in zip(parts, bounds)])
@@ -148,17 +154,7 @@ class Replicated:
         """int32 device ranks (n, len(sides_with_lists)) of the test triples Xi (global ids), each against its own candidates:
         sides_with_lists = [(side "s" | "o", (offsets int64 [n + 1], ids int32, max_len)), ...] (evaluation.candidates.as_csr, host
         arrays of global ids); fi: FilterIndex or None.  Several ranks share the triples exactly as rank() does."""
-        d, n = self.dist, Xi.shape[0]
-        if d is None or n < d.get_world_size():
-            return self._rank_candidates(Xi, sides_with_lists, fi, strategy, 0, n)
-        W = d.get_world_size()
-        bounds = [shard_bounds(n, W, q) for q in range(W)]
-        lo, hi = bounds[d.get_rank()]
-        buf = torch.zeros(-(-n // W), len(sides_with_lists), dtype=torch.int32, device=self.engine.device)
-        buf[:hi - lo] = self._rank_candidates(Xi, sides_with_lists, fi, strategy, lo, hi)
-        parts = [torch.empty_like(buf) for _ in range(W)]
-        d.all_gather(parts, buf)
-        return torch.cat([p[:b - a] for p, (a, b) in zip(parts, bounds)])
+        return self._over_ranks(Xi.shape[0], len(sides_with_lists), lambda a, b: self._rank_candidates(Xi, sides_with_lists, fi, strategy, a, b))
 
     def _rank_candidates(self, Xi, sides_with_lists, fi, strategy, a, b):
         """rank_candidates for the triples [a, b): chunks of at most 65 536 queries (as _rank) whose id lists stay under
@@ -183,6 +179,27 @@ class Replicated:
                 eng.rank_lists(xs, _ffi.SIDE_S if sd == "s" else _ffi.SIDE_O, cand, strategy, flt,
                                out=ranks[c0 - a:c1 - a, col], out_stride=len(sides_with_lists))
             c0 = c1
+        return ranks
+
+    # ---- ranks against the relation's domain / range set (evaluate_typed)
+    def rank_typed(self, Xi, sides, types, fi, strategy, min_size):
+        """int32 device ranks (n, len(sides)) of the test triples Xi (global ids), each against the set of its relation on that
+        side: types = a datasets.types.BoundRelationTypes, whose range lookup runs on the device (a set smaller than min_size, or
+        none: every entity).  Several ranks share the triples exactly as rank() does."""
+        return self._over_ranks(Xi.shape[0], len(sides), lambda a, b: self._rank_typed(Xi[a:b], sides, types, fi, strategy, min_size))
+
+    def _rank_typed(self, Xi, sides, types, fi, strategy, min_size):
+        eng = self.engine
+        Xd = torch.as_tensor(Xi).to(eng.device)
+        n = Xi.shape[0]
+        ranks = torch.empty(n, len(sides), dtype=torch.int32, device=eng.device)
+        CH = 1 << 16
+        for c0 in range(0, n, CH):
+            xs = Xd[c0:c0 + CH]
+            for col, sd in enumerate(sides):
+                cand = (*types.ranges(xs, sd, min_size, "all"), types.max_len)
+                flt = fi.device_filter(eng, xs, sd) if fi is not None else None
+                eng.rank_lists(xs, _ffi.SIDE_S if sd == "s" else _ffi.SIDE_O, cand, strategy, flt, out=ranks[c0:c0 + CH, col], out_stride=len(sides))
         return ranks
 
     # ---- relation prediction: the relation table is whole in every placement, so every rank computes every query
@@ -365,8 +382,13 @@ class Rows(Replicated):
                 eng.compose_ranks(counts, sub, strategy, out=ranks[c0:c0 + CH, col], out_stride=len(sides))
         return ranks
 
+    lists_supported = False
+
     def rank_candidates(self, Xi, sides_with_lists, fi, strategy):
         raise NotImplementedError(_LISTS_NEED_WHOLE_TABLE)
+
+    def rank_typed(self, Xi, sides, types, fi, strategy, min_size):
+        raise NotImplementedError(_LISTS_NEED_WHOLE_TABLE.replace("evaluate_candidates", "evaluate_typed"))
 
     def save(self, filepath, loop):
         """Rank r writes ITS rows of the entity table and of the optimizer slots to <filepath>.shardRRR-of-WWW.npz; rank 0
@@ -452,5 +474,10 @@ class Columns(Replicated):
         if self.callbacks_anywhere:
             self.publish()
 
+    lists_supported = False
+
     def rank_candidates(self, Xi, sides_with_lists, fi, strategy):
         raise NotImplementedError(_LISTS_NEED_WHOLE_TABLE)
+
+    def rank_typed(self, Xi, sides, types, fi, strategy, min_size):
+        raise NotImplementedError(_LISTS_NEED_WHOLE_TABLE.replace("evaluate_candidates", "evaluate_typed"))

@@ -746,5 +746,6 @@ int amdkge_session_group_rank(amdkge_session_group* g, const int32_t* triples, i
 }
 #endif
 #include "amdkge_lists.h"
+#include "amdkge_types.h"
 #include "amdkge_negatives.h"
 #endif /* AMDKGE_H */
