@@ -18,10 +18,14 @@
 //   shared_chain_kernel : a wave per positive.  With t_i = dQ_i + c_pos own_i = dL/dq_i, the gradients of the two kept rows are the
 //                         transpose of the query map applied to t_i, that of the replaced row's original is c_pos q_i; three
 //                         atomic row-adds per positive.
+//   shared_mask_kernel  : (include/amdkge_shared_mask.h, optional, between FWD and the loss) a wave per positive sets the scores of the
+//                         corruptions that are KNOWN statements to -inf, which every loss of loss_call already defines: no loss term, an
+//                         exact-zero coefficient, nothing for DQ / DE to add.
 // Groups are processed in chunks of at most CHUNK_SCORES scores, so the score buffer is bounded whatever B * M is.
 #include "kge_host.h"
 #include "kge_loss.h"
-#include "../../include/amdkge_shared.h"
+#include <string>
+#include "../../include/amdkge_shared_mask.h"
 
 namespace kge {
 
@@ -247,6 +251,71 @@ __global__ __launch_bounds__(256) void shared_loss_kernel(float* __restrict__ S,
     }
 }
 
+// ---- the mask of known statements (include/amdkge_shared_mask.h) ---------------------------------------------------------------------
+struct SharedMaskArgs {
+    float* S;              // [rows, M]: row r is batch row row0 + r
+    int64_t row0, rows, G;
+    int M;
+    const int32_t* ids;    // [n_groups, M]; not read in IDENTITY mode
+    const int32_t* side;   // the six below are indexed by batch row
+    const int64_t *s_lo, *s_hi, *o_lo, *o_hi;
+    const int32_t *s_ids, *o_ids;
+    int identity;
+    float fill;            // the buffer holds the plain sums: -inf, or +inf under a negative score scale
+    unsigned long long* stats;
+};
+
+// A wave per row.  GIVEN: lanes stride over j and look ids[g][j] up in the row's range.  A store cannot be undone and a FULLY KNOWN
+// row stays unmasked, so while every entry seen so far was a hit nothing is stored; the first miss (a wave-uniform event) stores the
+// whole prefix [0, j0) at once -- all of it was hits -- and from then on hits are stored where they are found: one search per entry.
+// IDENTITY: ids[g][j] == j, the hits are the range's ids below M; a strictly ascending range is fully known iff it has M of them.
+__global__ __launch_bounds__(256) void shared_mask_kernel(SharedMaskArgs a) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int64_t n_masked = 0, n_full = 0;   // (lane 0's are the wave's totals)
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wv; r < a.rows; r += (int64_t)gridDim.x * 4) {   // (wave-uniform)
+        const int64_t i = a.row0 + r;
+        const bool subj = a.side[i] != 0;
+        const int64_t lo = subj ? a.s_lo[i] : a.o_lo[i], hi = subj ? a.s_hi[i] : a.o_hi[i];
+        if (hi <= lo) continue;
+        const int32_t* __restrict__ kid = subj ? a.s_ids : a.o_ids;
+        float* s = a.S + r * a.M;
+        if (a.identity) {
+            int64_t b = lo, e = hi;   // the first id >= M
+            while (b < e) {
+                const int64_t mid = b + ((e - b) >> 1);
+                if (kid[mid] < a.M) b = mid + 1; else e = mid;
+            }
+            const int64_t c = b - lo;
+            if (c >= a.M) { ++n_full; continue; }
+            for (int64_t t = lo + lane; t < b; t += 64) {
+                const int id = kid[t];
+                if (id >= 0) s[id] = a.fill;
+            }
+            n_masked += c;
+            continue;
+        }
+        const int32_t* __restrict__ gid = a.ids + (i / a.G) * a.M;
+        bool all = true;
+        int cnt = 0;
+        for (int j0 = 0; j0 < a.M; j0 += 64) {   // (wave-uniform)
+            const int j = j0 + lane;
+            const bool in = j < a.M;
+            const bool hit = in && sorted_contains<int64_t>(kid, lo, hi, gid[j]);
+            if (all && __ballot(in && !hit) != 0ull) {
+                all = false;
+                for (int jj = lane; jj < j0; jj += 64) { s[jj] = a.fill; ++cnt; }
+            }
+            if (!all && hit) { s[j] = a.fill; ++cnt; }
+        }
+        if (all) ++n_full;
+        else n_masked += wave_sum_i(cnt);
+    }
+    if (a.stats && lane == 0) {
+        if (n_masked) atomicAdd(&a.stats[0], (unsigned long long)n_masked);
+        if (n_full) atomicAdd(&a.stats[1], (unsigned long long)n_full);
+    }
+}
+
 // ---- the transpose of the query map -------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void add_nz(float* p, float v) {
     if (v != 0.f) atomic_add_f32(p, v);
@@ -335,7 +404,7 @@ static bool shared_plan(const amdkge_model* m, int64_t B, int64_t G, int64_t M, 
 template <bool CPLX>
 static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int M,
                       const int32_t* d_ids, const int32_t* d_side, float* g_ent, float* g_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores,
-                      char* work, const SharedPlan& p, hipStream_t st) {
+                      char* work, const SharedPlan& p, const SharedMaskArgs* mask, hipStream_t st) {
     const int ks = stored_k(m), K = row_floats(m);
     const ModelConst mc = model_const(m);
     float* Q = reinterpret_cast<float*>(work + p.off_q);
@@ -362,6 +431,13 @@ static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const floa
         if (int rc = check_launch("shared_gemm_fwd")) return rc;
         int64_t lb = (rows + 3) / 4;
         if (lb > 2048) lb = 2048;
+        if (mask) {   // known statements -> -inf, on the chunk's own rows
+            SharedMaskArgs ma = *mask;
+            ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = G; ma.M = M; ma.ids = d_ids; ma.side = d_side;
+            ma.fill = mc.score_sign * mc.score_scale < 0.f ? INFINITY : -INFINITY;
+            hipLaunchKernelGGL(shared_mask_kernel, dim3((unsigned)lb), dim3(256), 0, st, ma);
+            if (int rc = check_launch("shared_mask")) return rc;
+        }
         hipLaunchKernelGGL(shared_loss_kernel, dim3((unsigned)lb), dim3(256), 0, st, S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum,
                            d_pos_scores, d_neg_scores);
         if (int rc = check_launch("shared_loss")) return rc;
@@ -409,9 +485,10 @@ extern "C" int64_t amdkge_train_shared_workspace_bytes(const amdkge_model* m, in
     return shared_plan(m, B, G, M, p) ? p.total : 0;
 }
 
-extern "C" int amdkge_train_shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
-                                          int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum,
-                                          float* d_pos_scores, float* d_neg_scores, void* d_work, void* stream) {
+// both step entry points: mask == nullptr is the unmasked step
+static int shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int32_t M,
+                         const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores,
+                         float* d_neg_scores, void* d_work, const SharedMaskArgs* mask, void* stream) {
     if (int rc = validate_model(m)) return rc;
     if (!shared_model_ok(m)) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: TransE and RotatE score a distance, not a contraction: only DistMult, ComplEx and HolE share negatives");
     if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_shared: unknown loss kind");
@@ -426,6 +503,56 @@ extern "C" int amdkge_train_shared_fwdbwd(const amdkge_model* m, const amdkge_lo
     hipStream_t st = (hipStream_t)stream;
     char* work = static_cast<char*>(d_work);
     if (m->scoring_type != AMDKGE_DISTMULT)   // ComplEx, and HolE on its instantiation (the 2/k scale travels in ModelConst)
-        return run_shared<true>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, st);
-    return run_shared<false>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, st);
+        return run_shared<true>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st);
+    return run_shared<false>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st);
+}
+
+extern "C" int amdkge_train_shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
+                                          int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum,
+                                          float* d_pos_scores, float* d_neg_scores, void* d_work, void* stream) {
+    return shared_fwdbwd(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work, nullptr, stream);
+}
+
+// the checks the two entry points of include/amdkge_shared_mask.h share; fills the part of the kernel's arguments that does not depend on the buffer
+static int shared_mask_args(const char* who, const int32_t* d_neg_ids, const int64_t* d_s_lo, const int64_t* d_s_hi, const int32_t* d_s_ids, const int64_t* d_o_lo,
+                            const int64_t* d_o_hi, const int32_t* d_o_ids, int32_t list_mode, int64_t* d_stats, bool ranges_required, SharedMaskArgs& a, bool& masked) {
+    const int given = (d_s_lo != nullptr) + (d_s_hi != nullptr) + (d_s_ids != nullptr) + (d_o_lo != nullptr) + (d_o_hi != nullptr) + (d_o_ids != nullptr);
+    if (given != 6 && (given != 0 || ranges_required)) return set_error(AMDKGE_EINVAL, (std::string(who) + (ranges_required ? ": the six range arrays are all required" : ": the six range arrays are given together or not at all")).c_str());
+    if (list_mode != AMDKGE_SHARED_LIST_GIVEN && list_mode != AMDKGE_SHARED_LIST_IDENTITY) return set_error(AMDKGE_EINVAL, (std::string(who) + ": unknown list_mode").c_str());
+    if (list_mode == AMDKGE_SHARED_LIST_GIVEN && !d_neg_ids) return set_error(AMDKGE_EINVAL, (std::string(who) + ": AMDKGE_SHARED_LIST_GIVEN needs d_neg_ids").c_str());
+    masked = given == 6;
+    a = SharedMaskArgs{};
+    a.s_lo = d_s_lo; a.s_hi = d_s_hi; a.s_ids = d_s_ids; a.o_lo = d_o_lo; a.o_hi = d_o_hi; a.o_ids = d_o_ids;
+    a.identity = list_mode == AMDKGE_SHARED_LIST_IDENTITY;
+    a.fill = -INFINITY;
+    a.stats = reinterpret_cast<unsigned long long*>(d_stats);
+    return AMDKGE_OK;
+}
+
+extern "C" int amdkge_shared_mask_scores(float* d_scores, int64_t row0, int64_t rows, int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side,
+                                         const int64_t* d_s_lo, const int64_t* d_s_hi, const int32_t* d_s_ids, const int64_t* d_o_lo, const int64_t* d_o_hi,
+                                         const int32_t* d_o_ids, int32_t list_mode, int64_t* d_stats, void* stream) {
+    if (row0 < 0 || rows < 0 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return set_error(AMDKGE_EINVAL, "shared_mask_scores: bad sizes (row0 >= 0, rows >= 0, G >= 1, 1 <= M < 2^24)");
+    if (!d_scores || !d_side) return set_error(AMDKGE_EINVAL, "shared_mask_scores: NULL scores / sides");
+    SharedMaskArgs a;
+    bool masked;
+    if (int rc = shared_mask_args("shared_mask_scores", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, d_stats, true, a, masked)) return rc;
+    if (rows == 0) return AMDKGE_OK;
+    a.S = d_scores; a.row0 = row0; a.rows = rows; a.G = G; a.M = M; a.ids = d_neg_ids; a.side = d_side;
+    int64_t lb = (rows + 3) / 4;
+    if (lb > 2048) lb = 2048;
+    hipLaunchKernelGGL(shared_mask_kernel, dim3((unsigned)lb), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("shared_mask_scores");
+}
+
+extern "C" int amdkge_train_shared_masked_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
+                                                 int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel,
+                                                 double* d_loss_sum, float* d_pos_scores, float* d_neg_scores, void* d_work, const int64_t* d_s_lo, const int64_t* d_s_hi,
+                                                 const int32_t* d_s_ids, const int64_t* d_o_lo, const int64_t* d_o_hi, const int32_t* d_o_ids, int32_t list_mode,
+                                                 int64_t* d_stats, void* stream) {
+    SharedMaskArgs a;
+    bool masked;
+    if (int rc = shared_mask_args("train_shared_masked", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, d_stats, false, a, masked)) return rc;
+    return shared_fwdbwd(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
+                         masked ? &a : nullptr, stream);
 }

@@ -483,6 +483,42 @@ class KgeEngine:
             C.byref(self.model), C.byref(loss), _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M, _ptr(ids), _ptr(side),
             _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work), _stream()))
 
+    def shared_mask_scores(self, scores, row0, group_size, ids, side, s_filter, o_filter, identity=False, stats=None):
+        """amdkge_shared_mask_scores (include/amdkge_shared_mask.h): the mask of the masked shared step alone, in place on the fp32
+        device tensor scores [rows, M] whose row r is batch row row0 + r.  side int32 [B]; ids int32 [ceil(B / group_size), M] (may
+        be None with identity=True, the promise that ids[g][j] == j); s_filter / o_filter: (lo, hi, ids) of the B positives
+        (FilterIndex.device_filter's form); stats: int64 [2] device tensor, += (masked, unmaskable)."""
+        rows, M = int(scores.shape[0]), int(scores.shape[1])
+        B = int(side.shape[0])
+        if int(row0) < 0 or int(row0) + rows > B or not scores.is_contiguous():
+            raise ValueError("shared_mask_scores: rows [row0, row0 + rows) must lie inside the batch and the buffer be contiguous")
+        G = max(1, min(int(group_size), B)) if int(group_size) >= 1 else int(group_size)
+        check(self.lib.amdkge_shared_mask_scores(
+            _ptr(scores), int(row0), rows, G, M, _ptr(ids), _ptr(side), _ptr(s_filter[0]), _ptr(s_filter[1]), _ptr(s_filter[2]),
+            _ptr(o_filter[0]), _ptr(o_filter[1]), _ptr(o_filter[2]), _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
+        return scores
+
+    def train_shared_masked_fwdbwd(self, triples, group_size, num_negs, ids, side, loss, s_filter=None, o_filter=None, identity=False, stats=None,
+                                   pos_scores=None, neg_scores=None):
+        """amdkge_train_shared_masked_fwdbwd: train_shared_fwdbwd in which the score of a corruption whose replacement is in the
+        positive's known range -- s_filter / o_filter: (lo, hi, ids) of the B positives, both or neither -- is -inf before the loss;
+        a positive whose whole list is known keeps its row.  identity: the promise that ids[g][j] == j (the all-entities list);
+        stats: int64 [2] device tensor, += (masked, unmaskable).  Without the filters it is train_shared_fwdbwd."""
+        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
+        if (s_filter is None) != (o_filter is None):
+            raise ValueError("train_shared_masked_fwdbwd: s_filter and o_filter are given together or not at all")
+        need = int(self.lib.amdkge_train_shared_workspace_bytes(C.byref(self.model), B, G, M)) if B > 0 else 0
+        if B > 0 and need <= 0:
+            raise ValueError("train_shared_masked_fwdbwd: shared negatives are not offered for this model / shape "
+                             f"({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
+        work = self._buf("shared_work", (need,), torch.uint8)
+        sf, of = s_filter or (None, None, None), o_filter or (None, None, None)
+        check(self.lib.amdkge_train_shared_masked_fwdbwd(
+            C.byref(self.model), C.byref(loss), _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M, _ptr(ids), _ptr(side),
+            _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work),
+            _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]),
+            _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
+
     def negatives_side_thresholds(self, po_keys, sp_keys, n_ents=None, n_rels=None):
         """amdkge_negatives_side_thresholds: the Bernoulli thresholds floor(2^32 G_po / (G_sp + G_po)) per relation from a
         FilterIndex's two int64 device key arrays -> int32 device tensor [n_rels] holding the uint32 bit patterns."""

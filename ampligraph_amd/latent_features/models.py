@@ -118,7 +118,9 @@ class ScoringBasedEmbeddingModel:
         form {"types": "observed" | RelationTypes, "filter", "side", "entities", "max_tries", "min_size"} (type-constrained: a
         corruption replaces the subject / object by a member of the relation's domain / range set, datasets/types.py; replicated
         tables only; model.relation_types_ after fit(), which evaluate_typed() ranks against) | SharedNegatives | its dict
-        form {"shared": num_negs, "group_size", "side", "entities"} (groups of positives share one list of replacements, scored by a
+        form {"shared": num_negs | "all", "group_size", "side", "entities", "mask_known"} (mask_known: False | True | dict of datasets -- the
+        scores of corruptions that are known statements are -inf before the loss; "all": every list is every entity, 1-vs-all training;
+        model.negative_sampling_stats_ = {"masked", "unmaskable"} after fit(); groups of positives share one list of replacements, scored by a
         matrix product: DistMult / ComplEx / HolE on one GPU, no deterministic, lazy or FocusE mode).  Multi-GPU, one process per GPU under torch.distributed:
         entity_sharding="replicated" (default: tables replicated, gradient all-reduce) | "rows" (entity table
         row-sharded over the ranks, ampligraph_amd/sharded.py; sharded_negatives="local" | "global" chooses where its corruptions

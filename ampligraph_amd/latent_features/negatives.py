@@ -12,7 +12,9 @@ the ones of the default path.
 (datasets/types.py; amdkge_sample_negatives_typed, include/amdkge_types.h): it binds to a `BoundTypedNegatives`, the same step.
 
 `SharedNegatives` is the other kind: one list of replacement entities per GROUP of positives, scored by a matrix product
-(kge_train_shared.hip).  It binds to a `BoundSharedNegatives`, whose step is engine.train_shared_fwdbwd instead of the override.
+(kge_train_shared.hip).  It binds to a `BoundSharedNegatives`, whose step is engine.train_shared_fwdbwd instead of the override; with
+`mask_known` to a `BoundMaskedSharedNegatives`, whose step is engine.train_shared_masked_fwdbwd (include/amdkge_shared_mask.h: the
+scores of corruptions that are known statements are -inf before the loss).  num_negs="all" makes every list every entity.
 """
 import numpy as np
 
@@ -219,42 +221,65 @@ class SharedNegatives:
     the scores of a group are one matrix product on the matrix cores and a positive costs three row reads whatever `num_negs` is
     (include/amdkge_shared.h, kge_train_shared.hip).  DistMult, ComplEx and HolE only.
 
-    num_negs: corruptions per positive, 1 .. 2^24 - 1.  group_size: None (= num_negs) or the positives per group.
+    num_negs: corruptions per positive, 1 .. 2^24 - 1, or "all": every group's list is EVERY entity in id order (or the `entities`
+    pool in the order given), only the sides are drawn -- 1-vs-all training; with multiclass_nll and mask_known the filtered softmax
+    cross-entropy.  group_size: the positives per group; None = num_negs, or ALL_GROUP_SIZE = 4 096 with "all" (the result then does
+    not depend on it: it only sets how the matrix products are cut, and the score buffer's 4 * group_size * N bytes -- lower it for a
+    large entity table).
     side: "uniform" | "bernoulli" | "s" | "o", decided per POSITIVE.  entities: None or the labels replacements are drawn from.
+    mask_known: False | True (the training set) | a non-empty dict of datasets in the form NegativeSampling(filter=...) takes
+    (known next to the training set).  The score of a corruption that is a known statement -- the positive itself among them --
+    is set to -inf before the loss (PyTorch-BigGraph's masking): it adds no loss term and gets no gradient, the reduction
+    divisors stay; a positive whose WHOLE list is known keeps its row (include/amdkge_shared_mask.h).  After fit():
+    model.negative_sampling_stats_ = {"masked", "unmaskable"}.
     There is no `filter`: a rejection per positive would give every positive its own list.
 
-    compile(negatives=SharedNegatives(...)) or compile(negatives={"shared": num_negs, "group_size": ..., "side": ..., "entities": ...})."""
+    compile(negatives=SharedNegatives(...)) or compile(negatives={"shared": num_negs | "all", "group_size": ..., "side": ...,
+    "entities": ..., "mask_known": ...})."""
 
     shared = True   # what trainer.StepLoop.step looks for
+    ALL_GROUP_SIZE = 4096   # measured (DESIGN section 5): the products want >= 4 096 rows per chunk; the score buffer is 4 * group_size * num_negs bytes
 
-    def __init__(self, num_negs, group_size=None, side="uniform", entities=None):
+    def __init__(self, num_negs, group_size=None, side="uniform", entities=None, mask_known=False):
         def count(v, name, hi):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
                 raise ValueError("negatives: `{}` must be an integer in [1, {}]".format(name, hi))
             return int(v)
 
-        self.num_negs = count(num_negs, "num_negs", _ffi.SHARED_MAX_NEGS)
-        self.group_size = self.num_negs if group_size is None else count(group_size, "group_size", 2 ** 31 - 1)
+        if isinstance(num_negs, str):
+            if num_negs != "all":
+                raise ValueError("negatives: `num_negs` must be an integer in [1, {}] or 'all', got {!r}".format(_ffi.SHARED_MAX_NEGS, num_negs))
+            self.num_negs = "all"
+        else:
+            self.num_negs = count(num_negs, "num_negs", _ffi.SHARED_MAX_NEGS)
+        default_g = self.ALL_GROUP_SIZE if self.num_negs == "all" else self.num_negs
+        self.group_size = default_g if group_size is None else count(group_size, "group_size", 2 ** 31 - 1)
         if not isinstance(side, str) or side not in _ffi.NEG_SIDE_MODES:
             raise ValueError("negatives: `side` must be 'uniform', 'bernoulli', 's' or 'o', got {!r}".format(side))
         if entities is not None:
             if isinstance(entities, (str, bytes)) or np.ndim(entities) != 1 or len(entities) < 1:
                 raise ValueError("negatives: `entities` must be None or a non-empty 1-D sequence of entity labels")
             entities = np.asarray(entities)
+        if not (isinstance(mask_known, (bool, np.bool_)) or (isinstance(mask_known, dict) and len(mask_known) > 0)):
+            raise ValueError("negatives: `mask_known` must be False, True or a non-empty dict of datasets")
         self.side, self.entities = side, entities
+        self.mask_known = mask_known if isinstance(mask_known, dict) else bool(mask_known)
 
     @classmethod
     def from_dict(cls, spec):
         if "filter" in spec and spec["filter"] is not False:
             raise ValueError("negatives: shared negatives take no `filter`: a rejection per positive breaks the sharing")
-        unknown = set(spec) - {"shared", "group_size", "side", "entities", "filter"}
+        unknown = set(spec) - {"shared", "group_size", "side", "entities", "filter", "mask_known"}
         if unknown:
             raise ValueError("negatives: unknown keys {} for shared negatives".format(sorted(unknown)))
-        return cls(spec["shared"], spec.get("group_size"), spec.get("side", "uniform"), spec.get("entities"))
+        return cls(spec["shared"], spec.get("group_size"), spec.get("side", "uniform"), spec.get("entities"), spec.get("mask_known", False))
 
     def get_config(self):
-        """The dict form compile(negatives=...) takes (labels as given)."""
-        return {"shared": self.num_negs, "group_size": self.group_size, "side": self.side, "entities": self.entities}
+        """The dict form compile(negatives=...) takes (labels and datasets as given; `mask_known` only when it is set)."""
+        cfg = {"shared": self.num_negs, "group_size": self.group_size, "side": self.side, "entities": self.entities}
+        if self.mask_known is not False:
+            cfg["mask_known"] = self.mask_known
+        return cfg
 
     def check_model(self, model, optimizer_mode="dense"):
         """compile()'s refusals: everything that is known before a GPU is touched."""
@@ -285,23 +310,76 @@ class SharedNegatives:
             if ids.min() < 0 or ids.max() >= N:   # the train kernels do not check the ids
                 raise ValueError("negatives: entity ids outside [0, {})".format(N))
             pool = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32)).to(engine.device)
-        side_thr = None
-        if self.side == "bernoulli":
-            index = FilterIndex([train], N, R, engine=engine)
+        index, side_thr = None, None
+        if self.mask_known is not False or self.side == "bernoulli":
+            extra = []
+            if isinstance(self.mask_known, dict):
+                from .models import _load_triples
+
+                extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in self.mask_known.values()]
+            index = FilterIndex([train] + extra, N, R, engine=engine)
+        if self.side == "bernoulli":   # (thresholds over the index's statements: the training set, and the mask's datasets when given)
             side_thr = engine.negatives_side_thresholds(*index.device_keys(engine), index.n_ents, index.n_rels)
-        return BoundSharedNegatives(engine, self.num_negs, self.group_size, self.side, side_thr, pool)
+        num_negs, all_list = self.num_negs, None
+        if num_negs == "all":   # the list every group shares: every entity in id order, or the pool in the order given
+            all_list = pool if pool is not None else torch.arange(N, dtype=torch.int32, device=engine.device)
+            num_negs = int(all_list.numel())
+            if num_negs > _ffi.SHARED_MAX_NEGS:
+                raise ValueError("negatives: 'all' needs at most {} entities".format(_ffi.SHARED_MAX_NEGS))
+        if self.mask_known is False:
+            return BoundSharedNegatives(engine, num_negs, self.group_size, self.side, side_thr, pool, all_list=all_list)
+        return BoundMaskedSharedNegatives(engine, num_negs, self.group_size, self.side, side_thr, pool, all_list=all_list, train=train, index=index,
+                                          identity=all_list is not None and pool is None)
 
 
 class BoundSharedNegatives:
     """A SharedNegatives bound to one fit().  trainer.StepLoop.step calls draw(global_batch, seed, step) -> (ids int32
-    [n_groups, num_negs], side int32 [B]) and hands both to engine.train_shared_fwdbwd."""
+    [n_groups, num_negs], side int32 [B]) and hands both to engine.train_shared_fwdbwd.  all_list: None, or the int32 device list
+    [num_negs] of num_negs="all": every group's row of ids is that list -- the id tensor is built once (and again only for a batch
+    with more groups than any before), a step draws the sides alone."""
 
     shared = True
 
-    def __init__(self, engine, num_negs, group_size, side, side_thr, pool):
+    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list=None):
         self.engine, self.num_negs, self.group_size = engine, int(num_negs), int(group_size)
         self.side, self.side_thr, self.pool = side, side_thr, pool
+        self.all_list, self._all_ids = all_list, None
 
     def draw(self, global_batch, seed, step):
-        return self.engine.sample_shared(global_batch, self.group_size, self.num_negs, seed, step, side=self.side,
-                                         side_thr=self.side_thr, pool=self.pool)
+        if self.all_list is None:
+            return self.engine.sample_shared(global_batch, self.group_size, self.num_negs, seed, step, side=self.side,
+                                             side_thr=self.side_thr, pool=self.pool)
+        B = int(global_batch.shape[0])
+        n_groups = -(-B // min(self.group_size, B)) if B > 0 else 0
+        if self._all_ids is None or int(self._all_ids.shape[0]) < n_groups:
+            self._all_ids = self.all_list.reshape(1, -1).repeat(n_groups, 1).contiguous()
+        # the side of a positive does not depend on the list's length (include/amdkge_shared.h, THE DRAW): one id per group is drawn and dropped
+        _, side = self.engine.sample_shared(global_batch, self.group_size, 1, seed, step, side=self.side, side_thr=self.side_thr)
+        return self._all_ids[:n_groups], side
+
+
+class BoundMaskedSharedNegatives(BoundSharedNegatives):
+    """BoundSharedNegatives with the mask of known statements: the FilterIndex over the training set (and mask_known's datasets) and
+    the range arrays of ALL training rows -- two range lookups at bind time, as in BoundNegatives; mask(global_batch) slices them.
+    trainer.StepLoop.step hands them to engine.train_shared_masked_fwdbwd with `identity` (the list is 0 .. N - 1) and `stats_dev`."""
+
+    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity):
+        import torch
+
+        super().__init__(engine, num_negs, group_size, side, side_thr, pool, all_list=all_list)
+        self.train, self.index, self.identity = train, index, bool(identity)
+        self.stats_dev = torch.zeros(2, dtype=torch.int64, device=engine.device)
+        self.s_filter = index.device_filter(engine, train, "s")
+        self.o_filter = index.device_filter(engine, train, "o")
+
+    def mask(self, global_batch):
+        """-> (s_filter, o_filter) of the batch's rows: (lo, hi, ids) each"""
+        r0 = BoundNegatives._first_row(self, global_batch)
+        r1 = r0 + int(global_batch.shape[0])
+        return tuple((f[0][r0:r1], f[1][r0:r1], f[2]) for f in (self.s_filter, self.o_filter))
+
+    def stats(self):
+        """{"masked", "unmaskable"} since the bind -- the corruption scores set to -inf and the positives whose whole list was known
+        (left unmasked): one device read (synchronises the stream)."""
+        mk, un = (int(v) for v in self.stats_dev.tolist())
+        return {"masked": mk, "unmaskable": un}

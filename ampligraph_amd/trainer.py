@@ -126,7 +126,8 @@ class StepLoop:
         # compile(negatives=...): None (the train kernels draw their own corruptions) or a callable(global_batch, lo, hi, eta, seed,
         # rng_step) -> int32 device rows [(hi - lo) * eta, 3], the corruptions of rows [lo, hi) of the global batch drawn by GLOBAL
         # row (latent_features/negatives.py: BoundNegatives), which the step hands to the train kernels as their override; or an object
-        # with `.shared` set (BoundSharedNegatives: .draw(), .group_size, .num_negs), whose step is engine.train_shared_fwdbwd
+        # with `.shared` set (BoundSharedNegatives: .draw(), .group_size, .num_negs), whose step is engine.train_shared_fwdbwd -- or, when
+        # it has a .mask() (BoundMaskedSharedNegatives), engine.train_shared_masked_fwdbwd
         self.negatives = None
         engine.prepare_training(optimizer.name)
         if hasattr(optimizer, "bind"):
@@ -183,7 +184,13 @@ class StepLoop:
             if bg > 0:
                 sh = self.negatives
                 ids, side = sh.draw(global_batch, self.seed, rng_step)
-                eng.train_shared_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi)
+                mask = getattr(sh, "mask", None)   # BoundMaskedSharedNegatives: known statements score -inf (kge_train_shared.hip, shared_mask_kernel)
+                if mask is None:
+                    eng.train_shared_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi)
+                else:
+                    s_filter, o_filter = mask(global_batch)
+                    eng.train_shared_masked_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi, s_filter=s_filter, o_filter=o_filter,
+                                                   identity=bool(getattr(sh, "identity", False)), stats=getattr(sh, "stats_dev", None))
             if self.kernel_hook is not None:
                 self.kernel_hook(1)
             eng.opt_step(opt_ffi, lam, lam_r)

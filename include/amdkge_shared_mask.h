@@ -1,0 +1,77 @@
+/* libamdkge -- extension header: SHARED-NEGATIVE TRAINING WITH KNOWN STATEMENTS MASKED (and the all-entities list).
+ *
+ * An extension header like include/amdkge_shared.h: entry points ADDED to ABI version 5 without changing one of amdkge.h's or
+ * amdkge_shared.h's, bound through ampligraph_amd/_ffi.py's SHARED_MASK_SIGNATURES table.  The ABI version stays 5.
+ *
+ * THE MASKED STEP.  Given the shared step of include/amdkge_shared.h (B positives, groups of G, lists ids[g][0 .. M), side[i]) and
+ * for every positive i the ascending id range
+ *     known_i = d_s_ids[d_s_lo[i] .. d_s_hi[i])   the subjects known with (p_i, o_i)   when side[i] != 0 (the subject is replaced)
+ *             = d_o_ids[d_o_lo[i] .. d_o_hi[i])   the objects known with (s_i, p_i)    otherwise
+ * -- what amdkge_filter_ranges returns and amdkge_sample_negatives takes as the same six arrays --, the masked step is the shared
+ * step in which the SCORE of corruption (i, j) is replaced by -inf before Loss.__call__ whenever ids[i / G][j] is in known_i
+ * (PyTorch-BigGraph's treatment of batch negatives that are true statements: masked, not redrawn, so the sharing stays).
+ *   - Every loss is already defined at a score of -inf (kge_loss.h): no loss term, an exact-zero coefficient, no NaN; the masked
+ *     corruption receives no gradient and sends none.
+ *   - The reduction divisors do not change: "mean" still divides by M (by 2 M for nll).  multiclass_nll clips its scores to
+ *     [-75, 75] before the exponential, so a masked entry still adds e^-75 / red to the partition sum Z (2.7e-33: nothing in fp32
+ *     next to a live term).
+ *   - When the positives themselves are in the index, a positive's own entity is known: the identity corruption is masked too.
+ *   - ONE EXCEPTION: a positive whose M entries are ALL known keeps its whole row unmasked (self_adversarial would otherwise form
+ *     -inf - (-inf)); the rule is the same for every loss.
+ *   - d_stats: NULL, or int64 [2], += (masked entries, rows left unmasked by the exception).  Integer adds: order-free.
+ * An absent key is the empty range (0, 0): such a row is left alone.  Ids ascend STRICTLY inside a range (the filter index build's
+ * order: a set).
+ *
+ * THE ALL-ENTITIES LIST needs no step of its own: it is this step (or the unmasked one) with ids[g][j] = j and M = N, or with a
+ * pool's ids in the order given.  AMDKGE_SHARED_LIST_IDENTITY tells the mask that ids[g][j] == j, so that it can store at the
+ * known ids directly (|known_i| stores) instead of searching known_i for each of the M entries.
+ */
+#ifndef AMDKGE_SHARED_MASK_H
+#define AMDKGE_SHARED_MASK_H
+
+#include "amdkge_shared.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* list_mode */
+enum {
+    AMDKGE_SHARED_LIST_GIVEN = 0,     /* d_neg_ids holds the lists */
+    AMDKGE_SHARED_LIST_IDENTITY = 1   /* a PROMISE that ids[g][j] == j for every g (not checked): the mask does not read d_neg_ids,
+                                         and ids >= M of a range are ignored */
+};
+
+/* The mask alone, on a caller's score buffer: d_scores [rows, M] fp32, row r = batch row row0 + r; the entries (r, j) with
+ * ids[(row0 + r) / G][j] in known_(row0 + r) are set to -inf, every other entry is left untouched (bit for bit), a fully known row
+ * is left untouched and counted.  d_side and the four lo / hi arrays are indexed by BATCH row (at least row0 + rows of them),
+ * d_neg_ids is int32 [ceil(B / G), M] of the whole batch; G is taken as given (the caller has applied G = min(G, B)).
+ * d_neg_ids may be NULL with AMDKGE_SHARED_LIST_IDENTITY.
+ * Errors (before any launch): AMDKGE_EINVAL for a NULL d_scores / d_side, row0 < 0, rows < 0, G < 1, M out of
+ * [1, AMDKGE_SHARED_MAX_NEGS], the six range arrays not ALL given, an unknown list_mode, a NULL d_neg_ids in GIVEN mode.
+ * rows == 0: nothing is done. */
+int amdkge_shared_mask_scores(float* d_scores, int64_t row0, int64_t rows, int64_t G, int32_t M,
+                              const int32_t* d_neg_ids, const int32_t* d_side,
+                              const int64_t* d_s_lo, const int64_t* d_s_hi, const int32_t* d_s_ids,
+                              const int64_t* d_o_lo, const int64_t* d_o_hi, const int32_t* d_o_ids,
+                              int32_t list_mode, int64_t* d_stats, void* stream);
+
+/* amdkge_train_shared_fwdbwd with the mask applied between the score product and the loss.  Arguments, outputs, workspace
+ * (amdkge_train_shared_workspace_bytes) and error rules are that entry point's; d_neg_scores (optional) shows -inf at the masked
+ * entries.  The six range arrays are int64 [B] / int32, all six set or all six NULL; with all six NULL this IS the
+ * unmasked step of amdkge_shared.h: list_mode is still validated, d_stats is not touched.  Even with AMDKGE_SHARED_LIST_IDENTITY the
+ * matrix products gather by d_neg_ids: it must hold the lists.
+ * Additional errors (before any launch): AMDKGE_EINVAL for the six arrays given in part, an unknown list_mode, a NULL d_neg_ids
+ * in GIVEN mode. */
+int amdkge_train_shared_masked_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel,
+                                      const int32_t* d_triples, int64_t B, int64_t G, int32_t M,
+                                      const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel,
+                                      double* d_loss_sum, float* d_pos_scores, float* d_neg_scores, void* d_work,
+                                      const int64_t* d_s_lo, const int64_t* d_s_hi, const int32_t* d_s_ids,
+                                      const int64_t* d_o_lo, const int64_t* d_o_hi, const int32_t* d_o_ids,
+                                      int32_t list_mode, int64_t* d_stats, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* AMDKGE_SHARED_MASK_H */
