@@ -195,6 +195,13 @@ SHARED_MASK_SIGNATURES = {
                                                     P, P, P, P, P, P, I32, P, P]),
 }
 
+# include/amdkge_shared_dist.h (shared negatives for the distance models, TransE and RotatE, on distance tiles): again a table of its own
+SHARED_DIST_SIGNATURES = {
+    "amdkge_train_shared_dist_workspace_bytes": (I64, [C.POINTER(Model), I64, I64, I32]),
+    "amdkge_train_shared_dist_fwdbwd": (C.c_int, [C.POINTER(Model), C.POINTER(Loss), P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P,
+                                                  P, P, P, P, P, P, I32, P, P]),
+}
+
 # include/amdkge_types.h (type-constrained negatives and evaluation: per-relation domain / range sets): again a table of its own
 TYPES_SIGNATURES = {
     "amdkge_relation_sets_build": (C.c_int, [P, I64, I32, I64, I64, P, P, P, P, P, P]),
@@ -219,7 +226,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(SHARED_SIGNATURES.items()) + list(SHARED_MASK_SIGNATURES.items()) + list(TYPES_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(SHARED_SIGNATURES.items()) + list(SHARED_MASK_SIGNATURES.items()) + list(SHARED_DIST_SIGNATURES.items()) + list(TYPES_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -22,15 +22,13 @@
 //                         corruptions that are KNOWN statements to -inf, which every loss of loss_call already defines: no loss term, an
 //                         exact-zero coefficient, nothing for DQ / DE to add.
 // Groups are processed in chunks of at most CHUNK_SCORES scores, so the score buffer is bounded whatever B * M is.
-#include "kge_host.h"
+#include "kge_train_shared.h"
 #include "kge_loss.h"
 #include <string>
-#include "../../include/amdkge_shared_mask.h"
 
 namespace kge {
 
 constexpr uint32_t SHARED_TAG_IDS = 0xF0u << 24, SHARED_TAG_SIDE = 0xF1u << 24;
-constexpr int64_t CHUNK_SCORES = 1ll << 24;
 
 struct SharedDrawArgs {
     const int32_t* triples;
@@ -252,18 +250,6 @@ __global__ __launch_bounds__(256) void shared_loss_kernel(float* __restrict__ S,
 }
 
 // ---- the mask of known statements (include/amdkge_shared_mask.h) ---------------------------------------------------------------------
-struct SharedMaskArgs {
-    float* S;              // [rows, M]: row r is batch row row0 + r
-    int64_t row0, rows, G;
-    int M;
-    const int32_t* ids;    // [n_groups, M]; not read in IDENTITY mode
-    const int32_t* side;   // the six below are indexed by batch row
-    const int64_t *s_lo, *s_hi, *o_lo, *o_hi;
-    const int32_t *s_ids, *o_ids;
-    int identity;
-    float fill;            // the buffer holds the plain sums: -inf, or +inf under a negative score scale
-    unsigned long long* stats;
-};
 
 // A wave per row.  GIVEN: lanes stride over j and look ids[g][j] up in the row's range.  A store cannot be undone and a FULLY KNOWN
 // row stays unmasked, so while every entry seen so far was a hit nothing is stored; the first miss (a wave-uniform event) stores the
@@ -379,10 +365,7 @@ static int64_t shared_chunk_groups(int64_t n_groups, int64_t G, int64_t M) {
     if (gpc < 1) gpc = 1;
     return gpc < n_groups ? gpc : n_groups;
 }
-struct SharedPlan {
-    int64_t n_groups, gpc, off_q, off_dq, off_pos, off_cpos, off_s, total;
-};
-static bool shared_plan(const amdkge_model* m, int64_t B, int64_t G, int64_t M, SharedPlan& p) {
+bool shared_plan(const amdkge_model* m, int64_t B, int64_t G, int64_t M, SharedPlan& p) {
     if (B < 1 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return false;
     if (G > B) G = B;
     if (G > (1ll << 40) / M) return false;   // (G * M stays far inside 64 bits)
@@ -399,6 +382,21 @@ static bool shared_plan(const amdkge_model* m, int64_t B, int64_t G, int64_t M, 
     p.off_s = off; off += align256(rows * M * 4);
     p.total = off;
     return true;
+}
+
+int launch_shared_mask(const SharedMaskArgs& a, hipStream_t st) {
+    int64_t lb = (a.rows + 3) / 4;
+    if (lb > 2048) lb = 2048;
+    hipLaunchKernelGGL(shared_mask_kernel, dim3((unsigned)lb), dim3(256), 0, st, a);
+    return check_launch("shared_mask");
+}
+
+int launch_shared_loss(float* S, const float* pos_raw, float* cpos, int64_t row0, int64_t rows, int64_t B, int M, const amdkge_loss& L, float scale, double* loss_sum,
+                       float* pos_scores, float* neg_scores, hipStream_t st) {
+    int64_t lb = (rows + 3) / 4;
+    if (lb > 2048) lb = 2048;
+    hipLaunchKernelGGL(shared_loss_kernel, dim3((unsigned)lb), dim3(256), 0, st, S, pos_raw, cpos, row0, rows, B, M, L, scale, loss_sum, pos_scores, neg_scores);
+    return check_launch("shared_loss");
 }
 
 template <bool CPLX>
@@ -429,18 +427,13 @@ static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const floa
         a.tiles_m = tg; a.tiles_n = tm;
         hipLaunchKernelGGL(shared_gemm_kernel<GEMM_FWD>, dim3((unsigned)nb_fwd), dim3(256), 0, st, a);
         if (int rc = check_launch("shared_gemm_fwd")) return rc;
-        int64_t lb = (rows + 3) / 4;
-        if (lb > 2048) lb = 2048;
         if (mask) {   // known statements -> -inf, on the chunk's own rows
             SharedMaskArgs ma = *mask;
             ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = G; ma.M = M; ma.ids = d_ids; ma.side = d_side;
             ma.fill = mc.score_sign * mc.score_scale < 0.f ? INFINITY : -INFINITY;
-            hipLaunchKernelGGL(shared_mask_kernel, dim3((unsigned)lb), dim3(256), 0, st, ma);
-            if (int rc = check_launch("shared_mask")) return rc;
+            if (int rc = launch_shared_mask(ma, st)) return rc;
         }
-        hipLaunchKernelGGL(shared_loss_kernel, dim3((unsigned)lb), dim3(256), 0, st, S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum,
-                           d_pos_scores, d_neg_scores);
-        if (int rc = check_launch("shared_loss")) return rc;
+        if (int rc = launch_shared_loss(S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum, d_pos_scores, d_neg_scores, st)) return rc;
         a.tiles_m = tg; a.tiles_n = tk;
         hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DQ>, dim3((unsigned)nb_dq), dim3(256), 0, st, a);
         if (int rc = check_launch("shared_gemm_dq")) return rc;
@@ -513,8 +506,8 @@ extern "C" int amdkge_train_shared_fwdbwd(const amdkge_model* m, const amdkge_lo
     return shared_fwdbwd(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work, nullptr, stream);
 }
 
-// the checks the two entry points of include/amdkge_shared_mask.h share; fills the part of the kernel's arguments that does not depend on the buffer
-static int shared_mask_args(const char* who, const int32_t* d_neg_ids, const int64_t* d_s_lo, const int64_t* d_s_hi, const int32_t* d_s_ids, const int64_t* d_o_lo,
+// (declared in kge_train_shared.h)
+int kge::shared_mask_args(const char* who, const int32_t* d_neg_ids, const int64_t* d_s_lo, const int64_t* d_s_hi, const int32_t* d_s_ids, const int64_t* d_o_lo,
                             const int64_t* d_o_hi, const int32_t* d_o_ids, int32_t list_mode, int64_t* d_stats, bool ranges_required, SharedMaskArgs& a, bool& masked) {
     const int given = (d_s_lo != nullptr) + (d_s_hi != nullptr) + (d_s_ids != nullptr) + (d_o_lo != nullptr) + (d_o_hi != nullptr) + (d_o_ids != nullptr);
     if (given != 6 && (given != 0 || ranges_required)) return set_error(AMDKGE_EINVAL, (std::string(who) + (ranges_required ? ": the six range arrays are all required" : ": the six range arrays are given together or not at all")).c_str());
@@ -539,10 +532,7 @@ extern "C" int amdkge_shared_mask_scores(float* d_scores, int64_t row0, int64_t 
     if (int rc = shared_mask_args("shared_mask_scores", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, d_stats, true, a, masked)) return rc;
     if (rows == 0) return AMDKGE_OK;
     a.S = d_scores; a.row0 = row0; a.rows = rows; a.G = G; a.M = M; a.ids = d_neg_ids; a.side = d_side;
-    int64_t lb = (rows + 3) / 4;
-    if (lb > 2048) lb = 2048;
-    hipLaunchKernelGGL(shared_mask_kernel, dim3((unsigned)lb), dim3(256), 0, (hipStream_t)stream, a);
-    return check_launch("shared_mask_scores");
+    return launch_shared_mask(a, (hipStream_t)stream);
 }
 
 extern "C" int amdkge_train_shared_masked_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,

@@ -519,6 +519,31 @@ class KgeEngine:
             _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]),
             _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
 
+    def shared_dist_supported(self, B, group_size, num_negs):
+        """True when the distance-tile shared step (amdkge_train_shared_dist_fwdbwd: TransE, RotatE) covers this model and shape."""
+        return int(self.lib.amdkge_train_shared_dist_workspace_bytes(C.byref(self.model), int(B), int(group_size), int(num_negs))) > 0
+
+    def train_shared_dist_fwdbwd(self, triples, group_size, num_negs, ids, side, loss, s_filter=None, o_filter=None, identity=False, stats=None,
+                                 pos_scores=None, neg_scores=None):
+        """amdkge_train_shared_dist_fwdbwd (include/amdkge_shared_dist.h): train_shared_masked_fwdbwd's step for TransE and RotatE, whose
+        G x M scores of a group are a tile of distances instead of a matrix product.  The arguments are that method's: s_filter /
+        o_filter (both or neither) mask the known statements, identity promises ids[g][j] == j, stats int64 [2] += (masked,
+        unmaskable).  Accumulates into g_ent / g_rel and loss_acc[0]; neg_scores (optional) has row j * B + i."""
+        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
+        if (s_filter is None) != (o_filter is None):
+            raise ValueError("train_shared_dist_fwdbwd: s_filter and o_filter are given together or not at all")
+        need = int(self.lib.amdkge_train_shared_dist_workspace_bytes(C.byref(self.model), B, G, M)) if B > 0 else 0
+        if B > 0 and need <= 0:
+            raise ValueError("train_shared_dist_fwdbwd: distance-tile shared negatives are not offered for this model / shape "
+                             f"({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
+        work = self._buf("shared_work", (need,), torch.uint8)
+        sf, of = s_filter or (None, None, None), o_filter or (None, None, None)
+        check(self.lib.amdkge_train_shared_dist_fwdbwd(
+            C.byref(self.model), C.byref(loss), _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M, _ptr(ids), _ptr(side),
+            _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work),
+            _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]),
+            _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
+
     def negatives_side_thresholds(self, po_keys, sp_keys, n_ents=None, n_rels=None):
         """amdkge_negatives_side_thresholds: the Bernoulli thresholds floor(2^32 G_po / (G_sp + G_po)) per relation from a
         FilterIndex's two int64 device key arrays -> int32 device tensor [n_rels] holding the uint32 bit patterns."""

@@ -121,7 +121,9 @@ class ScoringBasedEmbeddingModel:
         form {"shared": num_negs | "all", "group_size", "side", "entities", "mask_known"} (mask_known: False | True | dict of datasets -- the
         scores of corruptions that are known statements are -inf before the loss; "all": every list is every entity, 1-vs-all training;
         model.negative_sampling_stats_ = {"masked", "unmaskable"} after fit(); groups of positives share one list of replacements, scored by a
-        matrix product: DistMult / ComplEx / HolE on one GPU, no deterministic, lazy or FocusE mode).  Multi-GPU, one process per GPU under torch.distributed:
+        matrix product: DistMult / ComplEx / HolE on one GPU, no deterministic, lazy or FocusE mode) | SharedDistanceNegatives | its dict form
+        {"shared_distance": num_negs | "all", "group_size", "side", "entities", "mask_known"} (the same step for TransE / RotatE, scored on
+        distance tiles; the same refusals).  Multi-GPU, one process per GPU under torch.distributed:
         entity_sharding="replicated" (default: tables replicated, gradient all-reduce) | "rows" (entity table
         row-sharded over the ranks, ampligraph_amd/sharded.py; sharded_negatives="local" | "global" chooses where its corruptions
         are drawn from) | "columns" (tables that fit every GPU: rank r TRAINS on k / W units of every row and the whole batch, one

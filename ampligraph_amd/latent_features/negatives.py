@@ -15,6 +15,10 @@ the ones of the default path.
 (kge_train_shared.hip).  It binds to a `BoundSharedNegatives`, whose step is engine.train_shared_fwdbwd instead of the override; with
 `mask_known` to a `BoundMaskedSharedNegatives`, whose step is engine.train_shared_masked_fwdbwd (include/amdkge_shared_mask.h: the
 scores of corruptions that are known statements are -inf before the loss).  num_negs="all" makes every list every entity.
+
+`SharedDistanceNegatives` is SharedNegatives for TransE and RotatE, whose score against a shared list is a tile of distances instead
+of a matrix product (kge_train_shared_dist.hip, include/amdkge_shared_dist.h).  It binds to the same two classes with
+`distance = True` set: their step is engine.train_shared_dist_fwdbwd.
 """
 import numpy as np
 
@@ -48,11 +52,14 @@ class NegativeSampling:
     @classmethod
     def get(cls, spec):
         """compile()'s `negatives` argument -> None or a sampler: None, a NegativeSampling or SharedNegatives (or anything with .bind()), a dict of
-        NegativeSampling's keywords, or {"shared": num_negs, ...} for a SharedNegatives."""
+        NegativeSampling's keywords, {"shared": num_negs, ...} for a SharedNegatives or {"shared_distance": num_negs, ...} for a
+        SharedDistanceNegatives."""
         if spec is None or hasattr(spec, "bind"):
             return spec
         if isinstance(spec, dict) and "shared" in spec:   # {"shared": M, ...}: SharedNegatives(num_negs=M, ...)
             return SharedNegatives.from_dict(spec)
+        if isinstance(spec, dict) and "shared_distance" in spec:   # {"shared_distance": M, ...}: SharedDistanceNegatives(num_negs=M, ...)
+            return SharedDistanceNegatives.from_dict(spec)
         if isinstance(spec, dict) and "types" in spec:    # {"types": "observed" | RelationTypes, ...}: TypedNegatives
             return TypedNegatives.from_dict(spec)
         if isinstance(spec, dict):
@@ -238,6 +245,7 @@ class SharedNegatives:
     "entities": ..., "mask_known": ...})."""
 
     shared = True   # what trainer.StepLoop.step looks for
+    KEY = "shared"  # the key of the dict form that carries num_negs
     ALL_GROUP_SIZE = 4096   # measured (DESIGN section 5): the products want >= 4 096 rows per chunk; the score buffer is 4 * group_size * num_negs bytes
 
     def __init__(self, num_negs, group_size=None, side="uniform", entities=None, mask_known=False):
@@ -269,14 +277,14 @@ class SharedNegatives:
     def from_dict(cls, spec):
         if "filter" in spec and spec["filter"] is not False:
             raise ValueError("negatives: shared negatives take no `filter`: a rejection per positive breaks the sharing")
-        unknown = set(spec) - {"shared", "group_size", "side", "entities", "filter", "mask_known"}
+        unknown = set(spec) - {cls.KEY, "group_size", "side", "entities", "filter", "mask_known"}
         if unknown:
             raise ValueError("negatives: unknown keys {} for shared negatives".format(sorted(unknown)))
-        return cls(spec["shared"], spec.get("group_size"), spec.get("side", "uniform"), spec.get("entities"), spec.get("mask_known", False))
+        return cls(spec[cls.KEY], spec.get("group_size"), spec.get("side", "uniform"), spec.get("entities"), spec.get("mask_known", False))
 
     def get_config(self):
         """The dict form compile(negatives=...) takes (labels and datasets as given; `mask_known` only when it is set)."""
-        cfg = {"shared": self.num_negs, "group_size": self.group_size, "side": self.side, "entities": self.entities}
+        cfg = {self.KEY: self.num_negs, "group_size": self.group_size, "side": self.side, "entities": self.entities}
         if self.mask_known is not False:
             cfg["mask_known"] = self.mask_known
         return cfg
@@ -285,7 +293,12 @@ class SharedNegatives:
         """compile()'s refusals: everything that is known before a GPU is touched."""
         if model.scoring_type not in ("DistMult", "ComplEx", "HolE"):
             raise NotImplementedError("negatives: shared negatives need a score that is a contraction with the replaced row "
-                                      "(DistMult, ComplEx, HolE); {} scores a distance".format(model.scoring_type))
+                                      "(DistMult, ComplEx, HolE); {} scores a distance: its shared step is "
+                                      "SharedDistanceNegatives".format(model.scoring_type))
+        self._check_modes(model, optimizer_mode)
+
+    @staticmethod
+    def _check_modes(model, optimizer_mode):
         if model._deterministic:
             raise NotImplementedError("negatives: shared negatives accumulate in no fixed order; deterministic=True is not offered")
         if optimizer_mode == "lazy":
@@ -332,9 +345,35 @@ class SharedNegatives:
                                           identity=all_list is not None and pool is None)
 
 
+class SharedDistanceNegatives(SharedNegatives):
+    """SharedNegatives for the DISTANCE models, TransE and RotatE: the same groups, lists, sides, losses, `mask_known` and
+    num_negs="all", the same constructor arguments.  A distance against a shared list is no matrix product, so the step runs on
+    distance tiles instead (include/amdkge_shared_dist.h, kge_train_shared_dist.hip): a group's query vectors and its gathered rows
+    are read once and the group_size x num_negs x k work is arithmetic on operands in LDS and registers.  RotatE with the subject
+    replaced is scored as |e - o o conj(r)|, which differs from the reference's |e o r - o| by fp32 rounding only (|r| = 1).
+    DistMult, ComplEx and HolE are refused: theirs is SharedNegatives.
+
+    compile(negatives=SharedDistanceNegatives(...)) or compile(negatives={"shared_distance": num_negs | "all", "group_size": ...,
+    "side": ..., "entities": ..., "mask_known": ...})."""
+
+    KEY = "shared_distance"
+
+    def check_model(self, model, optimizer_mode="dense"):
+        if model.scoring_type not in ("TransE", "RotatE"):
+            raise NotImplementedError("negatives: SharedDistanceNegatives is the shared step of the models that score a distance (TransE, RotatE); "
+                                      "{} scores a contraction: use SharedNegatives".format(model.scoring_type))
+        self._check_modes(model, optimizer_mode)
+
+    def bind(self, model, engine, train):
+        bound = super().bind(model, engine, train)
+        bound.distance = True   # trainer.StepLoop.step: engine.train_shared_dist_fwdbwd
+        return bound
+
+
 class BoundSharedNegatives:
     """A SharedNegatives bound to one fit().  trainer.StepLoop.step calls draw(global_batch, seed, step) -> (ids int32
-    [n_groups, num_negs], side int32 [B]) and hands both to engine.train_shared_fwdbwd.  all_list: None, or the int32 device list
+    [n_groups, num_negs], side int32 [B]) and hands both to engine.train_shared_fwdbwd -- to engine.train_shared_dist_fwdbwd when
+    `distance` is set (SharedDistanceNegatives.bind).  all_list: None, or the int32 device list
     [num_negs] of num_negs="all": every group's row of ids is that list -- the id tensor is built once (and again only for a batch
     with more groups than any before), a step draws the sides alone."""
 

@@ -127,7 +127,8 @@ class StepLoop:
         # rng_step) -> int32 device rows [(hi - lo) * eta, 3], the corruptions of rows [lo, hi) of the global batch drawn by GLOBAL
         # row (latent_features/negatives.py: BoundNegatives), which the step hands to the train kernels as their override; or an object
         # with `.shared` set (BoundSharedNegatives: .draw(), .group_size, .num_negs), whose step is engine.train_shared_fwdbwd -- or, when
-        # it has a .mask() (BoundMaskedSharedNegatives), engine.train_shared_masked_fwdbwd
+        # it has a .mask() (BoundMaskedSharedNegatives), engine.train_shared_masked_fwdbwd; with `.distance` set too
+        # (SharedDistanceNegatives: TransE, RotatE) both are engine.train_shared_dist_fwdbwd
         self.negatives = None
         engine.prepare_training(optimizer.name)
         if hasattr(optimizer, "bind"):
@@ -185,7 +186,13 @@ class StepLoop:
                 sh = self.negatives
                 ids, side = sh.draw(global_batch, self.seed, rng_step)
                 mask = getattr(sh, "mask", None)   # BoundMaskedSharedNegatives: known statements score -inf (kge_train_shared.hip, shared_mask_kernel)
-                if mask is None:
+                if getattr(sh, "distance", False):   # SharedDistanceNegatives: distance tiles (kge_train_shared_dist.hip), one entry point for both
+                    kw = {}
+                    if mask is not None:
+                        s_filter, o_filter = mask(global_batch)
+                        kw = dict(s_filter=s_filter, o_filter=o_filter, identity=bool(getattr(sh, "identity", False)), stats=getattr(sh, "stats_dev", None))
+                    eng.train_shared_dist_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi, **kw)
+                elif mask is None:
                     eng.train_shared_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi)
                 else:
                     s_filter, o_filter = mask(global_batch)

@@ -1,0 +1,100 @@
+"""The arithmetic of include/amdkge_shared_dist.h restated in numpy: the query vectors, the residuals and (TransE) their signs in
+fp32 in the DECLARED order, every sum in fp64.  The TransE sign then has no rounding ambiguity at any size: a kernel that follows the
+header computes the same fp32 residual.  Test infrastructure: the product does not import it.
+
+DistStep(model, ent, rel, X, G, ids, side, R) holds the scores of a step; .gradients(dP, dN) the dense gradients for given
+dL/dscore of the positives [B] and of the corruptions [M * B] (row j * B + i); .step(loss, reduction, mask) the whole (masked)
+step through the oracle's Loss.__call__."""
+import numpy as np
+
+from oracle import kge_oracle as O
+
+F32 = np.float32
+
+
+class DistStep:
+    def __init__(self, model, ent, rel, X, G, ids, side, R):
+        assert model in ("TransE", "RotatE")
+        X = np.asarray(X, dtype=np.int64).reshape(-1, 3)
+        ent, rel = np.asarray(ent, dtype=F32), np.asarray(rel, dtype=F32)
+        B, M = X.shape[0], np.asarray(ids).shape[1]
+        G = min(G, max(B, 1))
+        self.model, self.X, self.B, self.M, self.shape_e, self.shape_r = model, X, B, M, ent.shape, rel.shape
+        self.subj = subj = np.asarray(side)[:B] != 0
+        self.lists = np.asarray(ids, dtype=np.int64)[np.arange(B) // G]          # [B, M]: the list of every positive
+        self.own_id = np.where(subj, X[:, 0], X[:, 2])
+        self.kept_id = np.where(subj, X[:, 2], X[:, 0])
+        s, p, o = ent[X[:, 0]], rel[X[:, 1]], ent[X[:, 2]]
+        sj = subj[:, None]
+        if model == "TransE":
+            self.k = k = ent.shape[1]
+            q = np.where(sj, o - p, s + p).astype(F32)                           # fp32(o - p) | fp32(s + p)
+            self.q = q[:, None, :]                                               # [B, 1(component), k]
+        else:
+            self.k = k = ent.shape[1] // 2
+            self.div = O.rotate_phase_divisor(k, R)
+            phi = (rel[X[:, 1], :k] / self.div).astype(F32)
+            c, sn = np.cos(phi.astype(np.float64)).astype(F32), np.sin(phi.astype(np.float64)).astype(F32)
+            self.c, self.sn = c.astype(np.float64), sn.astype(np.float64)
+            s0, s1, o0, o1 = s[:, :k], s[:, k:], o[:, :k], o[:, k:]
+            q0 = np.where(sj, o0 * c + o1 * sn, s0 * c - s1 * sn).astype(F32)    # o o conj(r) | s o r, every product and sum rounded to fp32
+            q1 = np.where(sj, o1 * c - o0 * sn, s0 * sn + s1 * c).astype(F32)
+            self.q = np.stack([q0, q1], 1)                                       # [B, 2, k]
+        nc = self.q.shape[1]
+        self.E = ent.reshape(ent.shape[0], nc, k)                                # component c of unit u: column c * k + u
+        self.z_neg = (self.q[:, None] - self.E[self.lists]).astype(F32)          # [B, M, nc, k]: fp32(q - e)
+        self.z_pos = (self.q - self.E[self.own_id]).astype(F32)                  # [B, nc, k]
+        self.mod_neg = np.sqrt((self.z_neg.astype(np.float64) ** 2).sum(2))      # [B, M, k]: |d| / |z| per unit
+        self.mod_pos = np.sqrt((self.z_pos.astype(np.float64) ** 2).sum(1))
+        self.pos_scores = -self.mod_pos.sum(-1)                                  # [B] fp64
+        self.neg_matrix = -self.mod_neg.sum(-1)                                  # [B, M] fp64
+        self.neg_scores = self.neg_matrix.T.reshape(-1)                          # row j * B + i
+
+    def min_modulus(self):
+        """the smallest |d| (TransE) / |z| (RotatE) over every scored pair-unit: the conditioning of a comparison with an fp64 oracle"""
+        return float(min(self.mod_neg.min(), self.mod_pos.min()))
+
+    def gradients(self, dP, dN):
+        """dL/dscore of the positives [B] and of the corruptions [M * B] -> (G_ent fp64, G_rel fp64)"""
+        B, M, k = self.B, self.M, self.k
+        cP = np.asarray(dP, dtype=np.float64).reshape(B)
+        cN = np.asarray(dN, dtype=np.float64).reshape(M, B).T                    # [B, M]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if self.model == "TransE":
+                n_neg, n_pos = np.sign(self.z_neg).astype(np.float64), np.sign(self.z_pos).astype(np.float64)
+            else:
+                n_neg = self.z_neg.astype(np.float64) / self.mod_neg[:, :, None, :]
+                n_pos = self.z_pos.astype(np.float64) / self.mod_pos[:, None, :]
+        # score = -sum |q - e|: d score / dq = -n, d score / de = +n.  A zero coefficient adds nothing (whatever n is).
+        w_neg = np.where(cN[:, :, None, None] != 0, cN[:, :, None, None] * n_neg, 0.0)
+        w_pos = cP[:, None, None] * n_pos
+        t = -(w_neg.sum(1) + w_pos)                                              # dL/dq [B, nc, k]
+        Ge, Gr = np.zeros(self.shape_e), np.zeros(self.shape_r)
+        np.add.at(Ge, self.lists.reshape(-1), w_neg.reshape(B * M, -1))
+        np.add.at(Ge, self.own_id, w_pos.reshape(B, -1))
+        sj = self.subj[:, None]
+        if self.model == "TransE":                                               # q = o - p | s + p
+            np.add.at(Ge, self.kept_id, t[:, 0])
+            np.add.at(Gr, self.X[:, 1], np.where(sj, -t[:, 0], t[:, 0]))
+        else:
+            c, sn, t0, t1 = self.c, self.sn, t[:, 0], t[:, 1]
+            q0, q1 = self.q[:, 0].astype(np.float64), self.q[:, 1].astype(np.float64)
+            k0 = np.where(sj, t0 * c - t1 * sn, t0 * c + t1 * sn)                # the transpose of o -> o o conj(r) | s -> s o r
+            k1 = np.where(sj, t0 * sn + t1 * c, t1 * c - t0 * sn)
+            dphi = np.where(sj, t0 * q1 - t1 * q0, t1 * q0 - t0 * q1)            # dq/dphi = (q1, -q0) | (-q1, q0)
+            np.add.at(Ge, self.kept_id, np.concatenate([k0, k1], 1))
+            gp = np.zeros((B, self.shape_r[1]))
+            gp[:, :k] = dphi / float(self.div)
+            np.add.at(Gr, self.X[:, 1], gp)
+        return Ge, Gr
+
+    def step(self, loss, reduction, mask=None, loss_params=None):
+        """The whole step: the scores (fp32, -inf where `mask` [B, M] is set) through the oracle's Loss.__call__
+        -> (loss sum, G_ent, G_rel, positive scores fp32 [B], corruption scores fp32 [M * B])"""
+        sp, sn = self.pos_scores.astype(F32), self.neg_scores.astype(F32)
+        if mask is not None:
+            sn[np.asarray(mask).T.reshape(-1)] = -np.inf
+        with np.errstate(invalid="ignore", over="ignore"):
+            _, per, dP, dN = O.loss_and_grads(loss, sp, sn, self.M, loss_params, reduction)
+        Ge, Gr = self.gradients(dP, dN)
+        return float(per.astype(np.float64).sum()), Ge, Gr, sp, sn
