@@ -51,7 +51,8 @@ extern "C" int amdkge_topk_rows_excluding(const float* d_vals, int64_t n, int64_
     if (n < 0 || m < 0 || ld < m || k < 1 || k > TOPK_MAX) return set_error(AMDKGE_EINVAL, "topk_rows_excluding: bad sizes (1 <= k <= 1024, ld >= m)");
     if ((d_ex_lo == nullptr) != (d_ex_hi == nullptr) || (d_ex_lo == nullptr) != (d_ex_ids == nullptr))
         return set_error(AMDKGE_EINVAL, "topk_rows_excluding: the excluded ids are (lo, hi, ids) or three NULLs");
-    if (n > 0x7FFFFFFFll || m > 0xFFFFFFFEll) return set_error(AMDKGE_EUNSUPPORTED, "topk_rows_excluding: too many rows / columns for one call");
+    // (d_out_idx holds int32 column indices, -1 = missing: a column beyond 2^31 - 1 has no representation)
+    if (n > 0x7FFFFFFFll || m > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "topk_rows_excluding: rows and columns are int32 (n, m <= 2^31 - 1)");
     if (n == 0) return AMDKGE_OK;
     if (!d_out_idx || !d_out_val || (m > 0 && !d_vals)) return set_error(AMDKGE_EINVAL, "topk_rows_excluding: NULL pointer");
     hipLaunchKernelGGL(topk_rows_excluding_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, d_vals, m, ld, d_col_ids, id_base, d_ex_lo,

@@ -79,7 +79,8 @@ using namespace kge;
 extern "C" int amdkge_topk_rows(const float* d_vals, int64_t n, int64_t m, int64_t ld, const float* d_col_scale, const float* d_col_bias,
                                 const int32_t* d_payload, int32_t k, int32_t largest, int32_t* d_out_idx, float* d_out_val, void* stream) {
     if (n < 0 || m < 0 || ld < m || k < 1 || k > TOPK_MAX) return set_error(AMDKGE_EINVAL, "topk_rows: bad sizes (1 <= k <= 1024, ld >= m)");
-    if (n > 0x7FFFFFFFll || m > 0xFFFFFFFEll) return set_error(AMDKGE_EUNSUPPORTED, "topk_rows: too many rows / columns for one call");
+    // (d_out_idx holds int32 column indices, -1 = missing: a column beyond 2^31 - 1 has no representation)
+    if (n > 0x7FFFFFFFll || m > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "topk_rows: rows and columns are int32 (n, m <= 2^31 - 1)");
     if (n == 0) return AMDKGE_OK;
     if (!d_out_idx || !d_out_val || (m > 0 && !d_vals)) return set_error(AMDKGE_EINVAL, "topk_rows: NULL pointer");
     hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, d_vals, m, ld, d_col_scale, d_col_bias, d_payload,

@@ -422,7 +422,8 @@ int amdkge_rank_compose(const int32_t* d_counts, const int32_t* d_sub, int64_t n
  *   entries of v[j] = d_vals[i*ld + j] * d_col_scale[j] + d_col_bias[j] (either array may be NULL): d_out_idx [n, k] column
  *   indices (-1 when m < k) -- or, with d_payload int32 [n, ld], the payload entries of those columns (merging per-shard
  *   candidate lists: payload = their global ids) --, d_out_val [n, k] the values v, best first; equal values in order of
- *   increasing column. */
+ *   increasing column.  The indices are int32: n, m <= 2^31 - 1, AMDKGE_EUNSUPPORTED beyond (amdkge_topk_rows_excluding alike); ld and
+ *   every i * ld are 64-bit. */
 int amdkge_corruption_scores(const amdkge_model* m, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t n,
                              int32_t side, const int32_t* d_ent_ids, int64_t ent_lo, int64_t ent_hi, float* d_scores, int64_t ld,
                              void* d_work, void* stream);
@@ -440,7 +441,8 @@ int amdkge_topk_rows(const float* d_vals, int64_t n, int64_t m, int64_t ld, cons
  * ids ascending inside a range (amdkge_filter_build's order); three NULLs: nothing excluded -- or equals d_own[i] (d_own may be
  * NULL).  An excluded column never reaches the output, not even as a filler: it is left out of the selection, the score block is
  * read only (-inf and NaN are scores like any other).  With three NULLs and d_own NULL the output is amdkge_topk_rows', bit for bit.
- * Bad sizes, and a range array without its two siblings, fail with AMDKGE_EINVAL before any launch; n == 0 is a no-op. */
+ * Bad sizes, and a range array without its two siblings, fail with AMDKGE_EINVAL before any launch, n or m beyond 2^31 - 1 (the
+ * indices are int32) with AMDKGE_EUNSUPPORTED; n == 0 is a no-op. */
 int amdkge_topk_rows_excluding(const float* d_vals, int64_t n, int64_t m, int64_t ld, const int32_t* d_col_ids, int64_t id_base,
                                const int64_t* d_ex_lo, const int64_t* d_ex_hi, const int32_t* d_ex_ids, const int32_t* d_own,
                                int32_t k, int32_t* d_out_idx, float* d_out_val, void* stream);

@@ -233,4 +233,11 @@ def test_session_group_argument_validation_without_gpu():
     m.k_full = 16
     assert lib.amdkge_cols_partial_scores(ctypes.byref(m), None, None, None, 0, 5, 0, 100, 0, 0, 0, 0, None, None, None) == 0    # an empty batch is a no-op
     assert lib.amdkge_cols_partial_scores(ctypes.byref(m), None, None, None, 1, 5, 0, 100, 0, 0, 0, 1, None, None, None) == -1   # NULL pointers
+    # a slice holds up to 256 stored units per half: DistMult's 400-unit rows (the C3 width as a slice of an 800-unit model) are refused
+    # before any launch -- host buffers stand in for device memory, no checked path reads them
+    m.scoring_type, m.k, m.k_pad, m.k_full, m.n_ents = 1, 400, 400, 800, 5_500_858
+    buf = (ctypes.c_float * 16)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    assert lib.amdkge_cols_partial_scores(ctypes.byref(m), p, p, p, 1, 5, 0, 100, 0, 0, 0, 1, None, p, None) == -5
+    assert b"256 units per half" in lib.amdkge_last_error()
     assert "AMDKGE_ERCCL (-3)" in open(os.path.join(ROOT, "include", "amdkge.h")).read()

@@ -35,6 +35,24 @@ def test_topk_rows_excluding_argument_validation_without_gpu():
     assert _call(lib, vals=0) == -1                                       # NULL score block with m > 0
 
 
+def test_topk_rows_refuse_columns_beyond_int32():
+    """amdkge_topk_rows and amdkge_topk_rows_excluding return int32 column indices (-1 = missing): m, like n, is at most 2^31 - 1 and a
+    wider block is refused with AMDKGE_EUNSUPPORTED before any launch (a block that wide is selected in column chunks, the chunks' winners
+    merged through d_payload).  The limit itself passes the size checks: the call then fails on the NULL pointer behind them."""
+    from ampligraph_amd import _ffi
+
+    lib = _ffi.lib()
+    top = 2 ** 31 - 1
+    buf = [(ctypes.c_int32 * 8)(), (ctypes.c_float * 8)()]
+    p = lambda b: ctypes.cast(b, ctypes.c_void_p)   # noqa: E731
+    for m in (top + 1, 2 ** 32 - 2, 2 ** 32):
+        assert _call(lib, m=m, ld=m) == -5 and b"int32" in lib.amdkge_last_error(), m
+        assert lib.amdkge_topk_rows(p(buf[1]), 1, m, m, None, None, None, 4, 1, p(buf[0]), p(buf[1]), None) == -5 and b"int32" in lib.amdkge_last_error(), m
+    assert _call(lib, n=top + 1) == -5 and lib.amdkge_topk_rows(p(buf[1]), top + 1, 8, 8, None, None, None, 4, 1, p(buf[0]), p(buf[1]), None) == -5
+    assert _call(lib, m=top, ld=top, vals=0) == -1 and b"NULL" in lib.amdkge_last_error()
+    assert lib.amdkge_topk_rows(None, 1, top, top, None, None, None, 4, 1, p(buf[0]), p(buf[1]), None) == -1 and b"NULL" in lib.amdkge_last_error()
+
+
 class _StubModel:
     """What query_topn_batch reads before it reaches the device: the fitted flag and the label maps."""
 
