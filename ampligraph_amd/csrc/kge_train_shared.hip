@@ -11,7 +11,9 @@
 //                           FWD : S_g  = Q_g E^T     (G x K by K x M)   E gathered by id          -> the score buffer [rows, M]
 //                           DQ  : dQ_g = C_g E       (G x M by M x K)   E gathered by id          -> dQ [B, K]
 //                           DE  : dE   = C_g^T Q_g   (M x G by G x K)   C read transposed         -> atomic row-adds into d_grad_ent
-//                         Elements past a matrix edge are staged as zeros, so every tile shape is one code path.
+//                         Elements past a matrix edge are staged as zeros, so every tile shape is one code path.  Non-finite tables:
+//                         a +-inf FWD result of ComplEx / HolE is computed again in the reference's order (shared_reference_score);
+//                         DE and the chain kernel never write a padding unit (NaN coefficient * zero padding = NaN).
 //   shared_loss_kernel  : a wave per positive walks loss_call (kge_loss.h) over its row of the score buffer: scores -> dL/dscore in
 //                         place.  The buffer holds the plain sums; HolE's 2/k is applied where a score is loaded (the reference's
 //                         rounding: reduce_sum, then scale) and again where a coefficient is stored (the chain rule through it).
@@ -20,7 +22,7 @@
 //                         atomic row-adds per positive.
 //   shared_mask_kernel  : (include/amdkge_shared_mask.h, optional, between FWD and the loss) a wave per positive sets the scores of the
 //                         corruptions that are KNOWN statements to -inf, which every loss of loss_call already defines: no loss term, an
-//                         exact-zero coefficient, nothing for DQ / DE to add.
+//                         exact-zero coefficient, nothing for DQ / DE to add where the rows are finite (0 * NaN = NaN where not).
 // Groups are processed in chunks of at most CHUNK_SCORES scores, so the score buffer is bounded whatever B * M is.
 #include "kge_train_shared.h"
 #include "kge_loss.h"
@@ -110,6 +112,9 @@ constexpr int GLD = GT + 1;   // LDS row stride: a chunk staged along the contra
 
 struct SharedGemmArgs {
     const float* ent;
+    const float* rel;
+    const int32_t* triples;
+    const int32_t* side;
     const int32_t* ids;   // [n_groups, M]
     float* Q;             // [B, K]
     float* S;             // [rows of the chunk, M]: scores, then dL/dscore
@@ -117,11 +122,32 @@ struct SharedGemmArgs {
     float* g_ent;
     int64_t B, G;
     int M, K;
+    int ks, k;            // units per half as stored, live units (DE: the padding units of a gradient row are never written)
+    int cplx;             // ComplEx / HolE: an infinite score is recomputed in the reference's operation order (shared_reference_score)
     int64_t g0;           // first group of the chunk (row0 = g0 * G)
     int tiles_m, tiles_n;
 };
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// The score of ONE corruption of a ComplEx / HolE positive in the reference's own operation order (ComplEx.py:58-62, score_unit of
+// kge_device.h: what amdkge_train_fwdbwd computes on the override row), one lane, serially.  Only for a score that the matrix product
+// made +-inf: <q, e> with an inf in e is (a - b) * inf = +-inf where the reference forms a * inf - b * inf, which is NaN when a and b
+// have one sign -- a NaN loss and NaN coefficients for the whole positive, where +-inf is clipped to a finite loss.  Which of the
+// three non-finite values it is depends only on the units' terms, not on the order of their sum.
+__device__ float shared_reference_score(const SharedGemmArgs& a, int64_t i, int id) {
+    const int32_t* t = a.triples + 3 * i;
+    const bool subj = a.side[i] != 0;
+    const float* S = a.ent + (int64_t)(subj ? id : t[0]) * a.K;
+    const float* P = a.rel + (int64_t)t[1] * a.K;
+    const float* O = a.ent + (int64_t)(subj ? t[2] : id) * a.K;
+    float acc = 0.f;
+    for (int u = 0; u < a.k; ++u) {
+        const float s0 = S[u], s1 = S[a.ks + u], p0 = P[u], p1 = P[a.ks + u], o0 = O[u], o1 = O[a.ks + u];
+        acc += s0 * (p0 * o0 + p1 * o1) + s1 * (p0 * o1 - p1 * o0);
+    }
+    return acc;
+}
 
 template <int MODE>
 __global__ __launch_bounds__(256) void shared_gemm_kernel(SharedGemmArgs a) {
@@ -198,18 +224,27 @@ __global__ __launch_bounds__(256) void shared_gemm_kernel(SharedGemmArgs a) {
     // ---- results: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31 of the wave's 32 x 32 ----
     const int col = n0 + (wv >> 1) * 32 + (lane & 31);
     if (col >= ndim) return;
+    // A padding unit of Q is an exact zero, but a NaN coefficient times it is NaN: the padding floats of d_grad_ent stay untouched.
+    if (MODE == GEMM_DE && col % a.ks >= a.k) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = m0 + (wv & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (row >= mdim) continue;
-        const float v = acc[r];
-        if (MODE == GEMM_FWD) a.S[(srow + row) * a.M + col] = v;
+        float v = acc[r];
+        if (MODE == GEMM_FWD) {
+            if (a.cplx && __builtin_isinf(v)) v = shared_reference_score(a, row_first + row, gid[col]);   // (an inf in a table: rare, divergent)
+            a.S[(srow + row) * a.M + col] = v;
+        }
         else if (MODE == GEMM_DQ) a.dQ[(row_first + row) * a.K + col] = v;
-        else if (v != 0.f) atomic_add_f32(a.g_ent + (int64_t)gid[row] * a.K + col, v);   // (true for NaN; zeros -- the padding units -- add nothing)
+        else if (v != 0.f) atomic_add_f32(a.g_ent + (int64_t)gid[row] * a.K + col, v);   // (true for NaN; exact zeros add nothing)
     }
 }
 
 // ---- Loss.__call__ on a positive's row of the score buffer --------------------------------------------------------------------------
+// store(): masked_zero()'s -0.0f marker (kge_loss.h) does not survive scale < 0 -- the distance tiles run with scale = -1 and it comes
+// out +0.0f.  The shared paths do not need it: the marker tells the tile pass of kge_train_tile.hip to KEEP an entry whose coefficient
+// is zero, and here no entry is ever dropped -- every coefficient of the buffer, a zero of either sign included, is an operand of DQ /
+// DE, where 0 * NaN = NaN does what the marker asks for (tests/test_gpu_nonfinite_shared.py).
 struct SharedWalk {
     float* s;
     int lane;
@@ -309,7 +344,7 @@ __device__ __forceinline__ void add_nz(float* p, float v) {
 
 template <bool CPLX>
 __global__ __launch_bounds__(256) void shared_chain_kernel(const float* __restrict__ ent, const float* __restrict__ rel, const int32_t* __restrict__ triples,
-                                                           const int32_t* __restrict__ side, int64_t B, int ks, const float* __restrict__ Q, const float* __restrict__ dQ,
+                                                           const int32_t* __restrict__ side, int64_t B, int ks, int k, const float* __restrict__ Q, const float* __restrict__ dQ,
                                                            const float* __restrict__ cpos, float* g_ent, float* g_rel) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -326,7 +361,7 @@ __global__ __launch_bounds__(256) void shared_chain_kernel(const float* __restri
     float* g_own = g_ent + (subj ? so : oo);    // the replaced row's original: c_pos q_i
     float* g_kept = g_ent + (subj ? oo : so);   // the kept entity row
     float* g_p = g_rel + po;
-    for (int u = lane; u < ks; u += 64) {
+    for (int u = lane; u < k; u += 64) {   // the live units: dQ of a padding unit is NaN where a coefficient is (NaN * 0)
         if constexpr (CPLX) {
             const float p0 = P[u], p1 = P[ks + u];
             const float w0 = subj ? S[u] : O[u], w1 = subj ? S[ks + u] : O[ks + u];   // own
@@ -403,7 +438,7 @@ template <bool CPLX>
 static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int M,
                       const int32_t* d_ids, const int32_t* d_side, float* g_ent, float* g_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores,
                       char* work, const SharedPlan& p, const SharedMaskArgs* mask, hipStream_t st) {
-    const int ks = stored_k(m), K = row_floats(m);
+    const int ks = stored_k(m), K = row_floats(m), k = m->k;
     const ModelConst mc = model_const(m);
     float* Q = reinterpret_cast<float*>(work + p.off_q);
     float* dQ = reinterpret_cast<float*>(work + p.off_dq);
@@ -415,7 +450,7 @@ static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const floa
     hipLaunchKernelGGL(shared_query_kernel<CPLX>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, Q, pos_raw);
     if (int rc = check_launch("shared_query")) return rc;
     SharedGemmArgs a{};
-    a.ent = d_ent; a.ids = d_ids; a.Q = Q; a.S = S; a.dQ = dQ; a.g_ent = g_ent; a.B = B; a.G = G; a.M = M; a.K = K;
+    a.ent = d_ent; a.rel = d_rel; a.triples = d_triples; a.side = d_side; a.cplx = CPLX ? 1 : 0; a.ids = d_ids; a.Q = Q; a.S = S; a.dQ = dQ; a.g_ent = g_ent; a.B = B; a.G = G; a.M = M; a.K = K; a.ks = ks; a.k = k;
     const int tg = (int)((G + GT - 1) / GT), tm = (M + GT - 1) / GT, tk = (K + GT - 1) / GT;
     for (int64_t g0 = 0; g0 < p.n_groups; g0 += p.gpc) {
         const int64_t ng = (p.n_groups - g0) < p.gpc ? (p.n_groups - g0) : p.gpc;
@@ -441,7 +476,7 @@ static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const floa
         hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DE>, dim3((unsigned)nb_de), dim3(256), 0, st, a);
         if (int rc = check_launch("shared_gemm_de")) return rc;
     }
-    hipLaunchKernelGGL(shared_chain_kernel<CPLX>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, Q, dQ, cpos, g_ent, g_rel);
+    hipLaunchKernelGGL(shared_chain_kernel<CPLX>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, k, Q, dQ, cpos, g_ent, g_rel);
     return check_launch("shared_chain");
 }
 

@@ -16,6 +16,10 @@
  * product Q_g E^T of the group's query vectors with the M gathered rows, and so are both gradients (dQ_g = C_g E and
  * dE = C_g^T Q_g, C = dL/dscore).  A positive then costs 3 row reads and 3 gradient-row adds whatever M is; a group costs M.
  * Only models whose score is such a contraction take part: TransE and RotatE are refused.
+ * NaN and inf in the tables follow the definition's rules: a NaN score is a NaN loss, a coefficient that a clip or a hinge zeroes
+ * is still multiplied by the score's Jacobian (0 * NaN = NaN), and the padding floats of a padded gradient row are never written.
+ * A ComplEx / HolE score that the product makes +-inf is computed again in the reference's operation order, where a * inf - b * inf
+ * is NaN although (a - b) * inf is not.  An inf in a positive's own kept row may still become NaN where the definition says +-inf.
  */
 #ifndef AMDKGE_SHARED_H
 #define AMDKGE_SHARED_H

@@ -27,7 +27,9 @@
  * Both.     The positive's own score is the same distance to its own replaced-side row.  dL/dq_i goes to the two kept rows of
  *           the positive through the transpose of the query map (RotatE: the phase gradient, divided by the phase divisor, into
  *           the first k floats of the relation row); the replaced row's original gets the positive score's term.
- *           A pair with c_ij == +-0 (a masked entry) adds nothing.
+ *           A pair with c_ij == +-0 (a masked entry, a clipped score) adds that zero times sigma / z / |z|: nothing where the
+ *           residual is finite, NaN where it is not (0 * NaN = NaN, the reference's rule for every zeroed coefficient:
+ *           include/amdkge_shared_mask.h).
  */
 #ifndef AMDKGE_SHARED_DIST_H
 #define AMDKGE_SHARED_DIST_H

@@ -10,8 +10,10 @@
  * -- what amdkge_filter_ranges returns and amdkge_sample_negatives takes as the same six arrays --, the masked step is the shared
  * step in which the SCORE of corruption (i, j) is replaced by -inf before Loss.__call__ whenever ids[i / G][j] is in known_i
  * (PyTorch-BigGraph's treatment of batch negatives that are true statements: masked, not redrawn, so the sharing stays).
- *   - Every loss is already defined at a score of -inf (kge_loss.h): no loss term, an exact-zero coefficient, no NaN; the masked
- *     corruption receives no gradient and sends none.
+ *   - Every loss is already defined at a score of -inf (kge_loss.h): no loss term, an exact-zero coefficient, no NaN.  The masked
+ *     corruption contributes that exact zero TIMES THE SCORE'S JACOBIAN: nothing where the rows it was computed from are finite
+ *     (it receives no gradient and sends none), NaN into those rows where one of them holds a NaN or an inf -- exactly as a score
+ *     that a clip or a hinge zeroes does (0 * NaN = NaN, the reference's rule; tests/test_gpu_nonfinite_shared.py).
  *   - The reduction divisors do not change: "mean" still divides by M (by 2 M for nll).  multiclass_nll clips its scores to
  *     [-75, 75] before the exponential, so a masked entry still adds e^-75 / red to the partition sum Z (2.7e-33: nothing in fp32
  *     next to a live term).

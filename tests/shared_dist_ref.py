@@ -65,9 +65,12 @@ class DistStep:
             else:
                 n_neg = self.z_neg.astype(np.float64) / self.mod_neg[:, :, None, :]
                 n_pos = self.z_pos.astype(np.float64) / self.mod_pos[:, None, :]
-        # score = -sum |q - e|: d score / dq = -n, d score / de = +n.  A zero coefficient adds nothing (whatever n is).
-        w_neg = np.where(cN[:, :, None, None] != 0, cN[:, :, None, None] * n_neg, 0.0)
-        w_pos = cP[:, None, None] * n_pos
+            # score = -sum |q - e|: d score / dq = -n, d score / de = +n.  A zero coefficient is still multiplied by n: 0 * NaN = NaN
+            # where the residual is non-finite (the reference's exact zero times the score's Jacobian).  Only on a modulus of exactly
+            # zero (RotatE: n = 0 / 0 from finite rows) does it add nothing, as in the tiles.
+            dead = (cN[:, :, None, None] == 0) & (self.mod_neg[:, :, None, :] == 0)
+            w_neg = np.where(dead, 0.0, cN[:, :, None, None] * n_neg)
+            w_pos = cP[:, None, None] * n_pos
         t = -(w_neg.sum(1) + w_pos)                                              # dL/dq [B, nc, k]
         Ge, Gr = np.zeros(self.shape_e), np.zeros(self.shape_r)
         np.add.at(Ge, self.lists.reshape(-1), w_neg.reshape(B * M, -1))

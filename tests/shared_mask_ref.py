@@ -48,9 +48,12 @@ def mask_matrix(X, G, ids, side, known_s, known_o):
     return mask, int(mask.sum()), unmaskable
 
 
-def masked_step(model, ent, rel, X, G, ids, side, mask, loss, reduction, R, loss_params=None):
+def masked_step(model, ent, rel, X, G, ids, side, mask, loss, reduction, R, loss_params=None, finite=True):
     """The definition: the shared step on SR.override_rows with the scores at `mask` set to -inf before the loss.
-    -> (loss sum float, G_ent fp64, G_rel fp64, positive scores [B], corruption scores [M * B] with -inf at the mask)"""
+    -> (loss sum float, G_ent fp64, G_rel fp64, positive scores [B], corruption scores [M * B] with -inf at the mask)
+    finite=True asserts that the tables gave finite numbers throughout.  finite=False is for tables that hold a NaN or an inf: a
+    masked coefficient is an exact zero TIMES the score's Jacobian, so a masked corruption of a non-finite row sends NaN to the
+    rows it was computed from, exactly as a clipped score does (tests/test_shared_nonfinite_host.py)."""
     X = np.asarray(X, dtype=np.int64).reshape(-1, 3)
     B, M = X.shape[0], ids.shape[1]
     negs = SR.override_rows(X, G, ids, side).astype(np.int64)
@@ -61,13 +64,15 @@ def masked_step(model, ent, rel, X, G, ids, side, mask, loss, reduction, R, loss
     sn[np.asarray(mask).T.reshape(-1)] = -np.inf           # row j * B + i
     with np.errstate(invalid="ignore", over="ignore"):
         total, per, dP, dN = O.loss_and_grads(loss, sp, sn, M, loss_params, reduction)
-    assert np.isfinite(per).all() and np.isfinite(dP).all() and np.isfinite(dN).all() and not dN[np.asarray(mask).T.reshape(-1)].any()
+    if finite:
+        assert np.isfinite(per).all() and np.isfinite(dP).all() and np.isfinite(dN).all() and not dN[np.asarray(mask).T.reshape(-1)].any()
     Ge = np.zeros(ent.shape, dtype=np.float64)
     Gr = np.zeros(rel.shape, dtype=np.float64)
-    for tri, (a, b, c), g in ((X, (s, p, o), dP), (negs, (ns, npr, no), dN)):   # (dense_gradients' accumulation)
-        gs, gp, go = O.score_grads(model, a, b, c, R)
-        g = g.astype(np.float64)[:, None]
-        np.add.at(Ge, tri[:, 0], g * gs)
-        np.add.at(Gr, tri[:, 1], g * gp)
-        np.add.at(Ge, tri[:, 2], g * go)
+    with np.errstate(invalid="ignore" if not finite else "warn"):
+        for tri, (a, b, c), g in ((X, (s, p, o), dP), (negs, (ns, npr, no), dN)):   # (dense_gradients' accumulation)
+            gs, gp, go = O.score_grads(model, a, b, c, R)
+            g = g.astype(np.float64)[:, None]
+            np.add.at(Ge, tri[:, 0], g * gs)
+            np.add.at(Gr, tri[:, 1], g * gp)
+            np.add.at(Ge, tri[:, 2], g * go)
     return float(per.astype(np.float64).sum()), Ge, Gr, sp, sn
