@@ -31,6 +31,9 @@ def reg_fields(reg, default_p):
         return int(default_p), 0.0, int(default_p), 0.0
     if isinstance(reg, (int, float)):
         return int(default_p), float(reg), int(default_p), 0.0
+    if getattr(reg, "batch", False):
+        raise NotImplementedError("a batch regularizer (BatchLPRegularizer) is no term of the optimizer sweep: it goes to "
+                                  "KgeEngine.batch_reg_fwdbwd (trainer.StepLoop.step does); the session layer does not offer it")
     t = list(reg.terms)[:2]
     while len(t) < 2:
         t.append((int(default_p), 0.0))
@@ -543,6 +546,21 @@ class KgeEngine:
             _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work),
             _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]),
             _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
+
+    def batch_reg_fwdbwd(self, triples, reg_e=None, reg_r=None):
+        """amdkge_batch_reg_fwdbwd (include/amdkge_batch_reg.h): the batch regularisers reg_e / reg_r (BatchLPRegularizer or None:
+        that term is off) on the rows of the int32 device positives [B, 3], once per occurrence.  Runs between a forward / backward
+        call that leaves dense gradients and opt_step: the gradient is ADDED to g_ent / g_rel, the penalty to loss_acc[1], the slot
+        the whole-table regulariser's value uses."""
+        terms = []
+        for reg, table in ((reg_e, "ent"), (reg_r, "rel")):
+            if reg is None:
+                terms += [2, 0.0, _ffi.BATCH_REG_NORMS["float"]]
+            else:
+                terms += [int(reg.p), float(reg.lam), _ffi.BATCH_REG_NORMS[reg.norm_for(self.scoring_type, table)]]
+        check(self.lib.amdkge_batch_reg_fwdbwd(
+            C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples), int(triples.shape[0]), *terms,
+            _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr() + 8), _stream()))
 
     def negatives_side_thresholds(self, po_keys, sp_keys, n_ents=None, n_rels=None):
         """amdkge_negatives_side_thresholds: the Bernoulli thresholds floor(2^32 G_po / (G_sp + G_po)) per relation from a

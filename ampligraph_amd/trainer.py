@@ -175,6 +175,17 @@ class StepLoop:
         lam = self.reg    # LPRegularizer objects (or None): the engine turns them into the descriptor's (p, lambda) terms
         lam_r = self.reg if isinstance(self.reg_rel, str) else self.reg_rel
         opt_ffi = self.optimizer.to_ffi(self.optimizer.iterations, 2)
+        # BatchLPRegularizer members (N3, per-occurrence Lp: include/amdkge_batch_reg.h) act on the rows of this step's positives:
+        # engine.batch_reg_fwdbwd between the backward call and the dense sweep, which then takes only the whole-table members
+        breg_e = lam if getattr(lam, "batch", False) else None
+        breg_r = lam_r if getattr(lam_r, "batch", False) else None
+        batch_reg = breg_e is not None or breg_r is not None
+        if batch_reg:
+            if focus is not None or self.multi or self.deterministic or getattr(self.optimizer, "lazy", False):
+                raise NotImplementedError("batch regularizer: its row-adds are unordered atomics (no deterministic mode); FocusE, "
+                                          "optimizer_mode='lazy' and more than one rank were not built")
+            lam = None if breg_e is not None else lam
+            lam_r = None if breg_r is not None else lam_r
         if getattr(self.negatives, "shared", False):
             # SharedNegatives: draw -> matrix-product forward / backward (kge_train_shared.hip) -> dense sweep.  Every other
             # configuration runs the code below.
@@ -198,6 +209,8 @@ class StepLoop:
                     s_filter, o_filter = mask(global_batch)
                     eng.train_shared_masked_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi, s_filter=s_filter, o_filter=o_filter,
                                                    identity=bool(getattr(sh, "identity", False)), stats=getattr(sh, "stats_dev", None))
+                if batch_reg:
+                    eng.batch_reg_fwdbwd(global_batch, breg_e, breg_r)
             if self.kernel_hook is not None:
                 self.kernel_hook(1)
             eng.opt_step(opt_ffi, lam, lam_r)
@@ -207,7 +220,8 @@ class StepLoop:
             return
         # owner-computes path (kge_train_tiled.hip) whenever the shape allows it: no global atomics, no dense
         # entity gradient; data-parallel runs take its gradient-only form and keep the dense sweep
-        tiled = (self.use_tiled or self.deterministic) and hi > lo and eng.tiled_supported(hi - lo, self.eta)
+        # (a batch regulariser needs the dense entity gradient, which the owner-computes step never materialises)
+        tiled = (self.use_tiled or self.deterministic) and not batch_reg and hi > lo and eng.tiled_supported(hi - lo, self.eta)
         if self.deterministic and hi > lo and not tiled:
             raise ValueError("deterministic mode needs the owner-computes train path (k <= 2048)")
         if self.kernel_hook is not None:
@@ -222,6 +236,8 @@ class StepLoop:
         elif hi > lo:
             eng.train_fwdbwd(global_batch[lo:hi], self.eta, self.loss_ffi, self.seed, rng_step,
                              row_offset=lo, b_global=bg, **neg)
+            if batch_reg:
+                eng.batch_reg_fwdbwd(global_batch[lo:hi], breg_e, breg_r)
         if self.kernel_hook is not None:
             self.kernel_hook(1)
         if self.multi and self.merge == "sharded":
