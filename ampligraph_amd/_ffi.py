@@ -202,6 +202,15 @@ SHARED_DIST_SIGNATURES = {
                                                   P, P, P, P, P, P, I32, P, P]),
 }
 
+# include/amdkge_shared_labels.h (KvsAll on the shared step: binary cross-entropy with multi-hot labels): again a table of its own
+SHARED_LABELS_SIGNATURES = {
+    "amdkge_shared_label_loss": (C.c_int, [P, I64, I64, I64, I32, P, P, P, P, P, P, P, P, I32, C.c_float, I32, C.c_float, P, P, P, P, P]),
+    "amdkge_train_shared_labels_fwdbwd": (C.c_int, [C.POINTER(Model), C.c_float, I32, P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P,
+                                                    P, P, P, P, P, P, I32, P, P, P, P]),
+    "amdkge_train_shared_dist_labels_fwdbwd": (C.c_int, [C.POINTER(Model), C.c_float, I32, P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P,
+                                                         P, P, P, P, P, P, I32, P, P, P, P]),
+}
+
 # include/amdkge_batch_reg.h (batch regularisers: N3 and per-occurrence Lp on the rows of a step's positives): again a table of its own
 BATCH_REG_NORMS = {"float": 0, "modulus": 1}
 BATCH_REG_SIGNATURES = {
@@ -232,7 +241,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(SHARED_SIGNATURES.items()) + list(SHARED_MASK_SIGNATURES.items()) + list(SHARED_DIST_SIGNATURES.items()) + list(BATCH_REG_SIGNATURES.items()) + list(TYPES_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(SHARED_SIGNATURES.items()) + list(SHARED_MASK_SIGNATURES.items()) + list(SHARED_DIST_SIGNATURES.items()) + list(SHARED_LABELS_SIGNATURES.items()) + list(BATCH_REG_SIGNATURES.items()) + list(TYPES_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

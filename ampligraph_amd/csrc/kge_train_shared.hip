@@ -23,6 +23,8 @@
 //   shared_mask_kernel  : (include/amdkge_shared_mask.h, optional, between FWD and the loss) a wave per positive sets the scores of the
 //                         corruptions that are KNOWN statements to -inf, which every loss of loss_call already defines: no loss term, an
 //                         exact-zero coefficient, nothing for DQ / DE to add where the rows are finite (0 * NaN = NaN where not).
+//   shared_label_loss_kernel : (include/amdkge_shared_labels.h, kge_train_shared_labels.hip; in place of the mask and the loss) KvsAll:
+//                         labels from the known ranges and binary cross-entropy in one pass over the buffer.
 // Groups are processed in chunks of at most CHUNK_SCORES scores, so the score buffer is bounded whatever B * M is.
 #include "kge_train_shared.h"
 #include "kge_loss.h"
@@ -437,7 +439,7 @@ int launch_shared_loss(float* S, const float* pos_raw, float* cpos, int64_t row0
 template <bool CPLX>
 static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int M,
                       const int32_t* d_ids, const int32_t* d_side, float* g_ent, float* g_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores,
-                      char* work, const SharedPlan& p, const SharedMaskArgs* mask, hipStream_t st) {
+                      char* work, const SharedPlan& p, const SharedMaskArgs* mask, hipStream_t st, const SharedLabelArgs* labels = nullptr) {
     const int ks = stored_k(m), K = row_floats(m), k = m->k;
     const ModelConst mc = model_const(m);
     float* Q = reinterpret_cast<float*>(work + p.off_q);
@@ -462,13 +464,20 @@ static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const floa
         a.tiles_m = tg; a.tiles_n = tm;
         hipLaunchKernelGGL(shared_gemm_kernel<GEMM_FWD>, dim3((unsigned)nb_fwd), dim3(256), 0, st, a);
         if (int rc = check_launch("shared_gemm_fwd")) return rc;
-        if (mask) {   // known statements -> -inf, on the chunk's own rows
-            SharedMaskArgs ma = *mask;
-            ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = G; ma.M = M; ma.ids = d_ids; ma.side = d_side;
-            ma.fill = mc.score_sign * mc.score_scale < 0.f ? INFINITY : -INFINITY;
-            if (int rc = launch_shared_mask(ma, st)) return rc;
+        if (labels) {   // KvsAll (include/amdkge_shared_labels.h): labels + BCE in one pass, in place of mask + loss
+            SharedLabelArgs la = *labels;
+            la.S = S; la.row0 = row0; la.rows = rows; la.G = G; la.B = B; la.M = M; la.ids = d_ids; la.side = d_side; la.scale = mc.score_sign * mc.score_scale;
+            la.pos_raw = pos_raw; la.cpos = cpos; la.pos_scores = d_pos_scores; la.neg_scores = d_neg_scores; la.loss_sum = d_loss_sum;
+            if (int rc = launch_shared_label_loss(la, st)) return rc;
+        } else {
+            if (mask) {   // known statements -> -inf, on the chunk's own rows
+                SharedMaskArgs ma = *mask;
+                ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = G; ma.M = M; ma.ids = d_ids; ma.side = d_side;
+                ma.fill = mc.score_sign * mc.score_scale < 0.f ? INFINITY : -INFINITY;
+                if (int rc = launch_shared_mask(ma, st)) return rc;
+            }
+            if (int rc = launch_shared_loss(S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum, d_pos_scores, d_neg_scores, st)) return rc;
         }
-        if (int rc = launch_shared_loss(S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum, d_pos_scores, d_neg_scores, st)) return rc;
         a.tiles_m = tg; a.tiles_n = tk;
         hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DQ>, dim3((unsigned)nb_dq), dim3(256), 0, st, a);
         if (int rc = check_launch("shared_gemm_dq")) return rc;
@@ -513,14 +522,16 @@ extern "C" int64_t amdkge_train_shared_workspace_bytes(const amdkge_model* m, in
     return shared_plan(m, B, G, M, p) ? p.total : 0;
 }
 
-// both step entry points: mask == nullptr is the unmasked step
+// the step entry points: mask == nullptr is the unmasked step; labels != nullptr is the labelled step (loss is not read)
 static int shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int32_t M,
                          const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores,
-                         float* d_neg_scores, void* d_work, const SharedMaskArgs* mask, void* stream) {
+                         float* d_neg_scores, void* d_work, const SharedMaskArgs* mask, void* stream, const SharedLabelArgs* labels = nullptr) {
     if (int rc = validate_model(m)) return rc;
     if (!shared_model_ok(m)) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: TransE and RotatE score a distance, not a contraction: only DistMult, ComplEx and HolE share negatives");
-    if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_shared: unknown loss kind");
-    if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: FocusE is not offered with shared negatives");
+    if (!labels) {
+        if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_shared: unknown loss kind");
+        if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: FocusE is not offered with shared negatives");
+    }
     if (B < 0 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return set_error(AMDKGE_EINVAL, "train_shared: bad sizes (B >= 0, G >= 1, 1 <= M < 2^24)");
     if (!d_ent || !d_rel || !d_grad_ent || !d_grad_rel || !d_loss_sum) return set_error(AMDKGE_EINVAL, "train_shared: NULL table / gradient / loss pointer");
     if (B == 0) return AMDKGE_OK;
@@ -531,8 +542,8 @@ static int shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const f
     hipStream_t st = (hipStream_t)stream;
     char* work = static_cast<char*>(d_work);
     if (m->scoring_type != AMDKGE_DISTMULT)   // ComplEx, and HolE on its instantiation (the 2/k scale travels in ModelConst)
-        return run_shared<true>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st);
-    return run_shared<false>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st);
+        return run_shared<true>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st, labels);
+    return run_shared<false>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st, labels);
 }
 
 extern "C" int amdkge_train_shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
@@ -580,4 +591,17 @@ extern "C" int amdkge_train_shared_masked_fwdbwd(const amdkge_model* m, const am
     if (int rc = shared_mask_args("train_shared_masked", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, d_stats, false, a, masked)) return rc;
     return shared_fwdbwd(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
                          masked ? &a : nullptr, stream);
+}
+
+// (include/amdkge_shared_labels.h)
+extern "C" int amdkge_train_shared_labels_fwdbwd(const amdkge_model* m, float label_smoothing, int32_t reduction_mean, const float* d_ent, const float* d_rel,
+                                                 const int32_t* d_triples, int64_t B, int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side,
+                                                 float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores, void* d_work,
+                                                 const int64_t* d_s_lo, const int64_t* d_s_hi, const int32_t* d_s_ids, const int64_t* d_o_lo, const int64_t* d_o_hi,
+                                                 const int32_t* d_o_ids, int32_t list_mode, const float* d_w_s, const float* d_w_o, int64_t* d_stats, void* stream) {
+    SharedLabelArgs la;
+    if (int rc = shared_label_args("train_shared_labels", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, label_smoothing, reduction_mean, d_w_s,
+                                   d_w_o, d_stats, la)) return rc;
+    return shared_fwdbwd(m, nullptr, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work, nullptr,
+                         stream, &la);
 }

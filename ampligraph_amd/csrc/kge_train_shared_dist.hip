@@ -370,7 +370,7 @@ static bool dist_model_ok(const amdkge_model* m) { return m->scoring_type == AMD
 template <int MODEL>
 static int run_shared_dist(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int M,
                            const int32_t* d_ids, const int32_t* d_side, float* g_ent, float* g_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores,
-                           char* work, const SharedPlan& p, const SharedMaskArgs* mask, hipStream_t st) {
+                           char* work, const SharedPlan& p, const SharedMaskArgs* mask, hipStream_t st, const SharedLabelArgs* labels = nullptr) {
     const int ks = stored_k(m), K = row_floats(m), k = m->k;
     const ModelConst mc = model_const(m);
     float* Q = reinterpret_cast<float*>(work + p.off_q);
@@ -395,13 +395,20 @@ static int run_shared_dist(const amdkge_model* m, const amdkge_loss* loss, const
         a.tiles_m = tg; a.tiles_n = tm;
         hipLaunchKernelGGL((dist_tile_kernel<MODEL, DIST_FWD>), dim3((unsigned)nb_fwd), dim3(256), 0, st, a);
         if (int rc = check_launch("dist_tile_fwd")) return rc;
-        if (mask) {   // known statements -> score -inf: the buffer holds distances, so +inf
-            SharedMaskArgs ma = *mask;
-            ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = G; ma.M = M; ma.ids = d_ids; ma.side = d_side;
-            ma.fill = INFINITY;
-            if (int rc = launch_shared_mask(ma, st)) return rc;
+        if (labels) {   // KvsAll (include/amdkge_shared_labels.h): labels + BCE in one pass, in place of mask + loss
+            SharedLabelArgs la = *labels;
+            la.S = S; la.row0 = row0; la.rows = rows; la.G = G; la.B = B; la.M = M; la.ids = d_ids; la.side = d_side; la.scale = mc.score_sign * mc.score_scale;
+            la.pos_raw = pos_raw; la.cpos = cpos; la.pos_scores = d_pos_scores; la.neg_scores = d_neg_scores; la.loss_sum = d_loss_sum;
+            if (int rc = launch_shared_label_loss(la, st)) return rc;
+        } else {
+            if (mask) {   // known statements -> score -inf: the buffer holds distances, so +inf
+                SharedMaskArgs ma = *mask;
+                ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = G; ma.M = M; ma.ids = d_ids; ma.side = d_side;
+                ma.fill = INFINITY;
+                if (int rc = launch_shared_mask(ma, st)) return rc;
+            }
+            if (int rc = launch_shared_loss(S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum, d_pos_scores, d_neg_scores, st)) return rc;
         }
-        if (int rc = launch_shared_loss(S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum, d_pos_scores, d_neg_scores, st)) return rc;
         a.tiles_m = tg; a.tiles_n = tk;
         hipLaunchKernelGGL((dist_tile_kernel<MODEL, DIST_DQ>), dim3((unsigned)nb_dq), dim3(256), 0, st, a);
         if (int rc = check_launch("dist_tile_dq")) return rc;
@@ -423,18 +430,16 @@ extern "C" int64_t amdkge_train_shared_dist_workspace_bytes(const amdkge_model* 
     return shared_plan(m, B, G, M, p) ? p.total : 0;
 }
 
-extern "C" int amdkge_train_shared_dist_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
-                                               int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel,
-                                               double* d_loss_sum, float* d_pos_scores, float* d_neg_scores, void* d_work, const int64_t* d_s_lo, const int64_t* d_s_hi,
-                                               const int32_t* d_s_ids, const int64_t* d_o_lo, const int64_t* d_o_hi, const int32_t* d_o_ids, int32_t list_mode,
-                                               int64_t* d_stats, void* stream) {
-    SharedMaskArgs ma;
-    bool masked;
-    if (int rc = shared_mask_args("train_shared_dist", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, d_stats, false, ma, masked)) return rc;
+// both step entry points: mask == nullptr is the unmasked step; labels != nullptr is the labelled step (loss is not read)
+static int shared_dist_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int32_t M,
+                              const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores,
+                              float* d_neg_scores, void* d_work, const SharedMaskArgs* mask, const SharedLabelArgs* labels, void* stream) {
     if (int rc = validate_model(m)) return rc;
     if (!dist_model_ok(m)) return set_error(AMDKGE_EUNSUPPORTED, "train_shared_dist: DistMult, ComplEx and HolE score a contraction, not a distance: use amdkge_train_shared_fwdbwd");
-    if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_shared_dist: unknown loss kind");
-    if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "train_shared_dist: FocusE is not offered with shared negatives");
+    if (!labels) {
+        if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_shared_dist: unknown loss kind");
+        if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "train_shared_dist: FocusE is not offered with shared negatives");
+    }
     if (B < 0 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return set_error(AMDKGE_EINVAL, "train_shared_dist: bad sizes (B >= 0, G >= 1, 1 <= M < 2^24)");
     if (!d_ent || !d_rel || !d_grad_ent || !d_grad_rel || !d_loss_sum) return set_error(AMDKGE_EINVAL, "train_shared_dist: NULL table / gradient / loss pointer");
     if (B == 0) return AMDKGE_OK;
@@ -444,8 +449,33 @@ extern "C" int amdkge_train_shared_dist_fwdbwd(const amdkge_model* m, const amdk
     if (!shared_plan(m, B, G, M, p)) return set_error(AMDKGE_EINVAL, "train_shared_dist: bad sizes");
     hipStream_t st = (hipStream_t)stream;
     char* work = static_cast<char*>(d_work);
-    const SharedMaskArgs* mask = masked ? &ma : nullptr;
     if (m->scoring_type == AMDKGE_ROTATE)
-        return run_shared_dist<AMDKGE_ROTATE>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st);
-    return run_shared_dist<AMDKGE_TRANSE>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st);
+        return run_shared_dist<AMDKGE_ROTATE>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st, labels);
+    return run_shared_dist<AMDKGE_TRANSE>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st, labels);
+}
+
+extern "C" int amdkge_train_shared_dist_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
+                                               int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel,
+                                               double* d_loss_sum, float* d_pos_scores, float* d_neg_scores, void* d_work, const int64_t* d_s_lo, const int64_t* d_s_hi,
+                                               const int32_t* d_s_ids, const int64_t* d_o_lo, const int64_t* d_o_hi, const int32_t* d_o_ids, int32_t list_mode,
+                                               int64_t* d_stats, void* stream) {
+    SharedMaskArgs ma;
+    bool masked;
+    if (int rc = shared_mask_args("train_shared_dist", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, d_stats, false, ma, masked)) return rc;
+    return shared_dist_fwdbwd(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
+                              masked ? &ma : nullptr, nullptr, stream);
+}
+
+// (include/amdkge_shared_labels.h)
+extern "C" int amdkge_train_shared_dist_labels_fwdbwd(const amdkge_model* m, float label_smoothing, int32_t reduction_mean, const float* d_ent, const float* d_rel,
+                                                      const int32_t* d_triples, int64_t B, int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side,
+                                                      float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores, void* d_work,
+                                                      const int64_t* d_s_lo, const int64_t* d_s_hi, const int32_t* d_s_ids, const int64_t* d_o_lo,
+                                                      const int64_t* d_o_hi, const int32_t* d_o_ids, int32_t list_mode, const float* d_w_s, const float* d_w_o,
+                                                      int64_t* d_stats, void* stream) {
+    SharedLabelArgs la;
+    if (int rc = shared_label_args("train_shared_dist_labels", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, label_smoothing, reduction_mean,
+                                   d_w_s, d_w_o, d_stats, la)) return rc;
+    return shared_dist_fwdbwd(m, nullptr, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
+                              nullptr, &la, stream);
 }

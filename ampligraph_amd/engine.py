@@ -547,6 +547,66 @@ class KgeEngine:
             _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]),
             _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
 
+    def shared_label_loss(self, scores, row0, group_size, ids, side, s_filter, o_filter, label_smoothing=0.0, reduction="sum", scale=1.0,
+                          weights=None, identity=False, loss_sum=None, stats=None):
+        """amdkge_shared_label_loss (include/amdkge_shared_labels.h): the loss step of the labelled (KvsAll) shared step alone, in
+        place on the fp32 device tensor scores [rows, M] whose row r is batch row row0 + r: scores in, scale * dL/dscore out.  An
+        entry is labelled 1 when its id is in the row's known range -- s_filter / o_filter: (lo, hi, ids) of the B batch rows
+        (FilterIndex.device_filter's form) --, the loss is binary cross-entropy with logits on scale * score.  side int32 [B]; ids
+        int32 [ceil(B / group_size), M] (may be None with identity=True, the promise that ids[g][j] == j); weights: None or (w_s,
+        w_o) fp32 [B] device tensors; loss_sum: float64 [1] device tensor, += the rows' losses (default: loss_acc[0]); stats: int64
+        [2] device tensor, += (labelled, unlabelled_rows)."""
+        rows, M = int(scores.shape[0]), int(scores.shape[1])
+        B = int(side.shape[0])
+        if int(row0) < 0 or int(row0) + rows > B or not scores.is_contiguous():
+            raise ValueError("shared_label_loss: rows [row0, row0 + rows) must lie inside the batch and the buffer be contiguous")
+        G = max(1, min(int(group_size), B)) if int(group_size) >= 1 else int(group_size)
+        ws, wo = weights if weights is not None else (None, None)
+        acc = self.loss_acc if loss_sum is None else loss_sum
+        check(self.lib.amdkge_shared_label_loss(
+            _ptr(scores), int(row0), rows, G, M, _ptr(ids), _ptr(side), _ptr(s_filter[0]), _ptr(s_filter[1]), _ptr(s_filter[2]),
+            _ptr(o_filter[0]), _ptr(o_filter[1]), _ptr(o_filter[2]), _ffi.SHARED_LIST_MODES["identity" if identity else "given"],
+            float(label_smoothing), 1 if reduction == "mean" else 0, float(scale), _ptr(ws), _ptr(wo), C.c_void_p(acc.data_ptr()), _ptr(stats), _stream()))
+        return scores
+
+    def _train_shared_labels(self, fn, ws_fn, who, triples, group_size, num_negs, ids, side, s_filter, o_filter, label_smoothing, reduction, weights,
+                             identity, stats, pos_scores, neg_scores):
+        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
+        if s_filter is None or o_filter is None:
+            raise ValueError(who + ": s_filter and o_filter are both required (the labels are the known ranges)")
+        need = int(ws_fn(C.byref(self.model), B, G, M)) if B > 0 else 0
+        if B > 0 and need <= 0:
+            raise ValueError(who + ": the labelled shared step is not offered for this model / shape "
+                             f"({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
+        work = self._buf("shared_work", (need,), torch.uint8)
+        ws, wo = weights if weights is not None else (None, None)
+        check(fn(
+            C.byref(self.model), float(label_smoothing), 1 if reduction == "mean" else 0, _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M,
+            _ptr(ids), _ptr(side), _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores),
+            _ptr(work), _ptr(s_filter[0]), _ptr(s_filter[1]), _ptr(s_filter[2]), _ptr(o_filter[0]), _ptr(o_filter[1]), _ptr(o_filter[2]),
+            _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(ws), _ptr(wo), _ptr(stats), _stream()))
+
+    def train_shared_labels_fwdbwd(self, triples, group_size, num_negs, ids, side, s_filter, o_filter, label_smoothing=0.0, reduction="sum",
+                                   weights=None, identity=False, stats=None, pos_scores=None, neg_scores=None):
+        """amdkge_train_shared_labels_fwdbwd (include/amdkge_shared_labels.h): the KvsAll step of DistMult / ComplEx / HolE -- the
+        shared step in which every row is a query, every entry of its list a binary classification labelled 1 when its id is in the
+        row's known range (s_filter / o_filter: (lo, hi, ids) of the B positives, both required), and the loss binary
+        cross-entropy with logits, label_smoothing in [0, 1), reduction "sum" | "mean" (over the list).  weights: None or (w_s,
+        w_o) fp32 [B] row weights by replaced side; identity: the promise that ids[g][j] == j (the all-entities list); stats: int64
+        [2] device tensor, += (labelled, unlabelled_rows).  Accumulates into g_ent / g_rel and loss_acc[0]; neg_scores
+        (optional) has row j * B + i and shows the plain scores."""
+        self._train_shared_labels(self.lib.amdkge_train_shared_labels_fwdbwd, self.lib.amdkge_train_shared_workspace_bytes, "train_shared_labels_fwdbwd",
+                                  triples, group_size, num_negs, ids, side, s_filter, o_filter, label_smoothing, reduction, weights, identity, stats,
+                                  pos_scores, neg_scores)
+
+    def train_shared_dist_labels_fwdbwd(self, triples, group_size, num_negs, ids, side, s_filter, o_filter, label_smoothing=0.0, reduction="sum",
+                                        weights=None, identity=False, stats=None, pos_scores=None, neg_scores=None):
+        """amdkge_train_shared_dist_labels_fwdbwd: train_shared_labels_fwdbwd's step for TransE and RotatE, on the distance tiles of
+        train_shared_dist_fwdbwd.  The arguments are that method's."""
+        self._train_shared_labels(self.lib.amdkge_train_shared_dist_labels_fwdbwd, self.lib.amdkge_train_shared_dist_workspace_bytes,
+                                  "train_shared_dist_labels_fwdbwd", triples, group_size, num_negs, ids, side, s_filter, o_filter, label_smoothing,
+                                  reduction, weights, identity, stats, pos_scores, neg_scores)
+
     def batch_reg_fwdbwd(self, triples, reg_e=None, reg_r=None):
         """amdkge_batch_reg_fwdbwd (include/amdkge_batch_reg.h): the batch regularisers reg_e / reg_r (BatchLPRegularizer or None:
         that term is off) on the rows of the int32 device positives [B, 3], once per occurrence.  Runs between a forward / backward

@@ -67,10 +67,37 @@ class NLLMulticlass(Loss):
     pass
 
 
+class BCELoss(Loss):
+    """Binary cross-entropy with logits over a row's WHOLE list, every entry labelled 1 when it is a known answer of the row's query:
+    the loss of KvsAll training (ConvE; LibKGE's strongest DistMult / ComplEx configurations).  It exists only with
+    compile(negatives=KvsAll(...)) and runs inside shared_label_loss_kernel (include/amdkge_shared_labels.h has the arithmetic).
+    Hyper-parameters: "reduction" ("sum" | "mean" over the list) and "label_smoothing" in [0, 1) (default 0: the target of an entry
+    is (1 - eps) y + eps / M).  Not in LOSS_REGISTRY, which keeps the reference's five names: pass an instance,
+    compile(loss=BCELoss({...})); get() also takes the name "bce"."""
+
+    name = "bce"
+    labelled = True   # what compile() and trainer.StepLoop look for
+
+    def _init_hyperparams(self, h):
+        eps = h.get("label_smoothing", 0.0)
+        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= float(eps) < 1.0:
+            raise ValueError("BCELoss: `label_smoothing` must be a number in [0, 1), got {!r}".format(eps))
+        self._loss_parameters["label_smoothing"] = float(eps)
+
+    def to_ffi(self):
+        raise NotImplementedError("BCELoss has no amdkge_loss kind: it is the loss step of the labelled shared step "
+                                  "(compile(negatives=KvsAll(...)), include/amdkge_shared_labels.h)")
+
+
+EXTRA_LOSSES = {"bce": BCELoss}   # names get() takes beyond the reference's registry
+
+
 def get(identifier, hyperparams=None):
     """loss_functions.py:720-766: Loss instance | registered name | callable."""
     if isinstance(identifier, Loss):
         return identifier
+    if isinstance(identifier, str) and identifier in EXTRA_LOSSES:
+        return EXTRA_LOSSES[identifier](hyperparams or {})
     if isinstance(identifier, str):
         if identifier not in LOSS_REGISTRY:
             raise ValueError("Could not interpret loss identifier:", identifier)

@@ -88,20 +88,28 @@ class ScoringBasedEmbeddingModel:
     def from_config(cls, config):
         config = dict(config)
         regs = config.pop("entity_relation_regularizer", None)
+        negs = config.pop("negatives", None)
         model = cls(**config)
         if regs is not None:   # carried until compile() sets its own
             model._regularizers = [regularizers.from_config(r) for r in regs]
+        if negs is not None:   # a KvsAll sampler in its dict form: carried the same way (restore_model compiles with it)
+            from .negatives import NegativeSampling
+
+            model._negatives = NegativeSampling.get(negs)
         return model
 
     def get_config(self):
         """The constructor arguments, like the reference's Keras config (:84-98) -- and, for a model whose [entity, relation]
         regularisers include a batch regulariser (regularizers.BatchLPRegularizer), the pair in its JSON form: the step it
-        trains with differs in kind, not in a number.  Every other model's config is the constructor arguments alone."""
+        trains with differs in kind, not in a number; for a model compiled with a KvsAll sampler, the sampler's dict form under
+        "negatives" (its loss, BCELoss, compiles with nothing else).  Every other model's config is the constructor arguments alone."""
         cfg = {"eta": self.eta, "k": self.k, "scoring_type": self.scoring_type, "seed": self.seed,
                "max_ent_size": self.max_ent_size, "max_rel_size": self.max_rel_size}
         regs = getattr(self, "_regularizers", None)
         if regs and any(regularizers.is_batch(r) for r in regs):
             cfg["entity_relation_regularizer"] = [regularizers.to_config(r) for r in regs]
+        if getattr(self._negatives, "kvsall", False):   # KvsAll: its loss (BCELoss) cannot be compiled without it
+            cfg["negatives"] = self._negatives.get_config()
         return cfg
 
     def get_invalid_keys(self, X, data_type="raw", **kwargs):
@@ -140,7 +148,10 @@ class ScoringBasedEmbeddingModel:
         model.negative_sampling_stats_ = {"masked", "unmaskable"} after fit(); groups of positives share one list of replacements, scored by a
         matrix product: DistMult / ComplEx / HolE on one GPU, no deterministic, lazy or FocusE mode) | SharedDistanceNegatives | its dict form
         {"shared_distance": num_negs | "all", "group_size", "side", "entities", "mask_known"} (the same step for TransE / RotatE, scored on
-        distance tiles; the same refusals).  Multi-GPU, one process per GPU under torch.distributed:
+        distance tiles; the same refusals) | KvsAll | its dict form {"kvsall": "all", "side", "weight", "known", "group_size"} (KvsAll training,
+        all five models: every entity is a binary classification, all known answers of a row's query are labelled 1; only with
+        loss=BCELoss({"reduction", "label_smoothing"}), which in turn compiles with nothing else; weight="query" weighs a row by 1 / the rows
+        sharing its query; model.negative_sampling_stats_ = {"labelled", "unlabelled_rows"} after fit(); the same refusals).  Multi-GPU, one process per GPU under torch.distributed:
         entity_sharding="replicated" (default: tables replicated, gradient all-reduce) | "rows" (entity table
         row-sharded over the ranks, ampligraph_amd/sharded.py; sharded_negatives="local" | "global" chooses where its corruptions
         are drawn from) | "columns" (tables that fit every GPU: rank r TRAINS on k / W units of every row and the whole batch, one
@@ -174,6 +185,13 @@ class ScoringBasedEmbeddingModel:
         if loss is None:
             raise ValueError("compile(): a loss is required")
         self.loss = loss_functions.get(loss)
+        # KvsAll and BCELoss exist only together (include/amdkge_shared_labels.h: the labels are the loss step's)
+        if getattr(self._negatives, "kvsall", False) and not getattr(self.loss, "labelled", False):
+            raise NotImplementedError("negatives: KvsAll labels every entity for a binary cross-entropy and takes loss=BCELoss(...) only; the softmax "
+                                      "over every entity with the other known answers masked is SharedNegatives('all', mask_known=True) "
+                                      "with loss='multiclass_nll', not {!r}".format(self.loss.name))
+        if getattr(self.loss, "labelled", False) and not getattr(self._negatives, "kvsall", False):
+            raise NotImplementedError("loss: BCELoss is the loss of KvsAll training: compile(negatives=KvsAll(...), loss=BCELoss(...))")
         ini = entity_relation_initializer
         self._initializers = list(ini) if isinstance(ini, (list, tuple)) else [ini, ini]
         if len(self._initializers) != 2:

@@ -19,6 +19,10 @@ scores of corruptions that are known statements are -inf before the loss).  num_
 `SharedDistanceNegatives` is SharedNegatives for TransE and RotatE, whose score against a shared list is a tile of distances instead
 of a matrix product (kge_train_shared_dist.hip, include/amdkge_shared_dist.h).  It binds to the same two classes with
 `distance = True` set: their step is engine.train_shared_dist_fwdbwd.
+
+`KvsAll` is the shared step on the all-entities list with LABELS instead of a mask: every known answer of a row's query is labelled
+1 and the loss is binary cross-entropy (loss_functions.BCELoss; include/amdkge_shared_labels.h).  It binds to a `BoundKvsAll`, whose
+step is engine.train_shared_labels_fwdbwd, or engine.train_shared_dist_labels_fwdbwd for TransE / RotatE.
 """
 import numpy as np
 
@@ -60,6 +64,8 @@ class NegativeSampling:
             return SharedNegatives.from_dict(spec)
         if isinstance(spec, dict) and "shared_distance" in spec:   # {"shared_distance": M, ...}: SharedDistanceNegatives(num_negs=M, ...)
             return SharedDistanceNegatives.from_dict(spec)
+        if isinstance(spec, dict) and "kvsall" in spec:   # {"kvsall": "all", ...}: KvsAll
+            return KvsAll.from_dict(spec)
         if isinstance(spec, dict) and "types" in spec:    # {"types": "observed" | RelationTypes, ...}: TypedNegatives
             return TypedNegatives.from_dict(spec)
         if isinstance(spec, dict):
@@ -422,3 +428,123 @@ class BoundMaskedSharedNegatives(BoundSharedNegatives):
         (left unmasked): one device read (synchronises the stream)."""
         mk, un = (int(v) for v in self.stats_dev.tolist())
         return {"masked": mk, "unmaskable": un}
+
+
+class KvsAll:
+    """KvsAll training (ConvE, LibKGE): a training row is a QUERY (s, p, ?) or (?, p, o) -- the side is drawn per row, as in
+    SharedNegatives --, EVERY entity is a binary classification, and all KNOWN answers of the query are labelled 1 instead of being
+    masked away.  The loss is loss_functions.BCELoss (binary cross-entropy with logits, optional label smoothing), and only that one;
+    the softmax over the same list is SharedNegatives("all", mask_known=True) + multiclass_nll.  The step is the shared step on the
+    all-entities list in id order (include/amdkge_shared_labels.h: labels and loss are one pass over a chunk's scores), for all five
+    models: matrix products for DistMult / ComplEx / HolE, distance tiles for TransE / RotatE.
+
+    side: "uniform" | "bernoulli" | "s" | "o", decided per row.
+    weight: "triple" (every training triple is a row of weight 1) | "query" (a row weighs 1 / the number of training rows that share
+    its query -- (s, p) when the object is asked for, (p, o) when the subject is: with a fixed side an epoch's loss is then exactly
+    the loss over the UNIQUE queries, LibKGE's KvsAll objective, without touching the batch loop).
+    known: True (the training set) | a non-empty dict of datasets known next to it, in SharedNegatives(mask_known=...)'s form.
+    group_size: the rows per group; None = SharedNegatives.ALL_GROUP_SIZE.  The result does not depend on it.
+    There is no `entities`: the list is every entity.  After fit(): model.negative_sampling_stats_ = {"labelled", "unlabelled_rows"}.
+
+    compile(negatives=KvsAll(...), loss=BCELoss({...})) or compile(negatives={"kvsall": "all", "side": ..., "weight": ..., "known": ...,
+    "group_size": ...}, ...)."""
+
+    shared = True   # what trainer.StepLoop.step looks for
+    kvsall = True   # what compile() looks for
+    KEY = "kvsall"
+
+    def __init__(self, side="uniform", weight="triple", known=True, group_size=None):
+        if not isinstance(side, str) or side not in _ffi.NEG_SIDE_MODES:
+            raise ValueError("negatives: `side` must be 'uniform', 'bernoulli', 's' or 'o', got {!r}".format(side))
+        if not isinstance(weight, str) or weight not in ("triple", "query"):
+            raise ValueError("negatives: `weight` must be 'triple' or 'query', got {!r}".format(weight))
+        if not (known is True or (isinstance(known, dict) and len(known) > 0)):
+            raise ValueError("negatives: `known` must be True (the training set) or a non-empty dict of datasets known next to it")
+        if group_size is not None and (isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer)) or not 1 <= int(group_size) <= 2 ** 31 - 1):
+            raise ValueError("negatives: `group_size` must be None or an integer in [1, {}]".format(2 ** 31 - 1))
+        self.side, self.weight, self.known = side, weight, known
+        self.group_size = SharedNegatives.ALL_GROUP_SIZE if group_size is None else int(group_size)
+
+    @classmethod
+    def from_dict(cls, spec):
+        if spec[cls.KEY] != "all":
+            raise ValueError("negatives: {{'kvsall': 'all'}} is the one list KvsAll has, got {!r}".format(spec[cls.KEY]))
+        unknown = set(spec) - {cls.KEY, "side", "weight", "known", "group_size"}
+        if unknown:
+            raise ValueError("negatives: unknown keys {} for KvsAll (there is no `entities`: the list is every entity)".format(sorted(unknown)))
+        return cls(spec.get("side", "uniform"), spec.get("weight", "triple"), spec.get("known", True), spec.get("group_size"))
+
+    def get_config(self):
+        """The dict form compile(negatives=...) takes (datasets as given)."""
+        return {self.KEY: "all", "side": self.side, "weight": self.weight, "known": self.known, "group_size": self.group_size}
+
+    def check_model(self, model, optimizer_mode="dense"):
+        """compile()'s refusals: everything that is known before a GPU is touched (all five models take part)."""
+        SharedNegatives._check_modes(model, optimizer_mode)
+
+    @staticmethod
+    def query_weights(train):
+        """train: int [n, 3] id triples -> (w_s, w_o) float32 [n]: 1 / the number of rows sharing the row's (p, o) / (s, p)."""
+        t = np.asarray(train, dtype=np.int64).reshape(-1, 3)
+        out = []
+        for a, b in ((1, 2), (0, 1)):
+            _, inv, cnt = np.unique(t[:, [a, b]], axis=0, return_inverse=True, return_counts=True)
+            out.append((1.0 / cnt[inv.reshape(-1)]).astype(np.float32))
+        return out[0], out[1]
+
+    def bind(self, model, engine, train):
+        import torch
+
+        loop = getattr(model, "_loop", None)
+        if getattr(model, "use_focusE", False):
+            raise NotImplementedError("negatives: FocusE is not offered with shared negatives")
+        if getattr(loop, "multi", False):
+            raise NotImplementedError("negatives: shared negatives run on one rank only")
+        if getattr(loop, "deterministic", False):
+            raise NotImplementedError("negatives: shared negatives accumulate in no fixed order; deterministic mode is not offered")
+        N, R = int(model._n_ents), int(model._n_rels)
+        if N > _ffi.SHARED_MAX_NEGS:
+            raise ValueError("negatives: KvsAll needs at most {} entities".format(_ffi.SHARED_MAX_NEGS))
+        extra = []
+        if isinstance(self.known, dict):
+            from .models import _load_triples
+
+            extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in self.known.values()]
+        index = FilterIndex([train] + extra, N, R, engine=engine)
+        side_thr = None
+        if self.side == "bernoulli":
+            side_thr = engine.negatives_side_thresholds(*index.device_keys(engine), index.n_ents, index.n_rels)
+        weights = None
+        if self.weight == "query":   # both arrays once, in numpy
+            weights = tuple(torch.as_tensor(w).to(engine.device) for w in self.query_weights(train.cpu().numpy()))
+        all_list = torch.arange(N, dtype=torch.int32, device=engine.device)
+        bound = BoundKvsAll(engine, N, self.group_size, self.side, side_thr, None, all_list=all_list, train=train, index=index, identity=True,
+                            weights=weights)
+        bound.distance = model.scoring_type in ("TransE", "RotatE")   # trainer.StepLoop.step: engine.train_shared_dist_labels_fwdbwd
+        return bound
+
+
+class BoundKvsAll(BoundMaskedSharedNegatives):
+    """A KvsAll bound to one fit(): BoundMaskedSharedNegatives' index and range arrays (mask(global_batch) slices them: here they
+    are the LABELS), the all-entities list, and the row weights of weight="query" (weights(global_batch) slices them).
+    trainer.StepLoop.step hands them to engine.train_shared_labels_fwdbwd / train_shared_dist_labels_fwdbwd."""
+
+    labelled = True
+
+    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity, weights=None):
+        super().__init__(engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity)
+        self.row_weights = weights
+
+    def weights(self, global_batch):
+        """-> None or (w_s, w_o) of the batch's rows"""
+        if self.row_weights is None:
+            return None
+        r0 = BoundNegatives._first_row(self, global_batch)
+        r1 = r0 + int(global_batch.shape[0])
+        return tuple(w[r0:r1] for w in self.row_weights)
+
+    def stats(self):
+        """{"labelled", "unlabelled_rows"} since the bind -- the entries labelled 1 and the rows without one: one device read
+        (synchronises the stream)."""
+        lb, un = (int(v) for v in self.stats_dev.tolist())
+        return {"labelled": lb, "unlabelled_rows": un}

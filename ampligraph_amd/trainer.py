@@ -86,7 +86,10 @@ class StepLoop:
           "auto"     : measured on the first steps (tune_merge; AMDKGE_DP_MERGE=auto)."""
         self.engine = engine
         self.eta = int(eta)
-        self.loss_ffi = loss.to_ffi()
+        # loss_functions.BCELoss has no amdkge_loss descriptor: it is the loss step of the labelled shared step (KvsAll), which takes
+        # its two hyper-parameters as arguments
+        self.label_loss = loss if getattr(loss, "labelled", False) else None
+        self.loss_ffi = None if self.label_loss is not None else loss.to_ffi()
         self.optimizer = optimizer
         # regulariser of the entity table; the relation table takes `reg_rel` -- "same" (the default: one regulariser for both,
         # EmbeddingLookupLayer.py:153-155), None, or its own object (an [entity, relation] pair, :147-152)
@@ -128,7 +131,8 @@ class StepLoop:
         # row (latent_features/negatives.py: BoundNegatives), which the step hands to the train kernels as their override; or an object
         # with `.shared` set (BoundSharedNegatives: .draw(), .group_size, .num_negs), whose step is engine.train_shared_fwdbwd -- or, when
         # it has a .mask() (BoundMaskedSharedNegatives), engine.train_shared_masked_fwdbwd; with `.distance` set too
-        # (SharedDistanceNegatives: TransE, RotatE) both are engine.train_shared_dist_fwdbwd
+        # (SharedDistanceNegatives: TransE, RotatE) both are engine.train_shared_dist_fwdbwd; with `.labelled` set (BoundKvsAll, with
+        # loss_functions.BCELoss) engine.train_shared_labels_fwdbwd / train_shared_dist_labels_fwdbwd
         self.negatives = None
         engine.prepare_training(optimizer.name)
         if hasattr(optimizer, "bind"):
@@ -161,7 +165,12 @@ class StepLoop:
         eng = self.engine
         bg = int(global_batch.shape[0])
         lo, hi = shard_bounds(bg, self.world, self.rank)
-        if focus is not None:
+        if self.label_loss is not None:
+            if focus is not None or not getattr(self.negatives, "labelled", False):
+                raise NotImplementedError("BCELoss is the loss of the labelled shared step: it needs compile(negatives=KvsAll(...)) and takes no FocusE")
+        elif getattr(self.negatives, "labelled", False):
+            raise NotImplementedError("KvsAll labels every entity for a binary cross-entropy: it needs loss=BCELoss(...)")
+        elif focus is not None:
             from . import _ffi
 
             fw = focus[0][lo:hi].contiguous()   # kept alive until the launches below are enqueued
@@ -197,7 +206,14 @@ class StepLoop:
                 sh = self.negatives
                 ids, side = sh.draw(global_batch, self.seed, rng_step)
                 mask = getattr(sh, "mask", None)   # BoundMaskedSharedNegatives: known statements score -inf (kge_train_shared.hip, shared_mask_kernel)
-                if getattr(sh, "distance", False):   # SharedDistanceNegatives: distance tiles (kge_train_shared_dist.hip), one entry point for both
+                if getattr(sh, "labelled", False):   # KvsAll: labels + BCE in one pass over a chunk's scores (kge_train_shared_labels.hip)
+                    s_filter, o_filter = mask(global_batch)
+                    lp = self.label_loss._loss_parameters
+                    step_fn = eng.train_shared_dist_labels_fwdbwd if getattr(sh, "distance", False) else eng.train_shared_labels_fwdbwd
+                    step_fn(global_batch, sh.group_size, sh.num_negs, ids, side, s_filter, o_filter, label_smoothing=lp["label_smoothing"],
+                            reduction=lp["reduction"], weights=sh.weights(global_batch), identity=bool(getattr(sh, "identity", False)),
+                            stats=getattr(sh, "stats_dev", None))
+                elif getattr(sh, "distance", False):   # SharedDistanceNegatives: distance tiles (kge_train_shared_dist.hip), one entry point for both
                     kw = {}
                     if mask is not None:
                         s_filter, o_filter = mask(global_batch)

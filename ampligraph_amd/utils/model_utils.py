@@ -31,7 +31,7 @@ def save_model(model, model_name_path=None, protocol=None):
         meta["config"] = model.get_config()
         meta["focusE"] = getattr(model, "focusE_params", None) if getattr(model, "use_focusE", False) else None
         with open(base + ".json.tmp", "w") as f:
-            json.dump(meta, f)
+            json.dump(meta, f, default=lambda o: o.tolist())   # (a KvsAll sampler's `known` datasets may be numpy arrays)
         os.replace(base + ".json.tmp", base + ".json")
     if d is not None:
         d.barrier()
@@ -58,8 +58,10 @@ def restore_model(model_name_path=None):
 
         # (a member without a "kind" field is a whole-table LPRegularizer: what checkpoints held before the batch regularisers)
         regs = [regularizers.from_config(r) for r in (meta.get("regularizer") or [None, None])]
+        # (a KvsAll sampler travels in the config: from_config has put it on the model, and BCELoss compiles only with it)
+        kw = {"negatives": model._negatives} if getattr(model._negatives, "kvsall", False) else {}
         model.compile(optimizer=optimizers.get(name, oc), loss=loss_functions.get(meta["loss"]["name"], prm),
-                      entity_relation_regularizer=regs)
+                      entity_relation_regularizer=regs, **kw)
     model.load_weights(base)
     if meta.get("focusE"):
         model.use_focusE, model.focusE_params = True, meta["focusE"]
