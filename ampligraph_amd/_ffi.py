@@ -217,6 +217,12 @@ BATCH_REG_SIGNATURES = {
     "amdkge_batch_reg_fwdbwd": (C.c_int, [C.POINTER(Model), P, P, P, I64, I32, C.c_float, I32, I32, C.c_float, I32, P, P, P, P]),
 }
 
+# include/amdkge_relation_objective.h (the relation-prediction training objective: a softmax over the relation table): again a table of its own
+RELATION_OBJECTIVE_SIGNATURES = {
+    "amdkge_train_relation_workspace_bytes": (I64, [C.POINTER(Model), I64]),
+    "amdkge_train_relation_fwdbwd": (C.c_int, [C.POINTER(Model), C.POINTER(Loss), C.c_float, P, P, P, I64, P, P, P, P, P, P, P, P, P, P, P]),
+}
+
 # include/amdkge_types.h (type-constrained negatives and evaluation: per-relation domain / range sets): again a table of its own
 TYPES_SIGNATURES = {
     "amdkge_relation_sets_build": (C.c_int, [P, I64, I32, I64, I64, P, P, P, P, P, P]),
@@ -241,7 +247,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(SHARED_SIGNATURES.items()) + list(SHARED_MASK_SIGNATURES.items()) + list(SHARED_DIST_SIGNATURES.items()) + list(SHARED_LABELS_SIGNATURES.items()) + list(BATCH_REG_SIGNATURES.items()) + list(TYPES_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(SHARED_SIGNATURES.items()) + list(SHARED_MASK_SIGNATURES.items()) + list(SHARED_DIST_SIGNATURES.items()) + list(SHARED_LABELS_SIGNATURES.items()) + list(BATCH_REG_SIGNATURES.items()) + list(RELATION_OBJECTIVE_SIGNATURES.items()) + list(TYPES_SIGNATURES.items()):
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -622,6 +622,25 @@ class KgeEngine:
             C.byref(self.model), _ptr(self.ent), _ptr(self.rel), _ptr(triples), int(triples.shape[0]), *terms,
             _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr() + 8), _stream()))
 
+    def train_relation_fwdbwd(self, triples, loss, weight, flt=None, stats=None, pos_scores=None, rel_scores=None):
+        """amdkge_train_relation_fwdbwd (include/amdkge_relation_objective.h): the relation-prediction term on the int32 device
+        positives [B, 3] -- the train step of train_fwdbwd with eta = n_rels on the rows (s_i, j, o_i), j = 0 .. n_rels - 1, as matrix
+        products over the relation table, times `weight`.  flt: None (nothing is masked) or (lo, hi, ids), each positive's range of
+        known relation ids (PairFilterIndex.device_filter's form): those scores are -inf before the loss, a positive whose every
+        relation is known keeps its row; stats: int64 [2] device tensor, += (masked, unmaskable).  Runs between a forward / backward
+        call that leaves dense gradients and opt_step: accumulates into g_ent / g_rel and weight * loss into loss_acc[0];
+        rel_scores (optional, [n_rels * B]) has row j * B + i."""
+        B = int(triples.shape[0])
+        need = int(self.lib.amdkge_train_relation_workspace_bytes(C.byref(self.model), B)) if B > 0 else 0
+        if B > 0 and need <= 0:
+            raise ValueError(f"train_relation_fwdbwd: the relation objective is not offered for this model / shape ({self.scoring_type}, B={B})")
+        work = self._buf("relation_work", (need,), torch.uint8)
+        lo, hi, ids = flt if flt is not None else (None, None, None)
+        check(self.lib.amdkge_train_relation_fwdbwd(
+            C.byref(self.model), C.byref(loss), float(weight), _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, _ptr(lo), _ptr(hi), _ptr(ids),
+            _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(rel_scores), _ptr(work), _ptr(stats),
+            _stream()))
+
     def negatives_side_thresholds(self, po_keys, sp_keys, n_ents=None, n_rels=None):
         """amdkge_negatives_side_thresholds: the Bernoulli thresholds floor(2^32 G_po / (G_sp + G_po)) per relation from a
         FilterIndex's two int64 device key arrays -> int32 device tensor [n_rels] holding the uint32 bit patterns."""

@@ -76,6 +76,7 @@ class ScoringBasedEmbeddingModel:
         self._sharded_negatives = "local"
         self._deterministic = False
         self._negatives = None       # compile(negatives=...): latent_features/negatives.py
+        self._relation_prediction = None   # compile(relation_prediction=...): latent_features/relation_prediction.py
         self._dist_override = None   # tests: an object with the torch.distributed collective surface
 
     @property
@@ -89,7 +90,12 @@ class ScoringBasedEmbeddingModel:
         config = dict(config)
         regs = config.pop("entity_relation_regularizer", None)
         negs = config.pop("negatives", None)
+        relp = config.pop("relation_prediction", None)
         model = cls(**config)
+        if relp is not None:   # the relation-prediction term in its dict form: carried until compile() (restore_model compiles with it)
+            from .relation_prediction import RelationPrediction
+
+            model._relation_prediction = RelationPrediction.get(relp)
         if regs is not None:   # carried until compile() sets its own
             model._regularizers = [regularizers.from_config(r) for r in regs]
         if negs is not None:   # a KvsAll sampler in its dict form: carried the same way (restore_model compiles with it)
@@ -102,7 +108,8 @@ class ScoringBasedEmbeddingModel:
         """The constructor arguments, like the reference's Keras config (:84-98) -- and, for a model whose [entity, relation]
         regularisers include a batch regulariser (regularizers.BatchLPRegularizer), the pair in its JSON form: the step it
         trains with differs in kind, not in a number; for a model compiled with a KvsAll sampler, the sampler's dict form under
-        "negatives" (its loss, BCELoss, compiles with nothing else).  Every other model's config is the constructor arguments alone."""
+        "negatives" (its loss, BCELoss, compiles with nothing else); for a model compiled with relation_prediction=..., the term's dict
+        form under "relation_prediction".  Every other model's config is the constructor arguments alone."""
         cfg = {"eta": self.eta, "k": self.k, "scoring_type": self.scoring_type, "seed": self.seed,
                "max_ent_size": self.max_ent_size, "max_rel_size": self.max_rel_size}
         regs = getattr(self, "_regularizers", None)
@@ -110,6 +117,8 @@ class ScoringBasedEmbeddingModel:
             cfg["entity_relation_regularizer"] = [regularizers.to_config(r) for r in regs]
         if getattr(self._negatives, "kvsall", False):   # KvsAll: its loss (BCELoss) cannot be compiled without it
             cfg["negatives"] = self._negatives.get_config()
+        if self._relation_prediction is not None:   # the relation-prediction term: the step it trains with has one call more
+            cfg["relation_prediction"] = self._relation_prediction.get_config()
         return cfg
 
     def get_invalid_keys(self, X, data_type="raw", **kwargs):
@@ -158,7 +167,18 @@ class ScoringBasedEmbeddingModel:
         all-reduce of the partial scores per step -- ampligraph_amd/colsharded.py.  Memory and host cost of that mode: every rank
         keeps the WHOLE tables and their whole optimizer slots next to its slice -- predict / evaluate / save_weights / callbacks
         read them -- and they are refreshed from the slices through host numpy (all_gather + column merge) after each fit(),
-        before each validation pass and, when any rank's fit() was given callbacks, on every rank before the callbacks of every epoch)."""
+        before each validation pass and, when any rank's fit() was given callbacks, on every rank before the callbacks of every epoch).
+        relation_prediction=None (default: nothing changes) | RelationPrediction | its dict form {"weight", "loss", "loss_params",
+        "known"} (latent_features/relation_prediction.py): the auxiliary objective of Chen et al. 2021 -- every step adds weight *
+        loss over the scores of each positive's (s, o) pair against EVERY relation (loss: "multiclass_nll" by default; known: True --
+        the other relations the training set holds for the pair are masked --, a dict of further datasets, or False), computed by
+        three fp32 matrix products over the relation table between the step's backward call and the optimizer sweep
+        (include/amdkge_relation_objective.h); its weighted loss is part of the epoch loss; model.relation_prediction_stats_ =
+        {"masked", "unmaskable"} after fit().  DistMult / ComplEx / HolE on one GPU with replicated tables; no deterministic, lazy or
+        FocusE mode.  Like a batch regulariser it makes per-corruption training take the dense-gradient step (train_fwdbwd ->
+        train_relation_fwdbwd -> opt_step) instead of the owner-computes one.  Measured once at ComplEx k = 200, B = 10 000, R = 237
+        (DESIGN.md section 5): the term adds 0.44 ms per step (DistMult 0.36) -- 0.40 -> 0.83 ms on SharedNegatives(256), 15.1 -> 15.6 ms
+        on the all-entities step, 0.15 -> 0.79 ms on the per-corruption step, of which 0.20 are the dense-gradient step's."""
         optimizer_mode = kwargs.pop("optimizer_mode", "dense")
         if optimizer_mode not in ("dense", "lazy"):
             raise ValueError("optimizer_mode must be 'dense' (the reference's behaviour) or 'lazy' (touched rows only)")
@@ -177,6 +197,11 @@ class ScoringBasedEmbeddingModel:
                                       "their own corruption overrides and do not take a negative sampler; use replicated tables")
         if getattr(self._negatives, "shared", False):   # SharedNegatives: what it cannot be combined with
             self._negatives.check_model(self, optimizer_mode)
+        from .relation_prediction import RelationPrediction
+
+        self._relation_prediction = RelationPrediction.get(kwargs.pop("relation_prediction", None))
+        if self._relation_prediction is not None:   # what the term cannot be combined with
+            self._relation_prediction.check_model(self, optimizer_mode)
         self.optimizer = optimizers.get(optimizer)
         if optimizer_mode == "lazy":
             # DEVIATION from the reference (its optimizer is dense, optimizers.py:136-168): only rows that received a
@@ -336,8 +361,11 @@ class ScoringBasedEmbeddingModel:
 
         if type(loop) is StepLoop:
             loop.negatives = None if self._negatives is None else self._negatives.bind(self, eng, train)
+            loop.relation = None if self._relation_prediction is None else self._relation_prediction.bind(self, eng, train)
         elif self._negatives is not None:
             raise NotImplementedError("negatives: only the replicated step loop takes a negative sampler")
+        elif self._relation_prediction is not None:
+            raise NotImplementedError("relation_prediction: only the replicated step loop takes the relation objective")
         focus_dev = None
         if focus_w is not None:
             if focus_w.shape[0] != n:
@@ -405,6 +433,8 @@ class ScoringBasedEmbeddingModel:
         self._placement.publish()
         if hasattr(getattr(loop, "negatives", None), "stats"):
             self.negative_sampling_stats_ = loop.negatives.stats()   # {"redraws", "exhausted"} of this fit(): one read-back
+        if getattr(loop, "relation", None) is not None:
+            self.relation_prediction_stats_ = loop.relation.stats()   # {"masked", "unmaskable"} of this fit(): one read-back
         if hasattr(getattr(loop, "negatives", None), "relation_types"):
             self.relation_types_ = loop.negatives.relation_types     # TypedNegatives: the bound sets, evaluate_typed()'s default
         for cb in cbs:

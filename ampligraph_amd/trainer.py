@@ -134,6 +134,10 @@ class StepLoop:
         # (SharedDistanceNegatives: TransE, RotatE) both are engine.train_shared_dist_fwdbwd; with `.labelled` set (BoundKvsAll, with
         # loss_functions.BCELoss) engine.train_shared_labels_fwdbwd / train_shared_dist_labels_fwdbwd
         self.negatives = None
+        # compile(relation_prediction=...): None or an object with .step(batch) (latent_features/relation_prediction.py:
+        # BoundRelationPrediction), the relation-prediction term -- engine.train_relation_fwdbwd on the batch, between the backward call
+        # and the dense sweep, before the batch regulariser
+        self.relation = None
         engine.prepare_training(optimizer.name)
         if hasattr(optimizer, "bind"):
             optimizer.bind(engine)   # get_weights() / set_weights() of the wrapper read and write the engine's state tensors
@@ -195,6 +199,10 @@ class StepLoop:
                                           "optimizer_mode='lazy' and more than one rank were not built")
             lam = None if breg_e is not None else lam
             lam_r = None if breg_r is not None else lam_r
+        relation = self.relation
+        if relation is not None and (focus is not None or self.multi or self.deterministic or getattr(self.optimizer, "lazy", False)):
+            raise NotImplementedError("relation_prediction: its row-adds are unordered atomics (no deterministic mode); FocusE, "
+                                      "optimizer_mode='lazy' and more than one rank were not built")
         if getattr(self.negatives, "shared", False):
             # SharedNegatives: draw -> matrix-product forward / backward (kge_train_shared.hip) -> dense sweep.  Every other
             # configuration runs the code below.
@@ -225,6 +233,8 @@ class StepLoop:
                     s_filter, o_filter = mask(global_batch)
                     eng.train_shared_masked_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi, s_filter=s_filter, o_filter=o_filter,
                                                    identity=bool(getattr(sh, "identity", False)), stats=getattr(sh, "stats_dev", None))
+                if relation is not None:
+                    relation.step(global_batch)
                 if batch_reg:
                     eng.batch_reg_fwdbwd(global_batch, breg_e, breg_r)
             if self.kernel_hook is not None:
@@ -236,8 +246,9 @@ class StepLoop:
             return
         # owner-computes path (kge_train_tiled.hip) whenever the shape allows it: no global atomics, no dense
         # entity gradient; data-parallel runs take its gradient-only form and keep the dense sweep
-        # (a batch regulariser needs the dense entity gradient, which the owner-computes step never materialises)
-        tiled = (self.use_tiled or self.deterministic) and not batch_reg and hi > lo and eng.tiled_supported(hi - lo, self.eta)
+        # (a batch regulariser and the relation-prediction term need the dense entity gradient, which the owner-computes step never
+        # materialises)
+        tiled = (self.use_tiled or self.deterministic) and not batch_reg and relation is None and hi > lo and eng.tiled_supported(hi - lo, self.eta)
         if self.deterministic and hi > lo and not tiled:
             raise ValueError("deterministic mode needs the owner-computes train path (k <= 2048)")
         if self.kernel_hook is not None:
@@ -252,6 +263,8 @@ class StepLoop:
         elif hi > lo:
             eng.train_fwdbwd(global_batch[lo:hi], self.eta, self.loss_ffi, self.seed, rng_step,
                              row_offset=lo, b_global=bg, **neg)
+            if relation is not None:
+                relation.step(global_batch[lo:hi])
             if batch_reg:
                 eng.batch_reg_fwdbwd(global_batch[lo:hi], breg_e, breg_r)
         if self.kernel_hook is not None:
