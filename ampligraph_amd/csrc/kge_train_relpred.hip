@@ -20,8 +20,8 @@
 //                          the s_i and o_i gradient rows, c_pos' q_i goes to row p_i of the relation gradient: three atomic row-adds.
 //   relpred_loss_kernel  : one thread: *d_loss_sum += weight * (the step's loss sum, gathered in the workspace).
 // The mask and the loss are shared_mask_kernel (IDENTITY list; a zeroed side array makes the pair ranges the "object" ranges) and
-// shared_loss_kernel of kge_train_shared.hip, through launch_shared_mask / launch_shared_loss.  Rows are processed in chunks of at most
-// CHUNK_SCORES scores.
+// shared_loss_kernel of kge_train_shared.hip, through shared_loss_stage (kge_train_shared.h), the loss stage of the shared-list steps.
+// Rows, not groups, are processed in chunks of at most CHUNK_SCORES scores, so the step keeps its own chunk loop.
 #include "kge_train_shared.h"
 #include "../../include/amdkge_relation_objective.h"
 
@@ -197,10 +197,6 @@ __global__ __launch_bounds__(256) void relpred_gemm_kernel(RelGemmArgs a) {
 }
 
 // ---- the transpose of the pair-query map --------------------------------------------------------------------------------------------
-__device__ __forceinline__ void rp_add_nz(float* p, float v) {
-    if (v != 0.f) atomic_add_f32(p, v);
-}
-
 template <bool CPLX>
 __global__ __launch_bounds__(256) void relpred_chain_kernel(const float* __restrict__ ent, const float* __restrict__ rel, const int32_t* __restrict__ triples, int64_t B,
                                                             int ks, int k, float w, const float* __restrict__ Q, const float* __restrict__ dQ,
@@ -223,14 +219,14 @@ __global__ __launch_bounds__(256) void relpred_chain_kernel(const float* __restr
         if constexpr (CPLX) {
             const float s0 = S[u], s1 = S[ks + u], o0 = O[u], o1 = O[ks + u];
             const float t0 = d[u] + c * P[u], t1 = d[ks + u] + c * P[ks + u];   // dL/dq
-            rp_add_nz(g_s + u, t0 * o0 + t1 * o1); rp_add_nz(g_s + ks + u, t0 * o1 - t1 * o0);
-            rp_add_nz(g_o + u, t0 * s0 - t1 * s1); rp_add_nz(g_o + ks + u, t0 * s1 + t1 * s0);
-            rp_add_nz(g_p + u, c * q[u]); rp_add_nz(g_p + ks + u, c * q[ks + u]);
+            add_nz(g_s + u, t0 * o0 + t1 * o1); add_nz(g_s + ks + u, t0 * o1 - t1 * o0);
+            add_nz(g_o + u, t0 * s0 - t1 * s1); add_nz(g_o + ks + u, t0 * s1 + t1 * s0);
+            add_nz(g_p + u, c * q[u]); add_nz(g_p + ks + u, c * q[ks + u]);
         } else {
             const float t = d[u] + c * P[u];
-            rp_add_nz(g_s + u, t * O[u]);
-            rp_add_nz(g_o + u, t * S[u]);
-            rp_add_nz(g_p + u, c * q[u]);
+            add_nz(g_s + u, t * O[u]);
+            add_nz(g_o + u, t * S[u]);
+            add_nz(g_p + u, c * q[u]);
         }
     }
 }
@@ -243,11 +239,6 @@ __global__ void relpred_loss_kernel(const double* __restrict__ step_sum, float w
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static bool relpred_model_ok(const amdkge_model* m) {
-    return m->scoring_type == AMDKGE_DISTMULT || m->scoring_type == AMDKGE_COMPLEX || m->scoring_type == AMDKGE_HOLE;
-}
-static int64_t rp_align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 // the workspace of a step: the step's loss sum (a double), Q, dQ [B, K], the positives' raw scores and coefficients [B], the zeroed
 // side array of the mask [B], the score buffer of one chunk [rows, R]
 struct RelPlan {
@@ -261,12 +252,12 @@ static bool relpred_plan(const amdkge_model* m, int64_t B, RelPlan& p) {
     if (p.rpc > B) p.rpc = B;
     int64_t off = 0;
     p.off_sum = off; off += 256;
-    p.off_q = off; off += rp_align256(B * K * 4);
-    p.off_dq = off; off += rp_align256(B * K * 4);
-    p.off_pos = off; off += rp_align256(B * 4);
-    p.off_cpos = off; off += rp_align256(B * 4);
-    p.off_side = off; off += rp_align256(B * 4);
-    p.off_s = off; off += rp_align256(p.rpc * R * 4);
+    p.off_q = off; off += align256(B * K * 4);
+    p.off_dq = off; off += align256(B * K * 4);
+    p.off_pos = off; off += align256(B * 4);
+    p.off_cpos = off; off += align256(B * 4);
+    p.off_side = off; off += align256(B * 4);
+    p.off_s = off; off += align256(p.rpc * R * 4);
     p.total = off;
     return true;
 }
@@ -294,6 +285,10 @@ static int run_relpred(const amdkge_model* m, const amdkge_loss* loss, float w, 
     if (int rc = check_launch("relpred_query")) return rc;
     RelGemmArgs a{};
     a.ent = d_ent; a.rel = d_rel; a.triples = d_triples; a.Q = Q; a.S = S; a.dQ = dQ; a.g_rel = g_rel; a.R = R; a.K = K; a.ks = ks; a.k = k; a.cplx = CPLX ? 1 : 0; a.w = w;
+    // the loss stage of a chunk: the list is the relation table (G = 1, M = R, no ids), the zeroed side array, the step's own loss sum
+    SharedStep ls{};
+    ls.S = S; ls.pos_raw = pos_raw; ls.cpos = cpos; ls.B = B; ls.G = 1; ls.M = R; ls.side = side; ls.st = st; ls.scale = scale; ls.loss = loss; ls.mask = mask;
+    ls.loss_sum = step_sum; ls.pos_scores = d_pos_scores; ls.neg_scores = d_rel_scores;
     const int64_t tr = (R + RT - 1) / RT, tk = (K + RT - 1) / RT;
     for (int64_t row0 = 0; row0 < B; row0 += p.rpc) {
         const int64_t rows = (B - row0) < p.rpc ? (B - row0) : p.rpc;
@@ -304,13 +299,7 @@ static int run_relpred(const amdkge_model* m, const amdkge_loss* loss, float w, 
         a.tiles_n = (int)tr; a.per_slice = (int)nb_fwd;
         hipLaunchKernelGGL(relpred_gemm_kernel<RP_FWD>, dim3((unsigned)nb_fwd), dim3(256), 0, st, a);
         if (int rc = check_launch("relpred_gemm_fwd")) return rc;
-        if (mask) {   // known relations -> -inf, on the chunk's own rows
-            SharedMaskArgs ma = *mask;
-            ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = 1; ma.M = R; ma.ids = nullptr; ma.side = side;
-            ma.fill = scale < 0.f ? INFINITY : -INFINITY;
-            if (int rc = launch_shared_mask(ma, st)) return rc;
-        }
-        if (int rc = launch_shared_loss(S, pos_raw, cpos, row0, rows, B, R, *loss, scale, step_sum, d_pos_scores, d_rel_scores, st)) return rc;
+        if (int rc = shared_loss_stage(ls, row0, rows)) return rc;   // (the mask: known relations -> -inf)
         a.tiles_n = (int)tk; a.per_slice = (int)nb_dq;
         hipLaunchKernelGGL(relpred_gemm_kernel<RP_DQ>, dim3((unsigned)nb_dq), dim3(256), 0, st, a);
         if (int rc = check_launch("relpred_gemm_dq")) return rc;
@@ -329,7 +318,7 @@ static int run_relpred(const amdkge_model* m, const amdkge_loss* loss, float w, 
 using namespace kge;
 
 extern "C" int64_t amdkge_train_relation_workspace_bytes(const amdkge_model* m, int64_t B) {
-    if (validate_model(m) || !relpred_model_ok(m)) return 0;
+    if (validate_model(m) || !shared_model_ok(m)) return 0;
     RelPlan p;
     return relpred_plan(m, B, p) ? p.total : 0;
 }
@@ -339,7 +328,7 @@ extern "C" int amdkge_train_relation_fwdbwd(const amdkge_model* m, const amdkge_
                                             float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores, float* d_rel_scores, void* d_work,
                                             int64_t* d_stats, void* stream) {
     if (int rc = validate_model(m)) return rc;
-    if (!relpred_model_ok(m)) return set_error(AMDKGE_EUNSUPPORTED, "train_relation: the score of TransE and RotatE is a distance in the relation row, not a contraction with it: only DistMult, ComplEx and HolE take the relation objective");
+    if (!shared_model_ok(m)) return set_error(AMDKGE_EUNSUPPORTED, "train_relation: the score of TransE and RotatE is a distance in the relation row, not a contraction with it: only DistMult, ComplEx and HolE take the relation objective");
     if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_relation: unknown loss kind");
     if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "train_relation: FocusE is not offered with the relation objective");
     if (!(weight >= 0.f) || __builtin_isinf(weight)) return set_error(AMDKGE_EINVAL, "train_relation: weight must be finite and >= 0");

@@ -26,6 +26,9 @@
 //   shared_label_loss_kernel : (include/amdkge_shared_labels.h, kge_train_shared_labels.hip; in place of the mask and the loss) KvsAll:
 //                         labels from the known ranges and binary cross-entropy in one pass over the buffer.
 // Groups are processed in chunks of at most CHUNK_SCORES scores, so the score buffer is bounded whatever B * M is.
+// The host side of a step is shared_step (kge_train_shared.h), defined here for this unit's family and for the distance tiles of
+// kge_train_shared_dist.hip alike: the checks, the plan and the chunk loop once, each family's launches in its own unit
+// (product_launch here).  The loss stage of a chunk is shared_loss_stage, also the relation objective's (kge_train_relpred.hip).
 #include "kge_train_shared.h"
 #include "kge_loss.h"
 #include <string>
@@ -340,10 +343,6 @@ __global__ __launch_bounds__(256) void shared_mask_kernel(SharedMaskArgs a) {
 }
 
 // ---- the transpose of the query map -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void add_nz(float* p, float v) {
-    if (v != 0.f) atomic_add_f32(p, v);
-}
-
 template <bool CPLX>
 __global__ __launch_bounds__(256) void shared_chain_kernel(const float* __restrict__ ent, const float* __restrict__ rel, const int32_t* __restrict__ triples,
                                                            const int32_t* __restrict__ side, int64_t B, int ks, int k, const float* __restrict__ Q, const float* __restrict__ dQ,
@@ -392,10 +391,6 @@ __global__ __launch_bounds__(256) void shared_chain_kernel(const float* __restri
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static bool shared_model_ok(const amdkge_model* m) {
-    return m->scoring_type == AMDKGE_DISTMULT || m->scoring_type == AMDKGE_COMPLEX || m->scoring_type == AMDKGE_HOLE;
-}
-static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 // groups per chunk of the score buffer
 static int64_t shared_chunk_groups(int64_t n_groups, int64_t G, int64_t M) {
     int64_t gpc = CHUNK_SCORES / (G * M);
@@ -436,58 +431,94 @@ int launch_shared_loss(float* S, const float* pos_raw, float* cpos, int64_t row0
     return check_launch("shared_loss");
 }
 
-template <bool CPLX>
-static int run_shared(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int M,
-                      const int32_t* d_ids, const int32_t* d_side, float* g_ent, float* g_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores,
-                      char* work, const SharedPlan& p, const SharedMaskArgs* mask, hipStream_t st, const SharedLabelArgs* labels = nullptr) {
-    const int ks = stored_k(m), K = row_floats(m), k = m->k;
+int shared_loss_stage(const SharedStep& s, int64_t row0, int64_t rows) {
+    if (s.labels) {   // KvsAll (include/amdkge_shared_labels.h): labels + BCE in one pass, in place of mask + loss
+        SharedLabelArgs la = *s.labels;
+        la.S = s.S; la.row0 = row0; la.rows = rows; la.G = s.G; la.B = s.B; la.M = s.M; la.ids = s.ids; la.side = s.side; la.scale = s.scale;
+        la.pos_raw = s.pos_raw; la.cpos = s.cpos; la.pos_scores = s.pos_scores; la.neg_scores = s.neg_scores; la.loss_sum = s.loss_sum;
+        return launch_shared_label_loss(la, s.st);
+    }
+    if (s.mask) {   // known statements -> a score of -inf, on the chunk's own rows
+        SharedMaskArgs ma = *s.mask;
+        ma.S = s.S; ma.row0 = row0; ma.rows = rows; ma.G = s.G; ma.M = s.M; ma.ids = s.ids; ma.side = s.side;
+        ma.fill = s.scale < 0.f ? INFINITY : -INFINITY;
+        if (int rc = launch_shared_mask(ma, s.st)) return rc;
+    }
+    return launch_shared_loss(s.S, s.pos_raw, s.cpos, row0, rows, s.B, s.M, *s.loss, s.scale, s.loss_sum, s.pos_scores, s.neg_scores, s.st);
+}
+
+// ---- the driver ---------------------------------------------------------------------------------------------------------------------
+int64_t shared_step_workspace_bytes(const SharedFamily& f, const amdkge_model* m, int64_t B, int64_t G, int32_t M) {
+    if (validate_model(m) || !f.model_ok(m)) return 0;
+    SharedPlan p;
+    return shared_plan(m, B, G, M, p) ? p.total : 0;
+}
+
+int shared_step(const SharedFamily& f, const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G,
+                int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores,
+                float* d_neg_scores, void* d_work, const SharedMaskArgs* mask, const SharedLabelArgs* labels, void* stream) {
+    const auto refuse = [&f](int code, const char* what) { return set_error(code, (std::string(f.who) + ": " + what).c_str()); };
+    if (int rc = validate_model(m)) return rc;
+    if (!f.model_ok(m)) return refuse(AMDKGE_EUNSUPPORTED, f.wrong_model);
+    if (!labels) {
+        if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return refuse(AMDKGE_EINVAL, "unknown loss kind");
+        if (loss->focus_nonlinearity) return refuse(AMDKGE_EUNSUPPORTED, "FocusE is not offered with shared negatives");
+    }
+    if (B < 0 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return refuse(AMDKGE_EINVAL, "bad sizes (B >= 0, G >= 1, 1 <= M < 2^24)");
+    if (!d_ent || !d_rel || !d_grad_ent || !d_grad_rel || !d_loss_sum) return refuse(AMDKGE_EINVAL, "NULL table / gradient / loss pointer");
+    if (B == 0) return AMDKGE_OK;
+    if (!d_triples || !d_neg_ids || !d_side || !d_work) return refuse(AMDKGE_EINVAL, "NULL triples / ids / sides / workspace");
+    if (G > B) G = B;
+    SharedPlan p;
+    if (!shared_plan(m, B, G, M, p)) return refuse(AMDKGE_EINVAL, "bad sizes");
+    char* work = static_cast<char*>(d_work);
+    const auto at = [work](int64_t off) { return reinterpret_cast<float*>(work + off); };
     const ModelConst mc = model_const(m);
-    float* Q = reinterpret_cast<float*>(work + p.off_q);
-    float* dQ = reinterpret_cast<float*>(work + p.off_dq);
-    float* pos_raw = reinterpret_cast<float*>(work + p.off_pos);
-    float* cpos = reinterpret_cast<float*>(work + p.off_cpos);
-    float* S = reinterpret_cast<float*>(work + p.off_s);
+    const SharedStep s{m, d_ent, d_rel, d_triples, d_neg_ids, d_side, B, G, M, d_grad_ent, d_grad_rel, at(p.off_q), at(p.off_dq), at(p.off_pos), at(p.off_cpos), at(p.off_s),
+                       (hipStream_t)stream, mc.score_sign * mc.score_scale, loss, mask, labels, d_loss_sum, d_pos_scores, d_neg_scores};
     const int64_t wave_blocks = (B + 3) / 4;
-    if (wave_blocks > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: too many positives for one launch; split them");
-    hipLaunchKernelGGL(shared_query_kernel<CPLX>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, Q, pos_raw);
-    if (int rc = check_launch("shared_query")) return rc;
-    SharedGemmArgs a{};
-    a.ent = d_ent; a.rel = d_rel; a.triples = d_triples; a.side = d_side; a.cplx = CPLX ? 1 : 0; a.ids = d_ids; a.Q = Q; a.S = S; a.dQ = dQ; a.g_ent = g_ent; a.B = B; a.G = G; a.M = M; a.K = K; a.ks = ks; a.k = k;
-    const int tg = (int)((G + GT - 1) / GT), tm = (M + GT - 1) / GT, tk = (K + GT - 1) / GT;
+    if (wave_blocks > 0x7FFFFFFFll) return refuse(AMDKGE_EUNSUPPORTED, "too many positives for one launch; split them");
+    if (int rc = f.launch(s, SHARED_QUERY, (unsigned)wave_blocks, 0, 0, 0)) return rc;
+    const int tg = (int)((G + SHARED_TILE - 1) / SHARED_TILE), tm = (M + SHARED_TILE - 1) / SHARED_TILE, tk = f.unit_tiles(m);
     for (int64_t g0 = 0; g0 < p.n_groups; g0 += p.gpc) {
         const int64_t ng = (p.n_groups - g0) < p.gpc ? (p.n_groups - g0) : p.gpc;
         const int64_t row0 = g0 * G;
         const int64_t rows = ((g0 + ng) * G < B ? (g0 + ng) * G : B) - row0;
-        a.g0 = g0;
         const int64_t nb_fwd = ng * tg * tm, nb_dq = ng * tg * tk, nb_de = ng * tm * tk;
-        if (nb_fwd > 0x7FFFFFFFll || nb_dq > 0x7FFFFFFFll || nb_de > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: too many tiles for one launch");
-        a.tiles_m = tg; a.tiles_n = tm;
-        hipLaunchKernelGGL(shared_gemm_kernel<GEMM_FWD>, dim3((unsigned)nb_fwd), dim3(256), 0, st, a);
-        if (int rc = check_launch("shared_gemm_fwd")) return rc;
-        if (labels) {   // KvsAll (include/amdkge_shared_labels.h): labels + BCE in one pass, in place of mask + loss
-            SharedLabelArgs la = *labels;
-            la.S = S; la.row0 = row0; la.rows = rows; la.G = G; la.B = B; la.M = M; la.ids = d_ids; la.side = d_side; la.scale = mc.score_sign * mc.score_scale;
-            la.pos_raw = pos_raw; la.cpos = cpos; la.pos_scores = d_pos_scores; la.neg_scores = d_neg_scores; la.loss_sum = d_loss_sum;
-            if (int rc = launch_shared_label_loss(la, st)) return rc;
-        } else {
-            if (mask) {   // known statements -> -inf, on the chunk's own rows
-                SharedMaskArgs ma = *mask;
-                ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = G; ma.M = M; ma.ids = d_ids; ma.side = d_side;
-                ma.fill = mc.score_sign * mc.score_scale < 0.f ? INFINITY : -INFINITY;
-                if (int rc = launch_shared_mask(ma, st)) return rc;
-            }
-            if (int rc = launch_shared_loss(S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum, d_pos_scores, d_neg_scores, st)) return rc;
-        }
-        a.tiles_m = tg; a.tiles_n = tk;
-        hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DQ>, dim3((unsigned)nb_dq), dim3(256), 0, st, a);
-        if (int rc = check_launch("shared_gemm_dq")) return rc;
-        a.tiles_m = tm; a.tiles_n = tk;
-        hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DE>, dim3((unsigned)nb_de), dim3(256), 0, st, a);
-        if (int rc = check_launch("shared_gemm_de")) return rc;
+        if (nb_fwd > 0x7FFFFFFFll || nb_dq > 0x7FFFFFFFll || nb_de > 0x7FFFFFFFll) return refuse(AMDKGE_EUNSUPPORTED, "too many tiles for one launch");
+        if (int rc = f.launch(s, SHARED_FWD, (unsigned)nb_fwd, g0, tg, tm)) return rc;
+        if (int rc = shared_loss_stage(s, row0, rows)) return rc;
+        if (int rc = f.launch(s, SHARED_DQ, (unsigned)nb_dq, g0, tg, tk)) return rc;
+        if (int rc = f.launch(s, SHARED_DE, (unsigned)nb_de, g0, tm, tk)) return rc;
     }
-    hipLaunchKernelGGL(shared_chain_kernel<CPLX>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, k, Q, dQ, cpos, g_ent, g_rel);
-    return check_launch("shared_chain");
+    return f.launch(s, SHARED_CHAIN, (unsigned)wave_blocks, 0, 0, 0);
 }
+
+// ---- the product family: its kernels' launches ----------------------------------------------------------------------------------------
+static_assert(GT == SHARED_TILE, "the driver counts the tiles");
+template <bool CPLX>
+static int product_launch(const SharedStep& s, SharedStage stage, unsigned blocks, int64_t g0, int tiles_m, int tiles_n) {
+    const int ks = stored_k(s.m), k = s.m->k;
+    SharedGemmArgs a{};
+    a.ent = s.ent; a.rel = s.rel; a.triples = s.triples; a.side = s.side; a.cplx = CPLX ? 1 : 0; a.ids = s.ids; a.Q = s.Q; a.S = s.S; a.dQ = s.dQ; a.g_ent = s.g_ent; a.B = s.B; a.G = s.G; a.M = s.M; a.K = row_floats(s.m); a.ks = ks; a.k = k;
+    a.g0 = g0; a.tiles_m = tiles_m; a.tiles_n = tiles_n;
+    static const char* const NAMES[] = {"shared_query", "shared_gemm_fwd", "shared_gemm_dq", "shared_gemm_de", "shared_chain"};   // (by SharedStage)
+    switch (stage) {
+    case SHARED_QUERY: hipLaunchKernelGGL(shared_query_kernel<CPLX>, dim3(blocks), dim3(256), 0, s.st, s.ent, s.rel, s.triples, s.side, s.B, ks, s.Q, s.pos_raw); break;
+    case SHARED_FWD: hipLaunchKernelGGL(shared_gemm_kernel<GEMM_FWD>, dim3(blocks), dim3(256), 0, s.st, a); break;
+    case SHARED_DQ: hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DQ>, dim3(blocks), dim3(256), 0, s.st, a); break;
+    case SHARED_DE: hipLaunchKernelGGL(shared_gemm_kernel<GEMM_DE>, dim3(blocks), dim3(256), 0, s.st, a); break;
+    case SHARED_CHAIN: hipLaunchKernelGGL(shared_chain_kernel<CPLX>, dim3(blocks), dim3(256), 0, s.st, s.ent, s.rel, s.triples, s.side, s.B, ks, k, s.Q, s.dQ, s.cpos, s.g_ent, s.g_rel); break;
+    }
+    return check_launch(NAMES[stage]);
+}
+static const SharedFamily PRODUCTS = {
+    "train_shared", shared_model_ok, "TransE and RotatE score a distance, not a contraction: only DistMult, ComplEx and HolE share negatives",
+    [](const amdkge_model* m) { return (row_floats(m) + GT - 1) / GT; },
+    [](const SharedStep& s, SharedStage stage, unsigned blocks, int64_t g0, int tiles_m, int tiles_n) {
+        return s.m->scoring_type != AMDKGE_DISTMULT ? product_launch<true>(s, stage, blocks, g0, tiles_m, tiles_n)   // ComplEx, and HolE on its instantiation (the 2/k scale travels in ModelConst)
+                                                    : product_launch<false>(s, stage, blocks, g0, tiles_m, tiles_n);
+    }};
 
 }  // namespace kge
 
@@ -517,39 +548,15 @@ extern "C" int amdkge_sample_shared(const int32_t* d_triples, int64_t B, int64_t
 }
 
 extern "C" int64_t amdkge_train_shared_workspace_bytes(const amdkge_model* m, int64_t B, int64_t G, int32_t M) {
-    if (validate_model(m) || !shared_model_ok(m)) return 0;
-    SharedPlan p;
-    return shared_plan(m, B, G, M, p) ? p.total : 0;
+    return shared_step_workspace_bytes(PRODUCTS, m, B, G, M);
 }
 
-// the step entry points: mask == nullptr is the unmasked step; labels != nullptr is the labelled step (loss is not read)
-static int shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int32_t M,
-                         const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores,
-                         float* d_neg_scores, void* d_work, const SharedMaskArgs* mask, void* stream, const SharedLabelArgs* labels = nullptr) {
-    if (int rc = validate_model(m)) return rc;
-    if (!shared_model_ok(m)) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: TransE and RotatE score a distance, not a contraction: only DistMult, ComplEx and HolE share negatives");
-    if (!labels) {
-        if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_shared: unknown loss kind");
-        if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "train_shared: FocusE is not offered with shared negatives");
-    }
-    if (B < 0 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return set_error(AMDKGE_EINVAL, "train_shared: bad sizes (B >= 0, G >= 1, 1 <= M < 2^24)");
-    if (!d_ent || !d_rel || !d_grad_ent || !d_grad_rel || !d_loss_sum) return set_error(AMDKGE_EINVAL, "train_shared: NULL table / gradient / loss pointer");
-    if (B == 0) return AMDKGE_OK;
-    if (!d_triples || !d_neg_ids || !d_side || !d_work) return set_error(AMDKGE_EINVAL, "train_shared: NULL triples / ids / sides / workspace");
-    if (G > B) G = B;
-    SharedPlan p;
-    if (!shared_plan(m, B, G, M, p)) return set_error(AMDKGE_EINVAL, "train_shared: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    char* work = static_cast<char*>(d_work);
-    if (m->scoring_type != AMDKGE_DISTMULT)   // ComplEx, and HolE on its instantiation (the 2/k scale travels in ModelConst)
-        return run_shared<true>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st, labels);
-    return run_shared<false>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st, labels);
-}
-
+// the three step entry points are shared_step on the product family: no mask (the plain step), the mask, or the labels
 extern "C" int amdkge_train_shared_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
                                           int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum,
                                           float* d_pos_scores, float* d_neg_scores, void* d_work, void* stream) {
-    return shared_fwdbwd(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work, nullptr, stream);
+    return shared_step(PRODUCTS, m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work, nullptr,
+                       nullptr, stream);
 }
 
 // (declared in kge_train_shared.h)
@@ -589,8 +596,8 @@ extern "C" int amdkge_train_shared_masked_fwdbwd(const amdkge_model* m, const am
     SharedMaskArgs a;
     bool masked;
     if (int rc = shared_mask_args("train_shared_masked", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, d_stats, false, a, masked)) return rc;
-    return shared_fwdbwd(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
-                         masked ? &a : nullptr, stream);
+    return shared_step(PRODUCTS, m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
+                       masked ? &a : nullptr, nullptr, stream);
 }
 
 // (include/amdkge_shared_labels.h)
@@ -602,6 +609,6 @@ extern "C" int amdkge_train_shared_labels_fwdbwd(const amdkge_model* m, float la
     SharedLabelArgs la;
     if (int rc = shared_label_args("train_shared_labels", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, label_smoothing, reduction_mean, d_w_s,
                                    d_w_o, d_stats, la)) return rc;
-    return shared_fwdbwd(m, nullptr, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work, nullptr,
-                         stream, &la);
+    return shared_step(PRODUCTS, m, nullptr, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work, nullptr,
+                       &la, stream);
 }

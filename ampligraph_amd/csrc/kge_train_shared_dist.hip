@@ -20,8 +20,10 @@
 //                              kept rows get the transpose of the query map (RotatE: the phase gradient / phase_div), the replaced
 //                              row's original gets -c_pos n_i.
 // The score buffer holds the plain distance sums and the loss runs with scale = -1, so shared_mask_kernel (fill = +inf) and
-// shared_loss_kernel of kge_train_shared.hip run unchanged on it, through the launch functions of kge_train_shared.h; the
+// shared_loss_kernel of kge_train_shared.hip run unchanged on it, through shared_loss_stage of kge_train_shared.h; the
 // coefficients they leave are dL/dD = -dL/dscore.  Only the model's k live units are visited: a padding unit of RotatE has modulus 0.
+// The host side of a step is shared_step (kge_train_shared.h, defined in kge_train_shared.hip); this unit gives it the DISTANCES family:
+// the prefix and model test of its messages, ceil(k / 32) tiles along the units, and dist_launch for the kernels above.
 #include "kge_train_shared.h"
 #include "../../include/amdkge_shared_dist.h"
 
@@ -311,10 +313,6 @@ __global__ __launch_bounds__(256) void dist_tile_kernel(DistTileArgs a) {
 }
 
 // ---- the transpose of the query map -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dist_add_nz(float* p, float v) {
-    if (v != 0.f) atomic_add_f32(p, v);
-}
-
 template <int MODEL>
 __global__ __launch_bounds__(256) void dist_chain_kernel(const float* __restrict__ ent, const float* __restrict__ rel, const int32_t* __restrict__ triples,
                                                          const int32_t* __restrict__ side, int64_t B, int ks, int k, ModelConst mc, const float* __restrict__ Q,
@@ -338,9 +336,9 @@ __global__ __launch_bounds__(256) void dist_chain_kernel(const float* __restrict
         if constexpr (MODEL == AMDKGE_TRANSE) {
             const float n = sign_times(q[u] - own[u], c);   // c sigma
             const float t = d[u] + n;                       // dL/dq
-            dist_add_nz(g_own + u, -n);
-            dist_add_nz(g_kept + u, t);
-            dist_add_nz(g_p + u, subj ? -t : t);            // q = o - p : s + p
+            add_nz(g_own + u, -n);
+            add_nz(g_kept + u, t);
+            add_nz(g_p + u, subj ? -t : t);            // q = o - p : s + p
         } else {
             const float q0 = q[u], q1 = q[ks + u];
             const float z0 = q0 - own[u], z1 = q1 - own[ks + u];
@@ -357,9 +355,9 @@ __global__ __launch_bounds__(256) void dist_chain_kernel(const float* __restrict
                 k0 = t0 * r[0] + t1 * r[1]; k1 = t1 * r[0] - t0 * r[1];
                 dphi = t1 * q0 - t0 * q1;
             }
-            dist_add_nz(g_own + u, -n0); dist_add_nz(g_own + ks + u, -n1);
-            dist_add_nz(g_kept + u, k0); dist_add_nz(g_kept + ks + u, k1);
-            dist_add_nz(g_p + u, dphi / mc.phase_div);
+            add_nz(g_own + u, -n0); add_nz(g_own + ks + u, -n1);
+            add_nz(g_kept + u, k0); add_nz(g_kept + ks + u, k1);
+            add_nz(g_p + u, dphi / mc.phase_div);
         }
     }
 }
@@ -367,92 +365,42 @@ __global__ __launch_bounds__(256) void dist_chain_kernel(const float* __restrict
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 static bool dist_model_ok(const amdkge_model* m) { return m->scoring_type == AMDKGE_TRANSE || m->scoring_type == AMDKGE_ROTATE; }
 
+// the family's launches for shared_step (kge_train_shared.h)
+static_assert(DT == SHARED_TILE, "the driver counts the tiles");
 template <int MODEL>
-static int run_shared_dist(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int M,
-                           const int32_t* d_ids, const int32_t* d_side, float* g_ent, float* g_rel, double* d_loss_sum, float* d_pos_scores, float* d_neg_scores,
-                           char* work, const SharedPlan& p, const SharedMaskArgs* mask, hipStream_t st, const SharedLabelArgs* labels = nullptr) {
-    const int ks = stored_k(m), K = row_floats(m), k = m->k;
-    const ModelConst mc = model_const(m);
-    float* Q = reinterpret_cast<float*>(work + p.off_q);
-    float* dQ = reinterpret_cast<float*>(work + p.off_dq);
-    float* pos_raw = reinterpret_cast<float*>(work + p.off_pos);
-    float* cpos = reinterpret_cast<float*>(work + p.off_cpos);
-    float* S = reinterpret_cast<float*>(work + p.off_s);
-    const int64_t wave_blocks = (B + 3) / 4;
-    if (wave_blocks > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "train_shared_dist: too many positives for one launch; split them");
-    hipLaunchKernelGGL(dist_query_kernel<MODEL>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, k, mc, Q, pos_raw);
-    if (int rc = check_launch("dist_query")) return rc;
+static int dist_launch(const SharedStep& s, SharedStage stage, unsigned blocks, int64_t g0, int tiles_m, int tiles_n) {
+    const int ks = stored_k(s.m), k = s.m->k;
+    const ModelConst mc = model_const(s.m);
     DistTileArgs a{};
-    a.ent = d_ent; a.ids = d_ids; a.Q = Q; a.S = S; a.dQ = dQ; a.g_ent = g_ent; a.B = B; a.G = G; a.M = M; a.K = K; a.ks = ks; a.k = k;
-    const int tg = (int)((G + DT - 1) / DT), tm = (M + DT - 1) / DT, tk = (k + DKC - 1) / DKC;
-    for (int64_t g0 = 0; g0 < p.n_groups; g0 += p.gpc) {
-        const int64_t ng = (p.n_groups - g0) < p.gpc ? (p.n_groups - g0) : p.gpc;
-        const int64_t row0 = g0 * G;
-        const int64_t rows = ((g0 + ng) * G < B ? (g0 + ng) * G : B) - row0;
-        a.g0 = g0;
-        const int64_t nb_fwd = ng * tg * tm, nb_dq = ng * tg * tk, nb_de = ng * tm * tk;
-        if (nb_fwd > 0x7FFFFFFFll || nb_dq > 0x7FFFFFFFll || nb_de > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "train_shared_dist: too many tiles for one launch");
-        a.tiles_m = tg; a.tiles_n = tm;
-        hipLaunchKernelGGL((dist_tile_kernel<MODEL, DIST_FWD>), dim3((unsigned)nb_fwd), dim3(256), 0, st, a);
-        if (int rc = check_launch("dist_tile_fwd")) return rc;
-        if (labels) {   // KvsAll (include/amdkge_shared_labels.h): labels + BCE in one pass, in place of mask + loss
-            SharedLabelArgs la = *labels;
-            la.S = S; la.row0 = row0; la.rows = rows; la.G = G; la.B = B; la.M = M; la.ids = d_ids; la.side = d_side; la.scale = mc.score_sign * mc.score_scale;
-            la.pos_raw = pos_raw; la.cpos = cpos; la.pos_scores = d_pos_scores; la.neg_scores = d_neg_scores; la.loss_sum = d_loss_sum;
-            if (int rc = launch_shared_label_loss(la, st)) return rc;
-        } else {
-            if (mask) {   // known statements -> score -inf: the buffer holds distances, so +inf
-                SharedMaskArgs ma = *mask;
-                ma.S = S; ma.row0 = row0; ma.rows = rows; ma.G = G; ma.M = M; ma.ids = d_ids; ma.side = d_side;
-                ma.fill = INFINITY;
-                if (int rc = launch_shared_mask(ma, st)) return rc;
-            }
-            if (int rc = launch_shared_loss(S, pos_raw, cpos, row0, rows, B, M, *loss, mc.score_sign * mc.score_scale, d_loss_sum, d_pos_scores, d_neg_scores, st)) return rc;
-        }
-        a.tiles_m = tg; a.tiles_n = tk;
-        hipLaunchKernelGGL((dist_tile_kernel<MODEL, DIST_DQ>), dim3((unsigned)nb_dq), dim3(256), 0, st, a);
-        if (int rc = check_launch("dist_tile_dq")) return rc;
-        a.tiles_m = tm; a.tiles_n = tk;
-        hipLaunchKernelGGL((dist_tile_kernel<MODEL, DIST_DE>), dim3((unsigned)nb_de), dim3(256), 0, st, a);
-        if (int rc = check_launch("dist_tile_de")) return rc;
+    a.ent = s.ent; a.ids = s.ids; a.Q = s.Q; a.S = s.S; a.dQ = s.dQ; a.g_ent = s.g_ent; a.B = s.B; a.G = s.G; a.M = s.M; a.K = row_floats(s.m); a.ks = ks; a.k = k;
+    a.g0 = g0; a.tiles_m = tiles_m; a.tiles_n = tiles_n;
+    static const char* const NAMES[] = {"dist_query", "dist_tile_fwd", "dist_tile_dq", "dist_tile_de", "dist_chain"};   // (by SharedStage)
+    switch (stage) {
+    case SHARED_QUERY: hipLaunchKernelGGL(dist_query_kernel<MODEL>, dim3(blocks), dim3(256), 0, s.st, s.ent, s.rel, s.triples, s.side, s.B, ks, k, mc, s.Q, s.pos_raw); break;
+    case SHARED_FWD: hipLaunchKernelGGL((dist_tile_kernel<MODEL, DIST_FWD>), dim3(blocks), dim3(256), 0, s.st, a); break;
+    case SHARED_DQ: hipLaunchKernelGGL((dist_tile_kernel<MODEL, DIST_DQ>), dim3(blocks), dim3(256), 0, s.st, a); break;
+    case SHARED_DE: hipLaunchKernelGGL((dist_tile_kernel<MODEL, DIST_DE>), dim3(blocks), dim3(256), 0, s.st, a); break;
+    case SHARED_CHAIN: hipLaunchKernelGGL(dist_chain_kernel<MODEL>, dim3(blocks), dim3(256), 0, s.st, s.ent, s.rel, s.triples, s.side, s.B, ks, k, mc, s.Q, s.dQ, s.cpos, s.g_ent, s.g_rel); break;
     }
-    hipLaunchKernelGGL(dist_chain_kernel<MODEL>, dim3((unsigned)wave_blocks), dim3(256), 0, st, d_ent, d_rel, d_triples, d_side, B, ks, k, mc, Q, dQ, cpos, g_ent, g_rel);
-    return check_launch("dist_chain");
+    return check_launch(NAMES[stage]);
 }
+static const SharedFamily DISTANCES = {
+    "train_shared_dist", dist_model_ok, "DistMult, ComplEx and HolE score a contraction, not a distance: use amdkge_train_shared_fwdbwd",
+    [](const amdkge_model* m) { return (m->k + DKC - 1) / DKC; },
+    [](const SharedStep& s, SharedStage stage, unsigned blocks, int64_t g0, int tiles_m, int tiles_n) {
+        return s.m->scoring_type == AMDKGE_ROTATE ? dist_launch<AMDKGE_ROTATE>(s, stage, blocks, g0, tiles_m, tiles_n)
+                                                  : dist_launch<AMDKGE_TRANSE>(s, stage, blocks, g0, tiles_m, tiles_n);
+    }};
 
 }  // namespace kge
 
 using namespace kge;
 
 extern "C" int64_t amdkge_train_shared_dist_workspace_bytes(const amdkge_model* m, int64_t B, int64_t G, int32_t M) {
-    if (validate_model(m) || !dist_model_ok(m)) return 0;
-    SharedPlan p;
-    return shared_plan(m, B, G, M, p) ? p.total : 0;
+    return shared_step_workspace_bytes(DISTANCES, m, B, G, M);
 }
 
-// both step entry points: mask == nullptr is the unmasked step; labels != nullptr is the labelled step (loss is not read)
-static int shared_dist_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B, int64_t G, int32_t M,
-                              const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel, double* d_loss_sum, float* d_pos_scores,
-                              float* d_neg_scores, void* d_work, const SharedMaskArgs* mask, const SharedLabelArgs* labels, void* stream) {
-    if (int rc = validate_model(m)) return rc;
-    if (!dist_model_ok(m)) return set_error(AMDKGE_EUNSUPPORTED, "train_shared_dist: DistMult, ComplEx and HolE score a contraction, not a distance: use amdkge_train_shared_fwdbwd");
-    if (!labels) {
-        if (!loss || loss->kind < 0 || loss->kind > AMDKGE_LOSS_MULTICLASS_NLL) return set_error(AMDKGE_EINVAL, "train_shared_dist: unknown loss kind");
-        if (loss->focus_nonlinearity) return set_error(AMDKGE_EUNSUPPORTED, "train_shared_dist: FocusE is not offered with shared negatives");
-    }
-    if (B < 0 || G < 1 || M < 1 || M > AMDKGE_SHARED_MAX_NEGS) return set_error(AMDKGE_EINVAL, "train_shared_dist: bad sizes (B >= 0, G >= 1, 1 <= M < 2^24)");
-    if (!d_ent || !d_rel || !d_grad_ent || !d_grad_rel || !d_loss_sum) return set_error(AMDKGE_EINVAL, "train_shared_dist: NULL table / gradient / loss pointer");
-    if (B == 0) return AMDKGE_OK;
-    if (!d_triples || !d_neg_ids || !d_side || !d_work) return set_error(AMDKGE_EINVAL, "train_shared_dist: NULL triples / ids / sides / workspace");
-    if (G > B) G = B;
-    SharedPlan p;
-    if (!shared_plan(m, B, G, M, p)) return set_error(AMDKGE_EINVAL, "train_shared_dist: bad sizes");
-    hipStream_t st = (hipStream_t)stream;
-    char* work = static_cast<char*>(d_work);
-    if (m->scoring_type == AMDKGE_ROTATE)
-        return run_shared_dist<AMDKGE_ROTATE>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st, labels);
-    return run_shared_dist<AMDKGE_TRANSE>(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, work, p, mask, st, labels);
-}
+// both step entry points are shared_step on this family: the (optional) mask, or the labels
 
 extern "C" int amdkge_train_shared_dist_fwdbwd(const amdkge_model* m, const amdkge_loss* loss, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t B,
                                                int64_t G, int32_t M, const int32_t* d_neg_ids, const int32_t* d_side, float* d_grad_ent, float* d_grad_rel,
@@ -462,8 +410,8 @@ extern "C" int amdkge_train_shared_dist_fwdbwd(const amdkge_model* m, const amdk
     SharedMaskArgs ma;
     bool masked;
     if (int rc = shared_mask_args("train_shared_dist", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, d_stats, false, ma, masked)) return rc;
-    return shared_dist_fwdbwd(m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
-                              masked ? &ma : nullptr, nullptr, stream);
+    return shared_step(DISTANCES, m, loss, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
+                       masked ? &ma : nullptr, nullptr, stream);
 }
 
 // (include/amdkge_shared_labels.h)
@@ -476,6 +424,6 @@ extern "C" int amdkge_train_shared_dist_labels_fwdbwd(const amdkge_model* m, flo
     SharedLabelArgs la;
     if (int rc = shared_label_args("train_shared_dist_labels", d_neg_ids, d_s_lo, d_s_hi, d_s_ids, d_o_lo, d_o_hi, d_o_ids, list_mode, label_smoothing, reduction_mean,
                                    d_w_s, d_w_o, d_stats, la)) return rc;
-    return shared_dist_fwdbwd(m, nullptr, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
-                              nullptr, &la, stream);
+    return shared_step(DISTANCES, m, nullptr, d_ent, d_rel, d_triples, B, G, M, d_neg_ids, d_side, d_grad_ent, d_grad_rel, d_loss_sum, d_pos_scores, d_neg_scores, d_work,
+                       nullptr, &la, stream);
 }

@@ -472,19 +472,31 @@ class KgeEngine:
         """True when the shared-negative step (amdkge_train_shared_fwdbwd) covers this model and shape."""
         return int(self.lib.amdkge_train_shared_workspace_bytes(C.byref(self.model), int(B), int(group_size), int(num_negs))) > 0
 
+    def _shared_step(self, fn, ws_fn, refusal, head, triples, group_size, num_negs, ids, side, pos_scores, neg_scores, *tail):
+        """One shared-list train step, whichever entry point `fn` is: its family's workspace bytes (ws_fn) -> refuse a model /
+        shape it does not cover -> the "shared_work" buffer -> the call.  head: the arguments between the model and the tables
+        (the loss; label_smoothing and the reduction); tail: those between the workspace and the stream (_shared_lists, ...)."""
+        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
+        need = int(ws_fn(C.byref(self.model), B, G, M)) if B > 0 else 0
+        if B > 0 and need <= 0:
+            raise ValueError(f"{refusal} for this model / shape ({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
+        work = self._buf("shared_work", (need,), torch.uint8)
+        check(fn(C.byref(self.model), *head, _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M, _ptr(ids), _ptr(side), _ptr(self.g_ent), _ptr(self.g_rel),
+                 C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work), *tail, _stream()))
+
+    @staticmethod
+    def _shared_lists(s_filter, o_filter, identity):
+        """the six range arrays ((lo, hi, ids) per side, or None) and the list mode, as the masked and labelled entry points take them"""
+        sf, of = s_filter or (None, None, None), o_filter or (None, None, None)
+        return (_ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]), _ffi.SHARED_LIST_MODES["identity" if identity else "given"])
+
     def train_shared_fwdbwd(self, triples, group_size, num_negs, ids, side, loss, pos_scores=None, neg_scores=None):
         """amdkge_train_shared_fwdbwd: the train step of train_fwdbwd with eta = num_negs on the corruptions 'positive i with its
         side[i] entity replaced by ids[i // group_size][j]', as matrix products.  Accumulates into g_ent / g_rel and loss_acc[0];
         neg_scores (optional) has row j * B + i."""
-        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
-        need = int(self.lib.amdkge_train_shared_workspace_bytes(C.byref(self.model), B, G, M)) if B > 0 else 0
-        if B > 0 and need <= 0:
-            raise ValueError("train_shared_fwdbwd: shared negatives are not offered for this model / shape "
-                             f"({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
-        work = self._buf("shared_work", (need,), torch.uint8)
-        check(self.lib.amdkge_train_shared_fwdbwd(
-            C.byref(self.model), C.byref(loss), _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M, _ptr(ids), _ptr(side),
-            _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work), _stream()))
+        self._shared_step(self.lib.amdkge_train_shared_fwdbwd, self.lib.amdkge_train_shared_workspace_bytes,
+                          "train_shared_fwdbwd: shared negatives are not offered", (C.byref(loss),), triples, group_size, num_negs, ids, side,
+                          pos_scores, neg_scores)
 
     def shared_mask_scores(self, scores, row0, group_size, ids, side, s_filter, o_filter, identity=False, stats=None):
         """amdkge_shared_mask_scores (include/amdkge_shared_mask.h): the mask of the masked shared step alone, in place on the fp32
@@ -507,20 +519,11 @@ class KgeEngine:
         positive's known range -- s_filter / o_filter: (lo, hi, ids) of the B positives, both or neither -- is -inf before the loss;
         a positive whose whole list is known keeps its row.  identity: the promise that ids[g][j] == j (the all-entities list);
         stats: int64 [2] device tensor, += (masked, unmaskable).  Without the filters it is train_shared_fwdbwd."""
-        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
         if (s_filter is None) != (o_filter is None):
             raise ValueError("train_shared_masked_fwdbwd: s_filter and o_filter are given together or not at all")
-        need = int(self.lib.amdkge_train_shared_workspace_bytes(C.byref(self.model), B, G, M)) if B > 0 else 0
-        if B > 0 and need <= 0:
-            raise ValueError("train_shared_masked_fwdbwd: shared negatives are not offered for this model / shape "
-                             f"({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
-        work = self._buf("shared_work", (need,), torch.uint8)
-        sf, of = s_filter or (None, None, None), o_filter or (None, None, None)
-        check(self.lib.amdkge_train_shared_masked_fwdbwd(
-            C.byref(self.model), C.byref(loss), _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M, _ptr(ids), _ptr(side),
-            _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work),
-            _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]),
-            _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
+        self._shared_step(self.lib.amdkge_train_shared_masked_fwdbwd, self.lib.amdkge_train_shared_workspace_bytes,
+                          "train_shared_masked_fwdbwd: shared negatives are not offered", (C.byref(loss),), triples, group_size, num_negs, ids, side,
+                          pos_scores, neg_scores, *self._shared_lists(s_filter, o_filter, identity), _ptr(stats))
 
     def shared_dist_supported(self, B, group_size, num_negs):
         """True when the distance-tile shared step (amdkge_train_shared_dist_fwdbwd: TransE, RotatE) covers this model and shape."""
@@ -532,20 +535,11 @@ class KgeEngine:
         G x M scores of a group are a tile of distances instead of a matrix product.  The arguments are that method's: s_filter /
         o_filter (both or neither) mask the known statements, identity promises ids[g][j] == j, stats int64 [2] += (masked,
         unmaskable).  Accumulates into g_ent / g_rel and loss_acc[0]; neg_scores (optional) has row j * B + i."""
-        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
         if (s_filter is None) != (o_filter is None):
             raise ValueError("train_shared_dist_fwdbwd: s_filter and o_filter are given together or not at all")
-        need = int(self.lib.amdkge_train_shared_dist_workspace_bytes(C.byref(self.model), B, G, M)) if B > 0 else 0
-        if B > 0 and need <= 0:
-            raise ValueError("train_shared_dist_fwdbwd: distance-tile shared negatives are not offered for this model / shape "
-                             f"({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
-        work = self._buf("shared_work", (need,), torch.uint8)
-        sf, of = s_filter or (None, None, None), o_filter or (None, None, None)
-        check(self.lib.amdkge_train_shared_dist_fwdbwd(
-            C.byref(self.model), C.byref(loss), _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M, _ptr(ids), _ptr(side),
-            _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores), _ptr(work),
-            _ptr(sf[0]), _ptr(sf[1]), _ptr(sf[2]), _ptr(of[0]), _ptr(of[1]), _ptr(of[2]),
-            _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
+        self._shared_step(self.lib.amdkge_train_shared_dist_fwdbwd, self.lib.amdkge_train_shared_dist_workspace_bytes,
+                          "train_shared_dist_fwdbwd: distance-tile shared negatives are not offered", (C.byref(loss),), triples, group_size, num_negs, ids,
+                          side, pos_scores, neg_scores, *self._shared_lists(s_filter, o_filter, identity), _ptr(stats))
 
     def shared_label_loss(self, scores, row0, group_size, ids, side, s_filter, o_filter, label_smoothing=0.0, reduction="sum", scale=1.0,
                           weights=None, identity=False, loss_sum=None, stats=None):
@@ -571,20 +565,12 @@ class KgeEngine:
 
     def _train_shared_labels(self, fn, ws_fn, who, triples, group_size, num_negs, ids, side, s_filter, o_filter, label_smoothing, reduction, weights,
                              identity, stats, pos_scores, neg_scores):
-        B, G, M = int(triples.shape[0]), int(group_size), int(num_negs)
         if s_filter is None or o_filter is None:
             raise ValueError(who + ": s_filter and o_filter are both required (the labels are the known ranges)")
-        need = int(ws_fn(C.byref(self.model), B, G, M)) if B > 0 else 0
-        if B > 0 and need <= 0:
-            raise ValueError(who + ": the labelled shared step is not offered for this model / shape "
-                             f"({self.scoring_type}, B={B}, group_size={G}, num_negs={M})")
-        work = self._buf("shared_work", (need,), torch.uint8)
         ws, wo = weights if weights is not None else (None, None)
-        check(fn(
-            C.byref(self.model), float(label_smoothing), 1 if reduction == "mean" else 0, _ptr(self.ent), _ptr(self.rel), _ptr(triples), B, G, M,
-            _ptr(ids), _ptr(side), _ptr(self.g_ent), _ptr(self.g_rel), C.c_void_p(self.loss_acc.data_ptr()), _ptr(pos_scores), _ptr(neg_scores),
-            _ptr(work), _ptr(s_filter[0]), _ptr(s_filter[1]), _ptr(s_filter[2]), _ptr(o_filter[0]), _ptr(o_filter[1]), _ptr(o_filter[2]),
-            _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(ws), _ptr(wo), _ptr(stats), _stream()))
+        self._shared_step(fn, ws_fn, who + ": the labelled shared step is not offered", (float(label_smoothing), 1 if reduction == "mean" else 0), triples,
+                          group_size, num_negs, ids, side, pos_scores, neg_scores, *self._shared_lists(s_filter, o_filter, identity), _ptr(ws), _ptr(wo),
+                          _ptr(stats))
 
     def train_shared_labels_fwdbwd(self, triples, group_size, num_negs, ids, side, s_filter, o_filter, label_smoothing=0.0, reduction="sum",
                                    weights=None, identity=False, stats=None, pos_scores=None, neg_scores=None):

@@ -264,6 +264,45 @@ def test_shared_dist_masked_zero_gradient_rows(gpu_lib):
     assert not Ge[20:25].any() and Ge[25].any() and not Ge[26:].any() and np.isfinite(Ge).all() and np.isfinite(Gr).all()
 
 
+def test_shared_dist_masked_step_across_the_score_chunk(gpu_lib):
+    """B * M = 4 200 * 4 097 > 2^24 (test_gpu_shared_mask.py::test_masked_step_across_the_score_chunk's shape and batch) on the
+    distance tiles: 63 groups of 64 fill the first chunk, rows 4 032 .. 4 199 are the second, whose tiles must read ITS groups' lists
+    and whose mask ITS rows' ranges.  The reference is the header's arithmetic (tests/shared_dist_ref.py), a DistStep per group: the
+    pairwise loss is a sum over the positives, so the groups' losses and gradients add.  The bars are check_against_ref's, but for
+    the entity gradient: a row there is the fp32 sum, by atomics in arrival order, of some 3 * 10^5 terms +-c (TransE: a coefficient
+    times a sign, so the terms cancel down to a sum far below their number).  Its gap was 4.47e-5 and 4.63e-5 of the row's largest
+    entry in two runs of the two per-family drivers this test was first run on, against 2e-5; the bar is twice the larger.  The
+    relation gradient's was 1.95e-6 and 2.01e-6, the scores' 1.55e-7: their bars stay."""
+    from test_gpu_shared_mask import mask_case
+
+    model, N, R, k, B, G, M = "TransE", 50, 2, 7, 4200, 64, 4097
+    eng, ent, rel = make_engine(model, k, N, R, scale=0.6)
+    X, ids, side, ks, ko = mask_case(B, G, M, N, seed=7)
+    known = np.zeros((B, N), dtype=bool)                                     # (mask_matrix, vectorised: ids < N)
+    for i in range(B):
+        known[i, ks[i] if side[i] else ko[i]] = True
+    mask = known[np.arange(B)[:, None], ids[np.arange(B) // G]]
+    assert not mask.all(1).any() and mask[4032:].any() and not np.array_equal(mask[4032:], mask[:168])
+    got, stats = run_dist(eng, X, G, ids, side, "pairwise", "mean", ks, ko)
+    L, Ge, Gr, ps, ns = got
+    assert np.array_equal(np.isneginf(ns.reshape(M, B).T), mask) and not np.isposinf(ns).any() and stats == [int(mask.sum()), 0]
+    want, Te, Tr, sp, S = 0.0, np.zeros(ent.shape), np.zeros(rel.shape), np.empty(B, np.float32), np.empty((B, M), np.float32)
+    for g in range(SR.n_groups(B, G)):
+        rows = slice(g * G, min((g + 1) * G, B))
+        Lg, Eg, Rg, sp[rows], sn = DR.DistStep(model, ent, rel, X[rows], G, ids[g:g + 1], side[rows], R).step("pairwise", "mean", mask=mask[rows])
+        S[rows] = sn.reshape(M, -1).T
+        want, Te, Tr = want + Lg, Te + Eg, Tr + Rg
+    live = ~mask
+    nsm = ns.reshape(M, B).T
+    print(f"chunked: loss {L:.9g} / {want:.9g}, grad gap ent {grad_gap(Ge, Te):.3g} rel {grad_gap(Gr, Tr):.3g}, "
+          f"score gap {np.abs(nsm[live] - S[live]).max() / np.abs(S[live]).max():.3g}, masked {stats[0]}")
+    assert np.allclose(ps, sp, rtol=1e-5, atol=1e-5 * np.abs(sp).max())
+    assert np.allclose(nsm[live], S[live], rtol=1e-5, atol=1e-5 * np.abs(S[live]).max())
+    assert abs(L - want) <= 1e-5 * max(1.0, abs(L)), (L, want)
+    assert_grads_close(Ge, Te, tol=2 * 4.63e-5)
+    assert_grads_close(Gr, Tr)
+
+
 def test_shared_dist_device_path_refusals(gpu_lib):
     N, R, B, G, M = 50, 3, 10, 4, 6
     X = dev(rand_triples(np.random.default_rng(7), B, N, R))
