@@ -231,6 +231,7 @@ TYPES_SIGNATURES = {
                                                 P, P, P, P, P, P, P]),
 }
 
+SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, NEG_SIGNATURES, SHARED_SIGNATURES, SHARED_MASK_SIGNATURES, SHARED_DIST_SIGNATURES, SHARED_LABELS_SIGNATURES, BATCH_REG_SIGNATURES, RELATION_OBJECTIVE_SIGNATURES, TYPES_SIGNATURES)
 _lib = None
 
 
@@ -247,7 +248,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(SHARED_SIGNATURES.items()) + list(SHARED_MASK_SIGNATURES.items()) + list(SHARED_DIST_SIGNATURES.items()) + list(SHARED_LABELS_SIGNATURES.items()) + list(BATCH_REG_SIGNATURES.items()) + list(RELATION_OBJECTIVE_SIGNATURES.items()) + list(TYPES_SIGNATURES.items()):
+    for name, (res, args) in [entry for table in SIGNATURE_TABLES for entry in table.items()]:
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

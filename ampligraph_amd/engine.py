@@ -498,16 +498,21 @@ class KgeEngine:
                           "train_shared_fwdbwd: shared negatives are not offered", (C.byref(loss),), triples, group_size, num_negs, ids, side,
                           pos_scores, neg_scores)
 
+    @staticmethod
+    def _score_window(who, scores, row0, side, group_size):
+        """(rows, M, the group size clamped to the batch) of a score buffer [rows, M] whose row r is batch row row0 + r of side [B]"""
+        rows, M = int(scores.shape[0]), int(scores.shape[1])
+        B = int(side.shape[0])
+        if int(row0) < 0 or int(row0) + rows > B or not scores.is_contiguous():
+            raise ValueError(who + ": rows [row0, row0 + rows) must lie inside the batch and the buffer be contiguous")
+        return rows, M, max(1, min(int(group_size), B)) if int(group_size) >= 1 else int(group_size)
+
     def shared_mask_scores(self, scores, row0, group_size, ids, side, s_filter, o_filter, identity=False, stats=None):
         """amdkge_shared_mask_scores (include/amdkge_shared_mask.h): the mask of the masked shared step alone, in place on the fp32
         device tensor scores [rows, M] whose row r is batch row row0 + r.  side int32 [B]; ids int32 [ceil(B / group_size), M] (may
         be None with identity=True, the promise that ids[g][j] == j); s_filter / o_filter: (lo, hi, ids) of the B positives
         (FilterIndex.device_filter's form); stats: int64 [2] device tensor, += (masked, unmaskable)."""
-        rows, M = int(scores.shape[0]), int(scores.shape[1])
-        B = int(side.shape[0])
-        if int(row0) < 0 or int(row0) + rows > B or not scores.is_contiguous():
-            raise ValueError("shared_mask_scores: rows [row0, row0 + rows) must lie inside the batch and the buffer be contiguous")
-        G = max(1, min(int(group_size), B)) if int(group_size) >= 1 else int(group_size)
+        rows, M, G = self._score_window("shared_mask_scores", scores, row0, side, group_size)
         check(self.lib.amdkge_shared_mask_scores(
             _ptr(scores), int(row0), rows, G, M, _ptr(ids), _ptr(side), _ptr(s_filter[0]), _ptr(s_filter[1]), _ptr(s_filter[2]),
             _ptr(o_filter[0]), _ptr(o_filter[1]), _ptr(o_filter[2]), _ffi.SHARED_LIST_MODES["identity" if identity else "given"], _ptr(stats), _stream()))
@@ -550,11 +555,7 @@ class KgeEngine:
         int32 [ceil(B / group_size), M] (may be None with identity=True, the promise that ids[g][j] == j); weights: None or (w_s,
         w_o) fp32 [B] device tensors; loss_sum: float64 [1] device tensor, += the rows' losses (default: loss_acc[0]); stats: int64
         [2] device tensor, += (labelled, unlabelled_rows)."""
-        rows, M = int(scores.shape[0]), int(scores.shape[1])
-        B = int(side.shape[0])
-        if int(row0) < 0 or int(row0) + rows > B or not scores.is_contiguous():
-            raise ValueError("shared_label_loss: rows [row0, row0 + rows) must lie inside the batch and the buffer be contiguous")
-        G = max(1, min(int(group_size), B)) if int(group_size) >= 1 else int(group_size)
+        rows, M, G = self._score_window("shared_label_loss", scores, row0, side, group_size)
         ws, wo = weights if weights is not None else (None, None)
         acc = self.loss_acc if loss_sum is None else loss_sum
         check(self.lib.amdkge_shared_label_loss(

@@ -18,6 +18,7 @@ from .. import _ffi
 from ..datasets.filters import FilterIndex, PairFilterIndex
 from ..datasets.indexer import DataIndexer
 from ..evaluation.metrics import hits_at_n_score, mr_score, mrr_score
+from ..trainer import BATCH_REG, StepLoop, fit_modes, refuse_modes
 from . import loss_functions, optimizers, regularizers
 from .initializers import RowSource, initialise, stream_cost
 
@@ -232,14 +233,7 @@ class ScoringBasedEmbeddingModel:
         # independent per table, either may be None, each a sum of at most two LP terms (EmbeddingLookupLayer.py:131-155)
         self._regularizers = [regularizers.get(r) for r in regs]
         if any(regularizers.is_batch(r) for r in self._regularizers):   # BatchLPRegularizer: what it cannot be combined with
-            if self._deterministic:
-                raise NotImplementedError("batch regularizer: its gradient rows are added with atomics, in no fixed order; "
-                                          "deterministic=True is not offered")
-            if optimizer_mode == "lazy":
-                raise NotImplementedError("batch regularizer: optimizer_mode='lazy' was not built for it")
-            if self._sharding != "replicated":
-                raise NotImplementedError("batch regularizer: entity_sharding='{}' was not built for it; use replicated tables "
-                                          "on one GPU".format(self._sharding))
+            refuse_modes(*BATCH_REG, deterministic=self._deterministic, lazy=optimizer_mode == "lazy", sharding=self._sharding)
             for r, table in zip(self._regularizers, ("ent", "rel")):
                 if regularizers.is_batch(r):
                     r.norm_for(self.scoring_type, table)   # ValueError: norm="modulus" on rows without complex units
@@ -337,13 +331,7 @@ class ScoringBasedEmbeddingModel:
             self._loop = self._make_loop()
         loop = self._loop
         if any(regularizers.is_batch(r) for r in self._regularizers):
-            if self.use_focusE:
-                raise NotImplementedError("batch regularizer: FocusE was not built for it")
-            if getattr(loop, "multi", False):
-                raise NotImplementedError("batch regularizer: it runs on one rank only")
-            if getattr(loop, "deterministic", False):
-                raise NotImplementedError("batch regularizer: its gradient rows are added with atomics, in no fixed order; "
-                                          "deterministic mode is not offered")
+            refuse_modes(*BATCH_REG, **fit_modes(self))
         cbs = list(callbacks or [])
         self._placement.begin_fit(bool(cbs))
         # negatives are keyed by a step counter that continues where the optimizer's iteration count stands: a run resumed
@@ -357,8 +345,6 @@ class ScoringBasedEmbeddingModel:
         # rows, thresholds and pool are made once; a step slices them (negatives.BoundNegatives).  Only trainer.StepLoop has the
         # sampler attribute: ShardedStepLoop.negatives is that loop's own "local" | "global" setting and is never touched here
         # (compile() refuses a sampler on sharded tables)
-        from ..trainer import StepLoop
-
         if type(loop) is StepLoop:
             loop.negatives = None if self._negatives is None else self._negatives.bind(self, eng, train)
             loop.relation = None if self._relation_prediction is None else self._relation_prediction.bind(self, eng, train)

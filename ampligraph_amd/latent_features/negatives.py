@@ -4,21 +4,22 @@ Without the setting every corruption is drawn inside the train kernels: a fair c
 (draw_corruption, kge_device.h).  `NegativeSampling` describes the three things that rule lacks -- rejection of KNOWN statements
 (PyKEEN / LibKGE / DGL-KE's filtered negatives), the per-relation Bernoulli side choice of TransH, and a caller's pool of
 replacement entities (AmpliGraph 1.x's negative_corruption_entities) -- and `bind()` turns it, once per fit(), into a
-`BoundNegatives`: the object trainer.StepLoop calls each step.  It runs amdkge_sample_negatives (kge_negatives.hip; the draw is
-defined in include/amdkge_negatives.h) and hands the rows to the train step as its neg_override: the train kernels and the loss are
-the ones of the default path.
+`BoundNegatives`: the object trainer.StepLoop calls each step for its override rows.  It runs amdkge_sample_negatives
+(kge_negatives.hip; the draw is defined in include/amdkge_negatives.h) and hands the rows to the train step as its neg_override: the
+train kernels and the loss are the ones of the default path.
 
 `TypedNegatives` is a NegativeSampling whose replacements come from the positive's own relation's domain / range set
 (datasets/types.py; amdkge_sample_negatives_typed, include/amdkge_types.h): it binds to a `BoundTypedNegatives`, the same step.
 
 `SharedNegatives` is the other kind: one list of replacement entities per GROUP of positives, scored by a matrix product
-(kge_train_shared.hip).  It binds to a `BoundSharedNegatives`, whose step is engine.train_shared_fwdbwd instead of the override; with
+(kge_train_shared.hip).  It binds to a `BoundSharedNegatives`, which owns the step's backward call -- trainer.StepLoop asks its step() to
+draw and to run engine.train_shared_fwdbwd, instead of asking for override rows --; with
 `mask_known` to a `BoundMaskedSharedNegatives`, whose step is engine.train_shared_masked_fwdbwd (include/amdkge_shared_mask.h: the
 scores of corruptions that are known statements are -inf before the loss).  num_negs="all" makes every list every entity.
 
 `SharedDistanceNegatives` is SharedNegatives for TransE and RotatE, whose score against a shared list is a tile of distances instead
-of a matrix product (kge_train_shared_dist.hip, include/amdkge_shared_dist.h).  It binds to the same two classes with
-`distance = True` set: their step is engine.train_shared_dist_fwdbwd.
+of a matrix product (kge_train_shared_dist.hip, include/amdkge_shared_dist.h).  It binds to the same two classes, constructed with
+distance=True: their step is engine.train_shared_dist_fwdbwd.
 
 `KvsAll` is the shared step on the all-entities list with LABELS instead of a mask: every known answer of a row's query is labelled
 1 and the loss is binary cross-entropy (loss_functions.BCELoss; include/amdkge_shared_labels.h).  It binds to a `BoundKvsAll`, whose
@@ -28,6 +29,77 @@ import numpy as np
 
 from .. import _ffi
 from ..datasets.filters import FilterIndex
+from ..trainer import SHARED_STEP, fit_modes, refuse_modes
+
+
+# ---- the argument checks every setting shares (relation_prediction.py too); `who` is the message prefix, `name` the caller's argument
+def check_side(side, who="negatives"):
+    if not isinstance(side, str) or side not in _ffi.NEG_SIDE_MODES:
+        raise ValueError("{}: `side` must be 'uniform', 'bernoulli', 's' or 'o', got {!r}".format(who, side))
+    return side
+
+
+def check_entities(entities, who="negatives"):
+    """None or a non-empty 1-D sequence of labels -> None or their numpy array"""
+    if entities is None:
+        return None
+    if isinstance(entities, (str, bytes)) or np.ndim(entities) != 1 or len(entities) < 1:
+        raise ValueError("{}: `entities` must be None or a non-empty 1-D sequence of entity labels".format(who))
+    return np.asarray(entities)
+
+
+def check_datasets(value, name, who="negatives", allow_false=True):
+    """False (where the caller has an off state) | True (the training set) | a non-empty dict of datasets next to it -> bool or the dict"""
+    if isinstance(value, dict) and len(value) > 0:
+        return value
+    if isinstance(value, (bool, np.bool_)) and (allow_false or bool(value)):
+        return bool(value)
+    raise ValueError("{}: `{}` must be {}True (the training set) or a non-empty dict of datasets known next to it".format(
+        who, name, "False, " if allow_false else ""))
+
+
+# ---- what every bind() does with them, once per fit()
+def known_index(model, engine, train, datasets, index_cls=FilterIndex):
+    """The device index of class `index_cls` over the known statements: the training tensor and, when `datasets` is a dict, its
+    datasets in the training id map (rows with labels the training set does not hold are dropped)."""
+    extra = []
+    if isinstance(datasets, dict):
+        from .models import _load_triples
+
+        extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in datasets.values()]
+    return index_cls([train] + extra, int(model._n_ents), int(model._n_rels), engine=engine)
+
+
+def entity_pool(model, engine, labels):
+    """None, or the int32 device ids of the entity labels replacements are drawn from (the train kernels do not check ids)"""
+    if labels is None:
+        return None
+    import torch
+
+    N = int(model._n_ents)
+    ids = np.asarray(model.data_indexer.get_indexes(labels, "e"), dtype=np.int64)
+    if ids.shape[0] != labels.shape[0]:
+        raise ValueError("negatives: {} of the `entities` are not in the training set".format(labels.shape[0] - ids.shape[0]))
+    if ids.min() < 0 or ids.max() >= N:
+        raise ValueError("negatives: entity ids outside [0, {})".format(N))
+    return torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32)).to(engine.device)
+
+
+def batch_slice(train, batch, lo=0, hi=None):
+    """slice(r0, r1): where rows [lo, hi) of `batch` (all of it by default) lie in an array over ALL training rows -- fit()'s batches
+    are row slices of the tensor `train` a sampler was bound to, so a step slices what bind() looked up and runs no lookup of its own"""
+    if batch.untyped_storage().data_ptr() != train.untyped_storage().data_ptr() or batch.dtype != train.dtype or not batch.is_contiguous():
+        raise ValueError("negatives: the batch is not a row slice of the training tensor this sampler was bound to")
+    off = batch.storage_offset() - train.storage_offset()
+    if off < 0 or off % 3 or off // 3 + int(batch.shape[0]) > int(train.shape[0]):
+        raise ValueError("negatives: the batch is not a row slice of the training tensor this sampler was bound to")
+    r0 = off // 3 + int(lo)
+    return slice(r0, r0 + (int(batch.shape[0]) if hi is None else int(hi)) - int(lo))
+
+
+def _cut(ranges, rows):
+    """a (lo, hi, ids) of all training rows -> that of the rows"""
+    return ranges[0][rows], ranges[1][rows], ranges[2]
 
 
 class NegativeSampling:
@@ -40,18 +112,10 @@ class NegativeSampling:
     max_tries: draws per corruption before the last rejected one is kept (1 .. 32; 1 with a filter only counts)."""
 
     def __init__(self, filter=False, side="uniform", entities=None, max_tries=8):
-        if not (isinstance(filter, (bool, np.bool_)) or (isinstance(filter, dict) and len(filter) > 0)):
-            raise ValueError("negatives: `filter` must be False, True or a non-empty dict of datasets")
-        if not isinstance(side, str) or side not in _ffi.NEG_SIDE_MODES:
-            raise ValueError("negatives: `side` must be 'uniform', 'bernoulli', 's' or 'o', got {!r}".format(side))
+        self.filter, self.side = check_datasets(filter, "filter"), check_side(side)
         if isinstance(max_tries, bool) or not isinstance(max_tries, (int, np.integer)) or not 1 <= int(max_tries) <= _ffi.NEG_MAX_TRIES:
             raise ValueError("negatives: `max_tries` must be an integer in [1, {}]".format(_ffi.NEG_MAX_TRIES))
-        if entities is not None:
-            if isinstance(entities, (str, bytes)) or np.ndim(entities) != 1 or len(entities) < 1:
-                raise ValueError("negatives: `entities` must be None or a non-empty 1-D sequence of entity labels")
-            entities = np.asarray(entities)
-        self.filter = filter if isinstance(filter, dict) else bool(filter)
-        self.side, self.entities, self.max_tries = side, entities, int(max_tries)
+        self.entities, self.max_tries = check_entities(entities), int(max_tries)
 
     @classmethod
     def get(cls, spec):
@@ -86,25 +150,8 @@ class NegativeSampling:
 
     def _bind_parts(self, model, engine, train):
         """(the FilterIndex over the known statements or None, the pool's int32 device ids or None)"""
-        import torch
-
-        N, R = int(model._n_ents), int(model._n_rels)
-        pool = None
-        if self.entities is not None:
-            ids = np.asarray(model.data_indexer.get_indexes(self.entities, "e"), dtype=np.int64)
-            if ids.shape[0] != self.entities.shape[0]:
-                raise ValueError("negatives: {} of the `entities` are not in the training set".format(self.entities.shape[0] - ids.shape[0]))
-            if ids.min() < 0 or ids.max() >= N:   # the train kernels do not check override ids
-                raise ValueError("negatives: entity ids outside [0, {})".format(N))
-            pool = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32)).to(engine.device)
-        index = None
-        if self.filter is not False or self.side == "bernoulli":
-            extra = []
-            if isinstance(self.filter, dict):
-                from .models import _load_triples
-
-                extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in self.filter.values()]
-            index = FilterIndex([train] + extra, N, R, engine=engine)
+        pool = entity_pool(model, engine, self.entities)
+        index = known_index(model, engine, train, self.filter) if self.filter is not False or self.side == "bernoulli" else None
         return index, pool
 
 
@@ -134,19 +181,12 @@ class BoundNegatives:
 
     def _first_row(self, batch):
         """the training row `batch` starts at: fit()'s batches are row slices of the tensor this sampler was bound to"""
-        t = self.train
-        if batch.untyped_storage().data_ptr() != t.untyped_storage().data_ptr() or batch.dtype != t.dtype or not batch.is_contiguous():
-            raise ValueError("negatives: the batch is not a row slice of the training tensor this sampler was bound to")
-        off = batch.storage_offset() - t.storage_offset()
-        if off < 0 or off % 3 or off // 3 + int(batch.shape[0]) > int(t.shape[0]):
-            raise ValueError("negatives: the batch is not a row slice of the training tensor this sampler was bound to")
-        return off // 3
+        return batch_slice(self.train, batch).start
 
     def _step_args(self, global_batch, lo, hi):
         """(the batch rows, the keywords both samplers take, cut): cut slices a (lo, hi, ids) of all training rows to the batch's"""
-        r0 = self._first_row(global_batch) + int(lo)
-        r1 = r0 + int(hi) - int(lo)
-        cut = lambda f: None if f is None else (f[0][r0:r1], f[1][r0:r1], f[2])   # noqa: E731
+        rows = batch_slice(self.train, global_batch, lo, hi)
+        cut = lambda f: None if f is None else _cut(f, rows)   # noqa: E731
         kw = dict(row_offset=lo, b_global=int(global_batch.shape[0]), side=self.side, side_thr=self.side_thr, pool=self.pool,
                   s_filter=cut(self.s_filter), o_filter=cut(self.o_filter), max_tries=self.max_tries, stats=self.stats_dev)
         return global_batch[lo:hi], kw, cut
@@ -252,6 +292,7 @@ class SharedNegatives:
 
     shared = True   # what trainer.StepLoop.step looks for
     KEY = "shared"  # the key of the dict form that carries num_negs
+    DISTANCE = False   # the bound sampler's entry points: matrix products (kge_train_shared.hip) or distance tiles (kge_train_shared_dist.hip)
     ALL_GROUP_SIZE = 4096   # measured: the products want >= 4 096 rows per chunk; the score buffer is 4 * group_size * num_negs bytes
 
     def __init__(self, num_negs, group_size=None, side="uniform", entities=None, mask_known=False):
@@ -268,16 +309,7 @@ class SharedNegatives:
             self.num_negs = count(num_negs, "num_negs", _ffi.SHARED_MAX_NEGS)
         default_g = self.ALL_GROUP_SIZE if self.num_negs == "all" else self.num_negs
         self.group_size = default_g if group_size is None else count(group_size, "group_size", 2 ** 31 - 1)
-        if not isinstance(side, str) or side not in _ffi.NEG_SIDE_MODES:
-            raise ValueError("negatives: `side` must be 'uniform', 'bernoulli', 's' or 'o', got {!r}".format(side))
-        if entities is not None:
-            if isinstance(entities, (str, bytes)) or np.ndim(entities) != 1 or len(entities) < 1:
-                raise ValueError("negatives: `entities` must be None or a non-empty 1-D sequence of entity labels")
-            entities = np.asarray(entities)
-        if not (isinstance(mask_known, (bool, np.bool_)) or (isinstance(mask_known, dict) and len(mask_known) > 0)):
-            raise ValueError("negatives: `mask_known` must be False, True or a non-empty dict of datasets")
-        self.side, self.entities = side, entities
-        self.mask_known = mask_known if isinstance(mask_known, dict) else bool(mask_known)
+        self.side, self.entities, self.mask_known = check_side(side), check_entities(entities), check_datasets(mask_known, "mask_known")
 
     @classmethod
     def from_dict(cls, spec):
@@ -301,54 +333,33 @@ class SharedNegatives:
             raise NotImplementedError("negatives: shared negatives need a score that is a contraction with the replaced row "
                                       "(DistMult, ComplEx, HolE); {} scores a distance: its shared step is "
                                       "SharedDistanceNegatives".format(model.scoring_type))
-        self._check_modes(model, optimizer_mode)
-
-    @staticmethod
-    def _check_modes(model, optimizer_mode):
-        if model._deterministic:
-            raise NotImplementedError("negatives: shared negatives accumulate in no fixed order; deterministic=True is not offered")
-        if optimizer_mode == "lazy":
-            raise NotImplementedError("negatives: shared negatives are not offered with optimizer_mode='lazy'")
+        check_shared_modes(model, optimizer_mode)
 
     def bind(self, model, engine, train):
         import torch
 
-        loop = getattr(model, "_loop", None)
-        if getattr(model, "use_focusE", False):
-            raise NotImplementedError("negatives: FocusE is not offered with shared negatives")
-        if getattr(loop, "multi", False):
-            raise NotImplementedError("negatives: shared negatives run on one rank only")
-        if getattr(loop, "deterministic", False):
-            raise NotImplementedError("negatives: shared negatives accumulate in no fixed order; deterministic mode is not offered")
-        N, R = int(model._n_ents), int(model._n_rels)
-        pool = None
-        if self.entities is not None:
-            ids = np.asarray(model.data_indexer.get_indexes(self.entities, "e"), dtype=np.int64)
-            if ids.shape[0] != self.entities.shape[0]:
-                raise ValueError("negatives: {} of the `entities` are not in the training set".format(self.entities.shape[0] - ids.shape[0]))
-            if ids.min() < 0 or ids.max() >= N:   # the train kernels do not check the ids
-                raise ValueError("negatives: entity ids outside [0, {})".format(N))
-            pool = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32)).to(engine.device)
+        refuse_modes(*SHARED_STEP, **fit_modes(model))
+        pool = entity_pool(model, engine, self.entities)
         index, side_thr = None, None
         if self.mask_known is not False or self.side == "bernoulli":
-            extra = []
-            if isinstance(self.mask_known, dict):
-                from .models import _load_triples
-
-                extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in self.mask_known.values()]
-            index = FilterIndex([train] + extra, N, R, engine=engine)
+            index = known_index(model, engine, train, self.mask_known)
         if self.side == "bernoulli":   # (thresholds over the index's statements: the training set, and the mask's datasets when given)
             side_thr = engine.negatives_side_thresholds(*index.device_keys(engine), index.n_ents, index.n_rels)
         num_negs, all_list = self.num_negs, None
         if num_negs == "all":   # the list every group shares: every entity in id order, or the pool in the order given
-            all_list = pool if pool is not None else torch.arange(N, dtype=torch.int32, device=engine.device)
+            all_list = pool if pool is not None else torch.arange(int(model._n_ents), dtype=torch.int32, device=engine.device)
             num_negs = int(all_list.numel())
             if num_negs > _ffi.SHARED_MAX_NEGS:
                 raise ValueError("negatives: 'all' needs at most {} entities".format(_ffi.SHARED_MAX_NEGS))
         if self.mask_known is False:
-            return BoundSharedNegatives(engine, num_negs, self.group_size, self.side, side_thr, pool, all_list=all_list)
+            return BoundSharedNegatives(engine, num_negs, self.group_size, self.side, side_thr, pool, all_list=all_list, distance=self.DISTANCE)
         return BoundMaskedSharedNegatives(engine, num_negs, self.group_size, self.side, side_thr, pool, all_list=all_list, train=train, index=index,
-                                          identity=all_list is not None and pool is None)
+                                          identity=all_list is not None and pool is None, distance=self.DISTANCE)
+
+
+def check_shared_modes(model, optimizer_mode):
+    """compile()'s mode refusals of every sampler that owns its step (entity_sharding is refused for every sampler, in compile() itself)"""
+    refuse_modes(*SHARED_STEP, deterministic=model._deterministic, lazy=optimizer_mode == "lazy")
 
 
 class SharedDistanceNegatives(SharedNegatives):
@@ -363,32 +374,34 @@ class SharedDistanceNegatives(SharedNegatives):
     "side": ..., "entities": ..., "mask_known": ...})."""
 
     KEY = "shared_distance"
+    DISTANCE = True
 
     def check_model(self, model, optimizer_mode="dense"):
         if model.scoring_type not in ("TransE", "RotatE"):
             raise NotImplementedError("negatives: SharedDistanceNegatives is the shared step of the models that score a distance (TransE, RotatE); "
                                       "{} scores a contraction: use SharedNegatives".format(model.scoring_type))
-        self._check_modes(model, optimizer_mode)
-
-    def bind(self, model, engine, train):
-        bound = super().bind(model, engine, train)
-        bound.distance = True   # trainer.StepLoop.step: engine.train_shared_dist_fwdbwd
-        return bound
+        check_shared_modes(model, optimizer_mode)
 
 
 class BoundSharedNegatives:
-    """A SharedNegatives bound to one fit().  trainer.StepLoop.step calls draw(global_batch, seed, step) -> (ids int32
-    [n_groups, num_negs], side int32 [B]) and hands both to engine.train_shared_fwdbwd -- to engine.train_shared_dist_fwdbwd when
-    `distance` is set (SharedDistanceNegatives.bind).  all_list: None, or the int32 device list
-    [num_negs] of num_negs="all": every group's row of ids is that list -- the id tensor is built once (and again only for a batch
-    with more groups than any before), a step draws the sides alone."""
+    """A SharedNegatives bound to one fit().  It owns the step's backward call: trainer.StepLoop.step calls step(global_batch, loss,
+    seed, rng_step), which draws -- draw(global_batch, seed, step) -> (ids int32 [n_groups, num_negs], side int32 [B]) -- and hands
+    both to engine.train_shared_fwdbwd, or with distance=True (SharedDistanceNegatives) to engine.train_shared_dist_fwdbwd.
+    all_list: None, or the int32 device list [num_negs] of num_negs="all": every group's row of ids is that list -- the id tensor
+    is built once (and again only for a batch with more groups than any before), a step draws the sides alone."""
 
-    shared = True
+    shared = True   # what trainer.StepLoop.step looks for: the sampler runs the backward call itself
 
-    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list=None):
+    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list=None, distance=False):
         self.engine, self.num_negs, self.group_size = engine, int(num_negs), int(group_size)
         self.side, self.side_thr, self.pool = side, side_thr, pool
-        self.all_list, self._all_ids = all_list, None
+        self.distance, self.all_list, self._all_ids = bool(distance), all_list, None
+
+    def step(self, global_batch, loss, seed, rng_step):
+        """loss: the step's amdkge_loss descriptor"""
+        ids, side = self.draw(global_batch, seed, rng_step)
+        fwdbwd = self.engine.train_shared_dist_fwdbwd if self.distance else self.engine.train_shared_fwdbwd
+        fwdbwd(global_batch, self.group_size, self.num_negs, ids, side, loss)
 
     def draw(self, global_batch, seed, step):
         if self.all_list is None:
@@ -406,12 +419,13 @@ class BoundSharedNegatives:
 class BoundMaskedSharedNegatives(BoundSharedNegatives):
     """BoundSharedNegatives with the mask of known statements: the FilterIndex over the training set (and mask_known's datasets) and
     the range arrays of ALL training rows -- two range lookups at bind time, as in BoundNegatives; mask(global_batch) slices them.
-    trainer.StepLoop.step hands them to engine.train_shared_masked_fwdbwd with `identity` (the list is 0 .. N - 1) and `stats_dev`."""
+    step() hands them to engine.train_shared_masked_fwdbwd (distance=True: train_shared_dist_fwdbwd) with `identity` (the list is
+    0 .. N - 1) and `stats_dev`."""
 
-    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity):
+    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity, distance=False):
         import torch
 
-        super().__init__(engine, num_negs, group_size, side, side_thr, pool, all_list=all_list)
+        super().__init__(engine, num_negs, group_size, side, side_thr, pool, all_list=all_list, distance=distance)
         self.train, self.index, self.identity = train, index, bool(identity)
         self.stats_dev = torch.zeros(2, dtype=torch.int64, device=engine.device)
         self.s_filter = index.device_filter(engine, train, "s")
@@ -419,9 +433,15 @@ class BoundMaskedSharedNegatives(BoundSharedNegatives):
 
     def mask(self, global_batch):
         """-> (s_filter, o_filter) of the batch's rows: (lo, hi, ids) each"""
-        r0 = BoundNegatives._first_row(self, global_batch)
-        r1 = r0 + int(global_batch.shape[0])
-        return tuple((f[0][r0:r1], f[1][r0:r1], f[2]) for f in (self.s_filter, self.o_filter))
+        rows = batch_slice(self.train, global_batch)
+        return _cut(self.s_filter, rows), _cut(self.o_filter, rows)
+
+    def step(self, global_batch, loss, seed, rng_step):
+        ids, side = self.draw(global_batch, seed, rng_step)
+        s_filter, o_filter = self.mask(global_batch)
+        fwdbwd = self.engine.train_shared_dist_fwdbwd if self.distance else self.engine.train_shared_masked_fwdbwd
+        fwdbwd(global_batch, self.group_size, self.num_negs, ids, side, loss, s_filter=s_filter, o_filter=o_filter, identity=self.identity,
+               stats=self.stats_dev)
 
     def stats(self):
         """{"masked", "unmaskable"} since the bind -- the corruption scores set to -inf and the positives whose whole list was known
@@ -454,15 +474,11 @@ class KvsAll:
     KEY = "kvsall"
 
     def __init__(self, side="uniform", weight="triple", known=True, group_size=None):
-        if not isinstance(side, str) or side not in _ffi.NEG_SIDE_MODES:
-            raise ValueError("negatives: `side` must be 'uniform', 'bernoulli', 's' or 'o', got {!r}".format(side))
         if not isinstance(weight, str) or weight not in ("triple", "query"):
             raise ValueError("negatives: `weight` must be 'triple' or 'query', got {!r}".format(weight))
-        if not (known is True or (isinstance(known, dict) and len(known) > 0)):
-            raise ValueError("negatives: `known` must be True (the training set) or a non-empty dict of datasets known next to it")
         if group_size is not None and (isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer)) or not 1 <= int(group_size) <= 2 ** 31 - 1):
             raise ValueError("negatives: `group_size` must be None or an integer in [1, {}]".format(2 ** 31 - 1))
-        self.side, self.weight, self.known = side, weight, known
+        self.side, self.weight, self.known = check_side(side), weight, check_datasets(known, "known", allow_false=False)
         self.group_size = SharedNegatives.ALL_GROUP_SIZE if group_size is None else int(group_size)
 
     @classmethod
@@ -480,7 +496,7 @@ class KvsAll:
 
     def check_model(self, model, optimizer_mode="dense"):
         """compile()'s refusals: everything that is known before a GPU is touched (all five models take part)."""
-        SharedNegatives._check_modes(model, optimizer_mode)
+        check_shared_modes(model, optimizer_mode)
 
     @staticmethod
     def query_weights(train):
@@ -495,22 +511,11 @@ class KvsAll:
     def bind(self, model, engine, train):
         import torch
 
-        loop = getattr(model, "_loop", None)
-        if getattr(model, "use_focusE", False):
-            raise NotImplementedError("negatives: FocusE is not offered with shared negatives")
-        if getattr(loop, "multi", False):
-            raise NotImplementedError("negatives: shared negatives run on one rank only")
-        if getattr(loop, "deterministic", False):
-            raise NotImplementedError("negatives: shared negatives accumulate in no fixed order; deterministic mode is not offered")
-        N, R = int(model._n_ents), int(model._n_rels)
+        refuse_modes(*SHARED_STEP, **fit_modes(model))
+        N = int(model._n_ents)
         if N > _ffi.SHARED_MAX_NEGS:
             raise ValueError("negatives: KvsAll needs at most {} entities".format(_ffi.SHARED_MAX_NEGS))
-        extra = []
-        if isinstance(self.known, dict):
-            from .models import _load_triples
-
-            extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in self.known.values()]
-        index = FilterIndex([train] + extra, N, R, engine=engine)
+        index = known_index(model, engine, train, self.known)
         side_thr = None
         if self.side == "bernoulli":
             side_thr = engine.negatives_side_thresholds(*index.device_keys(engine), index.n_ents, index.n_rels)
@@ -518,30 +523,36 @@ class KvsAll:
         if self.weight == "query":   # both arrays once, in numpy
             weights = tuple(torch.as_tensor(w).to(engine.device) for w in self.query_weights(train.cpu().numpy()))
         all_list = torch.arange(N, dtype=torch.int32, device=engine.device)
-        bound = BoundKvsAll(engine, N, self.group_size, self.side, side_thr, None, all_list=all_list, train=train, index=index, identity=True,
-                            weights=weights)
-        bound.distance = model.scoring_type in ("TransE", "RotatE")   # trainer.StepLoop.step: engine.train_shared_dist_labels_fwdbwd
-        return bound
+        return BoundKvsAll(engine, N, self.group_size, self.side, side_thr, None, all_list=all_list, train=train, index=index, identity=True,
+                           weights=weights, distance=model.scoring_type in ("TransE", "RotatE"))
 
 
 class BoundKvsAll(BoundMaskedSharedNegatives):
     """A KvsAll bound to one fit(): BoundMaskedSharedNegatives' index and range arrays (mask(global_batch) slices them: here they
     are the LABELS), the all-entities list, and the row weights of weight="query" (weights(global_batch) slices them).
-    trainer.StepLoop.step hands them to engine.train_shared_labels_fwdbwd / train_shared_dist_labels_fwdbwd."""
+    step() hands them to engine.train_shared_labels_fwdbwd, or with distance=True (TransE, RotatE) to train_shared_dist_labels_fwdbwd."""
 
-    labelled = True
+    labelled = True   # what trainer.StepLoop.step pairs with loss_functions.BCELoss
 
-    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity, weights=None):
-        super().__init__(engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity)
+    def __init__(self, engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity, weights=None, distance=False):
+        super().__init__(engine, num_negs, group_size, side, side_thr, pool, all_list, train, index, identity, distance=distance)
         self.row_weights = weights
 
     def weights(self, global_batch):
         """-> None or (w_s, w_o) of the batch's rows"""
         if self.row_weights is None:
             return None
-        r0 = BoundNegatives._first_row(self, global_batch)
-        r1 = r0 + int(global_batch.shape[0])
-        return tuple(w[r0:r1] for w in self.row_weights)
+        rows = batch_slice(self.train, global_batch)
+        return tuple(w[rows] for w in self.row_weights)
+
+    def step(self, global_batch, loss, seed, rng_step):
+        """loss: the BCELoss object -- the labelled entry points take its two hyper-parameters as arguments"""
+        ids, side = self.draw(global_batch, seed, rng_step)
+        s_filter, o_filter = self.mask(global_batch)
+        lp = loss._loss_parameters
+        fwdbwd = self.engine.train_shared_dist_labels_fwdbwd if self.distance else self.engine.train_shared_labels_fwdbwd
+        fwdbwd(global_batch, self.group_size, self.num_negs, ids, side, s_filter, o_filter, label_smoothing=lp["label_smoothing"],
+               reduction=lp["reduction"], weights=self.weights(global_batch), identity=self.identity, stats=self.stats_dev)
 
     def stats(self):
         """{"labelled", "unlabelled_rows"} since the bind -- the entries labelled 1 and the rows without one: one device read

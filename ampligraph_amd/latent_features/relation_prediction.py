@@ -13,7 +13,9 @@ import math
 import numpy as np
 
 from ..datasets.filters import PairFilterIndex
+from ..trainer import RELATION_TERM, fit_modes, refuse_modes
 from . import loss_functions
+from .negatives import check_datasets, known_index
 
 
 class RelationPrediction:
@@ -40,9 +42,7 @@ class RelationPrediction:
         if getattr(self.loss, "labelled", False):
             raise ValueError("relation_prediction: BCELoss is the loss of KvsAll training over entities; a binary cross-entropy over "
                              "relations was not built")
-        if not (isinstance(known, (bool, np.bool_)) or (isinstance(known, dict) and len(known) > 0)):
-            raise ValueError("relation_prediction: `known` must be False, True or a non-empty dict of datasets")
-        self.known = known if isinstance(known, dict) else bool(known)
+        self.known = check_datasets(known, "known", who="relation_prediction")
 
     @classmethod
     def get(cls, spec):
@@ -65,34 +65,12 @@ class RelationPrediction:
         if model.scoring_type not in ("DistMult", "ComplEx", "HolE"):
             raise NotImplementedError("relation_prediction: the term needs a score that is linear in the relation row (DistMult, ComplEx, "
                                       "HolE); {} scores a distance".format(model.scoring_type))
-        if model._deterministic:
-            raise NotImplementedError("relation_prediction: its gradient rows are added with atomics, in no fixed order; "
-                                      "deterministic=True is not offered")
-        if optimizer_mode == "lazy":
-            raise NotImplementedError("relation_prediction: optimizer_mode='lazy' was not built for it")
-        if model._sharding != "replicated":
-            raise NotImplementedError("relation_prediction: entity_sharding='{}' was not built for it; use replicated tables on one "
-                                      "GPU".format(model._sharding))
-        if model._dist() is not None:
-            raise NotImplementedError("relation_prediction: it runs on one rank only")
+        refuse_modes(*RELATION_TERM, multi=model._dist() is not None, deterministic=model._deterministic, lazy=optimizer_mode == "lazy",
+                     sharding=model._sharding)
 
     def bind(self, model, engine, train):
-        if getattr(model, "use_focusE", False):
-            raise NotImplementedError("relation_prediction: FocusE is not offered with the relation objective")
-        loop = getattr(model, "_loop", None)
-        if getattr(loop, "multi", False):
-            raise NotImplementedError("relation_prediction: it runs on one rank only")
-        if getattr(loop, "deterministic", False):
-            raise NotImplementedError("relation_prediction: its gradient rows are added with atomics, in no fixed order; deterministic mode "
-                                      "is not offered")
-        index = None
-        if self.known is not False:
-            extra = []
-            if isinstance(self.known, dict):
-                from .models import _load_triples
-
-                extra = [model.data_indexer.get_indexes(_load_triples(v)[:, :3]) for v in self.known.values()]
-            index = PairFilterIndex([train] + extra, int(model._n_ents), int(model._n_rels), engine=engine)
+        refuse_modes(*RELATION_TERM, **fit_modes(model))
+        index = known_index(model, engine, train, self.known, PairFilterIndex) if self.known is not False else None
         return BoundRelationPrediction(engine, self.weight, self.loss.to_ffi(), index)
 
 

@@ -20,6 +20,35 @@ def shard_bounds(n, world, rank):
     return lo, hi
 
 
+# The three features that own a part of the step -- each a (message prefix, reason clause) -- and the modes they were not built for.
+# Whoever can see a mode asks refuse_modes: compile() (latent_features/models.py, negatives.py, relation_prediction.py), bind() /
+# fit() through fit_modes(model), and StepLoop.step.
+SHARED_STEP = ("negatives", "a shared-list step (SharedNegatives, SharedDistanceNegatives, KvsAll) accumulates its gradients in no fixed "
+                            "order and ends in one rank's dense sweep")
+BATCH_REG = ("batch regularizer", "its gradient rows are added with atomics, in no fixed order, into one rank's dense gradient")
+RELATION_TERM = ("relation_prediction", "its gradient rows are added with atomics, in no fixed order, into one rank's dense gradient")
+
+
+def refuse_modes(prefix, reason, focus=False, multi=False, deterministic=False, lazy=False, sharding="replicated"):
+    """Raise NotImplementedError("<prefix>: <reason>; not offered with <the modes that are on>") when any of the given modes is on:
+    focus (FocusE), multi (more than one rank), deterministic, lazy (optimizer_mode='lazy'), sharding (entity_sharding other than
+    "replicated").  A caller passes the modes it can see and the feature does not run under."""
+    if not (focus or multi or deterministic or lazy or sharding != "replicated"):
+        return
+    on = [name for flag, name in ((focus, "FocusE"), (multi, "more than one rank"), (deterministic, "deterministic mode"),
+                                  (lazy, "optimizer_mode='lazy'"), (sharding != "replicated", "entity_sharding='{}' (sharded tables)".format(sharding)))
+          if flag]
+    raise NotImplementedError("{}: {}; not offered with {}".format(prefix, reason, ", ".join(on)))
+
+
+def fit_modes(model):
+    """The modes refuse_modes can be asked about once fit() has a loop: what bind() of a sampler or of the relation term, and fit()
+    itself for a batch regulariser, pass on."""
+    loop = getattr(model, "_loop", None)
+    return dict(focus=bool(getattr(model, "use_focusE", False)), multi=bool(getattr(loop, "multi", False)),
+                deterministic=bool(getattr(loop, "deterministic", False)))
+
+
 def prefer_tiled(engine):
     """Which fused train path a loop should use when the shape allows both.  Owner-computes (kge_train_tiled.hip)
     wins 2.2x for the trilinear models (single pass over the rows, no global atomics).  TransE / RotatE read the rows
@@ -126,13 +155,14 @@ class StepLoop:
         # read once here.  Needs the owner-computes path (any k <= 2048); the merged DP sweep already sums in rank order.
         self.deterministic = os.environ.get("AMDKGE_DETERMINISTIC", "0") == "1"
         self.kernel_hook = None   # bench.py: callable(i) recording HIP events at the phase boundaries (PHASES)
-        # compile(negatives=...): None (the train kernels draw their own corruptions) or a callable(global_batch, lo, hi, eta, seed,
-        # rng_step) -> int32 device rows [(hi - lo) * eta, 3], the corruptions of rows [lo, hi) of the global batch drawn by GLOBAL
-        # row (latent_features/negatives.py: BoundNegatives), which the step hands to the train kernels as their override; or an object
-        # with `.shared` set (BoundSharedNegatives: .draw(), .group_size, .num_negs), whose step is engine.train_shared_fwdbwd -- or, when
-        # it has a .mask() (BoundMaskedSharedNegatives), engine.train_shared_masked_fwdbwd; with `.distance` set too
-        # (SharedDistanceNegatives: TransE, RotatE) both are engine.train_shared_dist_fwdbwd; with `.labelled` set (BoundKvsAll, with
-        # loss_functions.BCELoss) engine.train_shared_labels_fwdbwd / train_shared_dist_labels_fwdbwd
+        # compile(negatives=...) bound by fit(): None (the train kernels draw their own corruptions) or one of two kinds of bound sampler
+        # (latent_features/negatives.py; DESIGN.md "What a bound sampler provides"):
+        #   an OVERRIDE sampler (BoundNegatives, BoundTypedNegatives): a callable(global_batch, lo, hi, eta, seed, rng_step) -> int32 device
+        #     rows [(hi - lo) * eta, 3], the corruptions of rows [lo, hi) of the global batch drawn by GLOBAL row, which the step hands to
+        #     the train kernels as their neg_override; the loop reads nothing else of it;
+        #   a sampler that OWNS the backward call (`shared` set: BoundSharedNegatives, BoundMaskedSharedNegatives, BoundKvsAll):
+        #     step(global_batch, loss, seed, rng_step) draws and runs its own engine.train_shared*_fwdbwd; the loop reads `shared` and,
+        #     for the loss <-> sampler pairing (BCELoss exists only with KvsAll), `labelled`.
         self.negatives = None
         # compile(relation_prediction=...): None or an object with .step(batch) (latent_features/relation_prediction.py:
         # BoundRelationPrediction), the relation-prediction term -- engine.train_relation_fwdbwd on the batch, between the backward call
@@ -165,108 +195,76 @@ class StepLoop:
     def step(self, global_batch, rng_step, focus=None):
         """global_batch: (Bg,3) int32 device tensor holding the WHOLE batch (same on every rank);
         rng_step: the step counter the negatives are keyed by; focus: None or (w fp32 device tensor [Bg], beta,
-        non-linearity name) for FocusE (ScoringBasedEmbeddingModel.py:396-406)."""
-        eng = self.engine
+        non-linearity name) for FocusE (ScoringBasedEmbeddingModel.py:396-406).
+
+        Pairing check and refusals -> the optimizer's clock and the descriptors -> hook 0 -> ONE backward call (the sampler's own
+        step, the owner-computes step, or train_fwdbwd) -> the dense extras (relation term, batch regulariser) -> hook 1 -> merge
+        and / or sweep -> hook 2.  Everything that can refuse a step does so before anything is touched."""
+        eng, neg, relation = self.engine, self.negatives, self.relation
         bg = int(global_batch.shape[0])
         lo, hi = shard_bounds(bg, self.world, self.rank)
+        labelled = getattr(neg, "labelled", False)
         if self.label_loss is not None:
-            if focus is not None or not getattr(self.negatives, "labelled", False):
+            if focus is not None or not labelled:
                 raise NotImplementedError("BCELoss is the loss of the labelled shared step: it needs compile(negatives=KvsAll(...)) and takes no FocusE")
-        elif getattr(self.negatives, "labelled", False):
+        elif labelled:
             raise NotImplementedError("KvsAll labels every entity for a binary cross-entropy: it needs loss=BCELoss(...)")
-        elif focus is not None:
-            from . import _ffi
-
-            fw = focus[0][lo:hi].contiguous()   # kept alive until the launches below are enqueued
-            self.loss_ffi.focus_nonlinearity = _ffi.FOCUS_NONLINEARITY[focus[2]]
-            self.loss_ffi.focus_beta = float(focus[1])
-            self.loss_ffi.d_focus_w = fw.data_ptr()
-        else:
-            self.loss_ffi.focus_nonlinearity = 0
-            self.loss_ffi.d_focus_w = None
-        self.optimizer.iterations += 1
         lam = self.reg    # LPRegularizer objects (or None): the engine turns them into the descriptor's (p, lambda) terms
         lam_r = self.reg if isinstance(self.reg_rel, str) else self.reg_rel
-        opt_ffi = self.optimizer.to_ffi(self.optimizer.iterations, 2)
         # BatchLPRegularizer members (N3, per-occurrence Lp: include/amdkge_batch_reg.h) act on the rows of this step's positives:
         # engine.batch_reg_fwdbwd between the backward call and the dense sweep, which then takes only the whole-table members
         breg_e = lam if getattr(lam, "batch", False) else None
         breg_r = lam_r if getattr(lam_r, "batch", False) else None
         batch_reg = breg_e is not None or breg_r is not None
         if batch_reg:
-            if focus is not None or self.multi or self.deterministic or getattr(self.optimizer, "lazy", False):
-                raise NotImplementedError("batch regularizer: its row-adds are unordered atomics (no deterministic mode); FocusE, "
-                                          "optimizer_mode='lazy' and more than one rank were not built")
+            refuse_modes(*BATCH_REG, focus is not None, self.multi, self.deterministic, getattr(self.optimizer, "lazy", False))
             lam = None if breg_e is not None else lam
             lam_r = None if breg_r is not None else lam_r
-        relation = self.relation
-        if relation is not None and (focus is not None or self.multi or self.deterministic or getattr(self.optimizer, "lazy", False)):
-            raise NotImplementedError("relation_prediction: its row-adds are unordered atomics (no deterministic mode); FocusE, "
-                                      "optimizer_mode='lazy' and more than one rank were not built")
-        if getattr(self.negatives, "shared", False):
-            # SharedNegatives: draw -> matrix-product forward / backward (kge_train_shared.hip) -> dense sweep.  Every other
-            # configuration runs the code below.
-            if focus is not None or self.multi or self.deterministic:
-                raise NotImplementedError("shared negatives: no FocusE, no deterministic mode, one rank only")
-            if self.kernel_hook is not None:
-                self.kernel_hook(0)
-            if bg > 0:
-                sh = self.negatives
-                ids, side = sh.draw(global_batch, self.seed, rng_step)
-                mask = getattr(sh, "mask", None)   # BoundMaskedSharedNegatives: known statements score -inf (kge_train_shared.hip, shared_mask_kernel)
-                if getattr(sh, "labelled", False):   # KvsAll: labels + BCE in one pass over a chunk's scores (kge_train_shared_labels.hip)
-                    s_filter, o_filter = mask(global_batch)
-                    lp = self.label_loss._loss_parameters
-                    step_fn = eng.train_shared_dist_labels_fwdbwd if getattr(sh, "distance", False) else eng.train_shared_labels_fwdbwd
-                    step_fn(global_batch, sh.group_size, sh.num_negs, ids, side, s_filter, o_filter, label_smoothing=lp["label_smoothing"],
-                            reduction=lp["reduction"], weights=sh.weights(global_batch), identity=bool(getattr(sh, "identity", False)),
-                            stats=getattr(sh, "stats_dev", None))
-                elif getattr(sh, "distance", False):   # SharedDistanceNegatives: distance tiles (kge_train_shared_dist.hip), one entry point for both
-                    kw = {}
-                    if mask is not None:
-                        s_filter, o_filter = mask(global_batch)
-                        kw = dict(s_filter=s_filter, o_filter=o_filter, identity=bool(getattr(sh, "identity", False)), stats=getattr(sh, "stats_dev", None))
-                    eng.train_shared_dist_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi, **kw)
-                elif mask is None:
-                    eng.train_shared_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi)
-                else:
-                    s_filter, o_filter = mask(global_batch)
-                    eng.train_shared_masked_fwdbwd(global_batch, sh.group_size, sh.num_negs, ids, side, self.loss_ffi, s_filter=s_filter, o_filter=o_filter,
-                                                   identity=bool(getattr(sh, "identity", False)), stats=getattr(sh, "stats_dev", None))
-                if relation is not None:
-                    relation.step(global_batch)
-                if batch_reg:
-                    eng.batch_reg_fwdbwd(global_batch, breg_e, breg_r)
-            if self.kernel_hook is not None:
-                self.kernel_hook(1)
-            eng.opt_step(opt_ffi, lam, lam_r)
-            if self.kernel_hook is not None:
-                self.kernel_hook(2)
-            self.n_steps += 1
-            return
+        if relation is not None:
+            refuse_modes(*RELATION_TERM, focus is not None, self.multi, self.deterministic, getattr(self.optimizer, "lazy", False))
+        owns = getattr(neg, "shared", False)   # the sampler runs the backward call itself (kge_train_shared*.hip), on the whole batch
+        if owns:
+            refuse_modes(*SHARED_STEP, focus is not None, self.multi, self.deterministic)
         # owner-computes path (kge_train_tiled.hip) whenever the shape allows it: no global atomics, no dense
         # entity gradient; data-parallel runs take its gradient-only form and keep the dense sweep
         # (a batch regulariser and the relation-prediction term need the dense entity gradient, which the owner-computes step never
         # materialises)
-        tiled = (self.use_tiled or self.deterministic) and not batch_reg and relation is None and hi > lo and eng.tiled_supported(hi - lo, self.eta)
+        tiled = (not owns and (self.use_tiled or self.deterministic) and not batch_reg and relation is None and hi > lo
+                 and eng.tiled_supported(hi - lo, self.eta))
         if self.deterministic and hi > lo and not tiled:
             raise ValueError("deterministic mode needs the owner-computes train path (k <= 2048)")
+        self.optimizer.iterations += 1
+        if focus is not None:
+            from . import _ffi
+
+            fw = focus[0][lo:hi].contiguous()   # kept alive until the launches below are enqueued
+            self.loss_ffi.focus_nonlinearity = _ffi.FOCUS_NONLINEARITY[focus[2]]
+            self.loss_ffi.focus_beta = float(focus[1])
+            self.loss_ffi.d_focus_w = fw.data_ptr()
+        elif self.loss_ffi is not None:
+            self.loss_ffi.focus_nonlinearity = 0
+            self.loss_ffi.d_focus_w = None
+        opt_ffi = self.optimizer.to_ffi(self.optimizer.iterations, 2)
         if self.kernel_hook is not None:
             self.kernel_hook(0)
-        # (the override keyword is only passed when a sampler is set: backends without it keep working)
-        neg = {"neg_override": self.negatives(global_batch, lo, hi, self.eta, self.seed, rng_step)} if self.negatives is not None and hi > lo else {}
-        if tiled:
-            eng.train_step_tiled(global_batch[lo:hi], self.eta, self.loss_ffi, opt_ffi, self.seed, rng_step,
-                                 reg_e=lam, reg_r=lam_r, row_offset=lo, b_global=bg, grad_only=self.multi,
-                                 pos_atomic=self.pos_atomic, **neg,
-                                 **({"deterministic": True, **({"det_wide": True} if getattr(self, "det_wide", False) else {})} if self.deterministic else {}))
-        elif hi > lo:
-            eng.train_fwdbwd(global_batch[lo:hi], self.eta, self.loss_ffi, self.seed, rng_step,
-                             row_offset=lo, b_global=bg, **neg)
-            if relation is not None:
-                relation.step(global_batch[lo:hi])
-            if batch_reg:
-                eng.batch_reg_fwdbwd(global_batch[lo:hi], breg_e, breg_r)
+        rows, n_rows = (global_batch, bg) if owns else (global_batch[lo:hi], hi - lo)   # what this rank's backward call and extras work on
+        if owns and n_rows > 0:
+            neg.step(rows, self.label_loss if labelled else self.loss_ffi, self.seed, rng_step)
+        elif n_rows > 0:
+            # (the override keyword is only passed when a sampler is set: backends without it keep working)
+            over = {"neg_override": neg(global_batch, lo, hi, self.eta, self.seed, rng_step)} if neg is not None else {}
+            if tiled:
+                eng.train_step_tiled(rows, self.eta, self.loss_ffi, opt_ffi, self.seed, rng_step,
+                                     reg_e=lam, reg_r=lam_r, row_offset=lo, b_global=bg, grad_only=self.multi,
+                                     pos_atomic=self.pos_atomic, **over,
+                                     **({"deterministic": True, **({"det_wide": True} if getattr(self, "det_wide", False) else {})} if self.deterministic else {}))
+            else:
+                eng.train_fwdbwd(rows, self.eta, self.loss_ffi, self.seed, rng_step, row_offset=lo, b_global=bg, **over)
+        # the dense extras (never next to the owner-computes step: tiled is off with either)
+        if relation is not None and n_rows > 0:
+            relation.step(rows)
+        if batch_reg and n_rows > 0:
+            eng.batch_reg_fwdbwd(rows, breg_e, breg_r)
         if self.kernel_hook is not None:
             self.kernel_hook(1)
         if self.multi and self.merge == "sharded":

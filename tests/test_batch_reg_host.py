@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import batch_reg_ref as BR
+from bound_samplers import bound
 from ampligraph_amd.latent_features import ScoringBasedEmbeddingModel, loss_functions, optimizers, regularizers
 from ampligraph_amd.latent_features.regularizers import BatchLPRegularizer, LPRegularizer
 
@@ -237,14 +238,8 @@ class _RecordingEngine:
         self.calls.append(("opt_step", reg_e, reg_r))
 
 
-class _Shared:
-    shared, group_size, num_negs = True, 4, 3
-
-    def draw(self, batch, seed, step):
-        return None, None
-
-
-def _loop(reg, reg_rel="same", negatives=None, **opt_kw):
+def _loop(reg, reg_rel="same", shared=False, **opt_kw):
+    """shared: whether the loop gets a BoundSharedNegatives (tests/bound_samplers.py)"""
     import torch
 
     from ampligraph_amd.trainer import StepLoop
@@ -252,7 +247,7 @@ def _loop(reg, reg_rel="same", negatives=None, **opt_kw):
     eng = _RecordingEngine()
     loop = StepLoop(eng, 2, loss_functions.get("nll"), optimizers.get("sgd", opt_kw), reg, seed=0, dist=None)
     loop.reg_rel = reg_rel
-    loop.negatives = negatives
+    loop.negatives = bound(eng, "shared") if shared else None
     return loop, eng, torch.zeros(6, 3, dtype=torch.int32)
 
 
@@ -263,7 +258,7 @@ def test_step_without_a_batch_member_makes_todays_calls(monkeypatch):
     loop, eng, X = _loop(lp)
     loop.step(X, 0)
     assert eng.calls == [("train_step_tiled", lp, lp)]
-    loop, eng, X = _loop(lp, reg_rel=None, negatives=_Shared())
+    loop, eng, X = _loop(lp, reg_rel=None, shared=True)
     loop.step(X, 0)
     assert eng.calls == [("train_shared_fwdbwd",), ("opt_step", lp, None)]
 
@@ -273,7 +268,7 @@ def test_step_with_a_batch_member(monkeypatch):
     monkeypatch.delenv("AMDKGE_DETERMINISTIC", raising=False)
     n3, lp = BatchLPRegularizer(3, 0.25), LPRegularizer(2, 0.5)
     # shared branch: forward / backward, the batch regulariser, the sweep -- which takes the whole-table member only
-    loop, eng, X = _loop(n3, reg_rel=lp, negatives=_Shared())
+    loop, eng, X = _loop(n3, reg_rel=lp, shared=True)
     loop.step(X, 0)
     assert eng.calls == [("train_shared_fwdbwd",), ("batch_reg_fwdbwd", 6, n3, None), ("opt_step", None, lp)]
     # per-corruption branch: the dense-gradient form, never the owner-computes step

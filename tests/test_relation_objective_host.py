@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import relation_objective_ref as RR
+from bound_samplers import bound
 from ampligraph_amd.latent_features import RelationPrediction, ScoringBasedEmbeddingModel, loss_functions, optimizers
 from ampligraph_amd.latent_features.regularizers import BatchLPRegularizer, LPRegularizer
 from oracle import kge_oracle as O
@@ -176,7 +177,7 @@ def test_bind_refuses_focuse():
 # ------------------------------------------------------------------------------------------------ what the step loop calls
 class _RecordingEngine:
     """the surface trainer.StepLoop uses on one rank, recording the order of the calls"""
-    scoring_type, k = "ComplEx", 8
+    scoring_type, k, device = "ComplEx", 8, "cpu"
 
     def __init__(self):
         self.calls = []
@@ -215,19 +216,6 @@ class _RecordingEngine:
         self.calls.append(("opt_step",))
 
 
-class _Shared:
-    shared, group_size, num_negs = True, 4, 3
-
-    def __init__(self, **attrs):
-        self.__dict__.update(attrs)
-
-    def draw(self, batch, seed, step):
-        return None, None
-
-    def weights(self, batch):
-        return None
-
-
 class _Term:
     """BoundRelationPrediction without a device: step(batch) -> engine.train_relation_fwdbwd"""
 
@@ -239,11 +227,12 @@ class _Term:
 
 
 def _loop(reg=None, negatives=None, term=True, loss="nll", **opt_kw):
+    """negatives: None or the arguments of bound() (tests/bound_samplers.py) behind the engine"""
     from ampligraph_amd.trainer import StepLoop
 
     eng = _RecordingEngine()
     loop = StepLoop(eng, 2, loss_functions.get(loss), optimizers.get("sgd", opt_kw), reg, seed=0, dist=None)
-    loop.negatives = negatives
+    loop.negatives = None if negatives is None else bound(eng, **negatives)
     assert loop.relation is None
     if term:
         loop.relation = _Term(eng)
@@ -251,14 +240,13 @@ def _loop(reg=None, negatives=None, term=True, loss="nll", **opt_kw):
 
 
 REL = ("train_relation_fwdbwd", 6, 0.25, True)
-_mask = lambda batch: (None, None)   # noqa: E731
 
 
 @pytest.mark.parametrize("name,negatives,loss,main", [
-    ("shared", lambda: _Shared(), "nll", "train_shared_fwdbwd"),
-    ("masked", lambda: _Shared(mask=_mask), "nll", "train_shared_masked_fwdbwd"),
-    ("distance", lambda: _Shared(distance=True), "nll", "train_shared_dist_fwdbwd"),
-    ("kvsall", lambda: _Shared(labelled=True, mask=_mask), loss_functions.BCELoss(), "train_shared_labels_fwdbwd"),
+    ("shared", lambda: dict(kind="shared"), "nll", "train_shared_fwdbwd"),
+    ("masked", lambda: dict(kind="masked"), "nll", "train_shared_masked_fwdbwd"),
+    ("distance", lambda: dict(kind="shared", distance=True), "nll", "train_shared_dist_fwdbwd"),
+    ("kvsall", lambda: dict(kind="kvsall"), loss_functions.BCELoss(), "train_shared_labels_fwdbwd"),
     ("per-corruption", lambda: None, "nll", "train_fwdbwd")])
 def test_step_order(monkeypatch, name, negatives, loss, main):
     """main step -> relation term -> batch regulariser (if any) -> opt_step, on every branch; the per-corruption branch takes the

@@ -11,6 +11,7 @@ import pytest
 
 import shared_dist_ref as DR
 import shared_ref as SR
+from bound_samplers import bound
 from oracle import kge_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -211,7 +212,7 @@ def test_step_loop_takes_the_distance_call_only_for_a_distance_sampler():
     calls = []
 
     class Eng:
-        scoring_type, k = "TransE", 8
+        scoring_type, k, device = "TransE", 8, "cpu"
 
         def prepare_training(self, name):
             pass
@@ -228,45 +229,25 @@ def test_step_loop_takes_the_distance_call_only_for_a_distance_sampler():
         def opt_step(self, *a):
             calls.append(("opt",))
 
-    class Bound:
-        shared, group_size, num_negs = True, 4, 6
-
-        def draw(self, batch, seed, step):
-            calls.append(("draw", tuple(batch.shape), seed, step))
-            return "ids", "side"
-
-    class Masked(Bound):
-        identity, stats_dev = True, "stats"
-
-        def mask(self, batch):
-            calls.append(("mask", tuple(batch.shape)))
-            return "sf", "of"
-
-    class Dist(Bound):
-        distance = True
-
-    class DistMasked(Masked):
-        distance = True
-
     loop = StepLoop(Eng(), 3, loss_functions.get("nll"), optimizers.get("adam"), None, seed=5, dist=None)
     batch = torch.zeros(10, 3, dtype=torch.int32)
-    loop.negatives = Dist()
+    loop.negatives = bound(loop.engine, "shared", calls, distance=True)
     loop.step(batch, 7)
     assert calls == [("draw", (10, 3), 5, 7), ("dist", (10, 3), 4, 6, "ids", "side", {}), ("opt",)]
     del calls[:]
-    loop.negatives = DistMasked()
+    loop.negatives = bound(loop.engine, "masked", calls, distance=True)
     loop.step(batch, 8)
     assert calls == [("draw", (10, 3), 5, 8), ("mask", (10, 3)),
                      ("dist", (10, 3), 4, 6, "ids", "side", dict(s_filter="sf", o_filter="of", identity=True, stats="stats")), ("opt",)]
     del calls[:]
-    loop.negatives = Bound()                                                   # a sampler without the attribute: exactly today's calls
+    loop.negatives = bound(loop.engine, "shared", calls)                                                   # a sampler without the attribute: exactly today's calls
     loop.step(batch, 9)
     assert calls == [("draw", (10, 3), 5, 9), ("shared", (10, 3), 4, 6, "ids", "side"), ("opt",)]
     del calls[:]
-    loop.negatives = Masked()
+    loop.negatives = bound(loop.engine, "masked", calls)
     loop.step(batch, 10)
     assert calls == [("draw", (10, 3), 5, 10), ("mask", (10, 3)), ("masked", (10, 3), 4, 6, "ids", "side", "sf", "of", True, "stats"), ("opt",)] and loop.n_steps == 4
-    loop.negatives = Dist()
+    loop.negatives = bound(loop.engine, "shared", calls, distance=True)
     with pytest.raises(NotImplementedError, match="FocusE"):
         loop.step(batch, 11, focus=(torch.zeros(10), 0.5, "linear"))
     loop.deterministic = True

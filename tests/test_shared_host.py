@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import shared_ref as SR
+from bound_samplers import bound
 from oracle import kge_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -240,15 +241,8 @@ def test_step_loop_takes_the_shared_path_and_refuses_focus_ranks_and_determinism
         def opt_step(self, *a):
             calls.append(("opt",))
 
-    class Bound:
-        shared, group_size, num_negs = True, 4, 6
-
-        def draw(self, batch, seed, step):
-            calls.append(("draw", tuple(batch.shape), seed, step))
-            return "ids", "side"
-
     loop = StepLoop(Eng(), 3, loss_functions.get("nll"), optimizers.get("adam"), None, seed=5, dist=None)
-    loop.negatives = Bound()
+    loop.negatives = bound(loop.engine, "shared", calls)
     batch = torch.zeros(10, 3, dtype=torch.int32)
     loop.step(batch, 7)
     assert calls == [("draw", (10, 3), 5, 7), ("shared", (10, 3), 4, 6, "ids", "side"), ("opt",)] and loop.n_steps == 1

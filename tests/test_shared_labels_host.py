@@ -11,6 +11,7 @@ import torch
 import shared_labels_ref as LR
 import shared_mask_ref as MR
 import shared_ref as SR
+from bound_samplers import bound
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "ampligraph_amd", "lib", "libamdkge.so")
@@ -286,7 +287,7 @@ def test_argument_checks_return_before_touching_a_device(built):
 # ------------------------------------------------------------------------------------------------ 5. what the step loop calls
 class _RecordingEngine:
     """the surface trainer.StepLoop uses on one rank in the shared branch, recording the calls"""
-    scoring_type, k = "ComplEx", 8
+    scoring_type, k, device = "ComplEx", 8, "cpu"
 
     def __init__(self):
         self.calls = []
@@ -310,29 +311,14 @@ class _RecordingEngine:
         self.calls.append(("opt_step", reg_e, reg_r))
 
 
-class _Bound:
-    shared, labelled, group_size, num_negs, identity, stats_dev, distance = True, True, 4, 9, True, "stats", False
-
-    def __init__(self, weights=None):
-        self.w = weights
-
-    def draw(self, batch, seed, step):
-        return "ids", "side"
-
-    def mask(self, batch):
-        return "sf", "of"
-
-    def weights(self, batch):
-        return self.w
-
-
-def _loop(loss, reg=None, negatives=None):
+def _loop(loss, reg=None, negatives=False, **bound_kw):
+    """negatives: whether the loop gets a BoundKvsAll (tests/bound_samplers.py; bound_kw: its weights / distance)"""
     from ampligraph_amd.latent_features import optimizers
     from ampligraph_amd.trainer import StepLoop
 
     eng = _RecordingEngine()
     loop = StepLoop(eng, 2, loss, optimizers.get("sgd"), reg, seed=0, dist=None)
-    loop.negatives = negatives
+    loop.negatives = bound(eng, "kvsall", num_negs=9, **bound_kw) if negatives else None
     return loop, eng, torch.zeros(6, 3, dtype=torch.int32)
 
 
@@ -343,26 +329,24 @@ def test_the_calls_of_one_step(monkeypatch):
     monkeypatch.delenv("AMDKGE_DETERMINISTIC", raising=False)
     bce = BCELoss({"label_smoothing": 0.1, "reduction": "mean"})
     kw = dict(label_smoothing=0.1, reduction="mean", weights=None, identity=True, stats="stats")
-    loop, eng, X = _loop(bce, negatives=_Bound())
+    loop, eng, X = _loop(bce, negatives=True)
     assert loop.loss_ffi is None and loop.label_loss is bce
     loop.step(X, 0)
     assert eng.calls == [("train_shared_labels_fwdbwd", 4, 9, "sf", "of", kw), ("opt_step", None, None)]
     # the distance models; the row weights; N3 between the backward call and the sweep
     n3 = BatchLPRegularizer(3, 0.25)
-    b = _Bound(weights=("ws", "wo"))
-    b.distance = True
-    loop, eng, X = _loop(bce, reg=n3, negatives=b)
+    loop, eng, X = _loop(bce, reg=n3, negatives=True, weights=("ws", "wo"), distance=True)
     loop.step(X, 0)
     assert eng.calls == [("train_shared_dist_labels_fwdbwd", 4, 9, "sf", "of", dict(kw, weights=("ws", "wo"))), ("batch_reg_fwdbwd", 6, n3, n3),
                          ("opt_step", None, None)]
     # the two halves exist only together
-    loop, eng, X = _loop(bce, negatives=None)
+    loop, eng, X = _loop(bce)
     with pytest.raises(NotImplementedError, match="KvsAll"):
         loop.step(X, 0)
-    loop, eng, X = _loop(loss_functions.get("nll"), negatives=_Bound())
+    loop, eng, X = _loop(loss_functions.get("nll"), negatives=True)
     with pytest.raises(NotImplementedError, match="BCELoss"):
         loop.step(X, 0)
-    loop, eng, X = _loop(bce, negatives=_Bound())
+    loop, eng, X = _loop(bce, negatives=True)
     with pytest.raises(NotImplementedError, match="FocusE"):
         loop.step(X, 0, focus=(torch.ones(6), 0.5, "linear"))
     assert eng.calls == []

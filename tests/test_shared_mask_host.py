@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import shared_mask_ref as MR
+from bound_samplers import bound
 from oracle import kge_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -168,7 +169,7 @@ def test_step_loop_takes_the_masked_call_only_when_a_mask_is_bound():
     calls = []
 
     class Eng:
-        scoring_type, k = "ComplEx", 8
+        scoring_type, k, device = "ComplEx", 8, "cpu"
 
         def prepare_training(self, name):
             pass
@@ -182,30 +183,16 @@ def test_step_loop_takes_the_masked_call_only_when_a_mask_is_bound():
         def opt_step(self, *a):
             calls.append(("opt",))
 
-    class Bound:
-        shared, group_size, num_negs = True, 4, 6
-
-        def draw(self, batch, seed, step):
-            calls.append(("draw", tuple(batch.shape), seed, step))
-            return "ids", "side"
-
-    class Masked(Bound):
-        identity, stats_dev = True, "stats"
-
-        def mask(self, batch):
-            calls.append(("mask", tuple(batch.shape)))
-            return "sf", "of"
-
     loop = StepLoop(Eng(), 3, loss_functions.get("nll"), optimizers.get("adam"), None, seed=5, dist=None)
     batch = torch.zeros(10, 3, dtype=torch.int32)
-    loop.negatives = Masked()
+    loop.negatives = bound(loop.engine, "masked", calls)
     loop.step(batch, 7)
     assert calls == [("draw", (10, 3), 5, 7), ("mask", (10, 3)), ("masked", (10, 3), 4, 6, "ids", "side", "sf", "of", True, "stats"), ("opt",)]
     del calls[:]
-    loop.negatives = Bound()
+    loop.negatives = bound(loop.engine, "shared", calls)
     loop.step(batch, 8)
     assert calls == [("draw", (10, 3), 5, 8), ("shared", (10, 3), 4, 6, "ids", "side"), ("opt",)] and loop.n_steps == 2
-    loop.negatives = Masked()
+    loop.negatives = bound(loop.engine, "masked", calls)
     with pytest.raises(NotImplementedError, match="FocusE"):
         loop.step(batch, 9, focus=(torch.zeros(10), 0.5, "linear"))
     loop.deterministic = True
