@@ -16,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMDKGE_LIB") or os.path.join(_HERE, "lib", "libamdkge.so")   # AMDKGE_LIB: development builds
 ABI_VERSION = 5
 
-# enums of include/amdkge.h
+# error classes (the return values of the entry points), enums and flag bits of include/amdkge.h
+OK, EINVAL, EHIP, ERCCL, ENOMEM, EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 SCORING_TYPES = {"TransE": 0, "DistMult": 1, "ComplEx": 2, "HolE": 3, "RotatE": 4}
 LOSSES = {"pairwise": 0, "nll": 1, "absolute_margin": 2, "self_adversarial": 3, "multiclass_nll": 4}
 OPTIMIZERS = {"sgd": 0, "adagrad": 1, "adam": 2, "momentum": 3, "rmsprop": 4, "rmsprop_mom": 5, "adadelta": 6, "adamax": 7}
@@ -26,6 +27,15 @@ OPT_SLOTS = {"sgd": (), "adagrad": ("a",), "adam": ("m", "v"), "momentum": ("mom
 SIDE_S, SIDE_O = 1, 2
 RANK_STRATEGY = {"worst": 0, "best": 1, "middle": 2}
 FOCUS_NONLINEARITY = {"linear": 1, "tanh": 2, "sigmoid": 3, "softplus": 4}
+# AMDKGE_TILED_*: the flags of amdkge_train_step_tiled / amdkge_train_tiled_status, and what amdkge_session_config.flags holds
+TILED_POS_ATOMIC, TILED_DETERMINISTIC, TILED_HOT_ROWS, TILED_GIVEN_COEFFS, TILED_DET_WIDE_SORT = 1, 2, 4, 8, 16
+# AMDKGE_GROUP_*: the flags of amdkge_session_group_create_ex / _rows / _cols (ROWS and COLS are set by the library)
+GROUP_FORCE_RCCL, GROUP_ROWS, GROUP_GLOBAL_NEGATIVES, GROUP_COLS, GROUP_FORCE_THREADS = 1, 2, 4, 8, 16
+NEG_SIDE_MODES = {"uniform": 0, "bernoulli": 1, "s": 2, "o": 3}   # AMDKGE_NEG_SIDE_*, include/amdkge_negatives.h; amdkge_shared.h uses them too
+NEG_MAX_TRIES = 32
+SHARED_MAX_NEGS = (1 << 24) - 1                  # include/amdkge_shared.h
+SHARED_LIST_MODES = {"given": 0, "identity": 1}  # AMDKGE_SHARED_LIST_*, include/amdkge_shared_mask.h
+BATCH_REG_NORMS = {"float": 0, "modulus": 1}     # AMDKGE_BATCH_REG_*, include/amdkge_batch_reg.h
 
 
 class AmdKgeLibraryError(RuntimeError):
@@ -70,8 +80,11 @@ I64 = C.c_int64
 I32 = C.c_int32
 U64 = C.c_uint64
 
-# name -> (restype, argtypes): every symbol include/amdkge.h declares
-SIGNATURES = {
+# ABI: header -> {name: (restype, argtypes)}, every entry point the headers under include/ declare, the headers in the order they were
+# added.  This table is what lib() binds -- the package does not read include/ -- and tests/test_abi_host.py holds it, the four
+# Structures above and every constant of this module equal to the headers.  A new extension header is one more entry here.
+ABI = {}
+ABI["amdkge.h"] = {   # the frozen declaration set of ABI 5
     "amdkge_abi_version": (C.c_int, []),
     "amdkge_release_scratch": (C.c_int, []),
     "amdkge_set_rank_early": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -164,46 +177,46 @@ SIGNATURES = {
     "amdkge_session_group_rank": (C.c_int, [P, P, I64, P, P, P, P, P, I64, I32, I32, P]),
 }
 
-# name -> (restype, argtypes): every symbol the extension headers declare (include/amdkge_lists.h: entry points added to ABI 5
-# without changing one of include/amdkge.h's)
-EXT_SIGNATURES = {
+ABI["amdkge_lists.h"] = {   # ranking against per-triple candidate lists
     "amdkge_rank_lists_workspace_bytes": (I64, [C.POINTER(Model), I64]),
     "amdkge_rank_lists": (C.c_int, [C.POINTER(Model), P, P, I64, P, I64, I32, P, P, P, I64, P, P, P, P, P, P, P, P]),
 }
 
-# the same for include/amdkge_negatives.h (training negative samplers): a table of its own, EXT_SIGNATURES stays what it was
-NEG_SIDE_MODES = {"uniform": 0, "bernoulli": 1, "s": 2, "o": 3}
-NEG_MAX_TRIES = 32
-NEG_SIGNATURES = {
+ABI["amdkge_negatives.h"] = {   # training negative samplers
     "amdkge_sample_negatives": (C.c_int, [P, I64, I32, I64, I64, U64, U64, I64, I64, I32, P, P, I64, P, P, P, P, P, P, I32, P, P, P]),
     "amdkge_negatives_side_thresholds": (C.c_int, [P, I64, P, I64, I64, I64, P, P]),
 }
 
-# include/amdkge_shared.h (shared-negative training): again a table of its own.  The side modes are NEG_SIDE_MODES.
-SHARED_MAX_NEGS = (1 << 24) - 1
-SHARED_SIGNATURES = {
+ABI["amdkge_shared.h"] = {   # shared-negative training
     "amdkge_sample_shared": (C.c_int, [P, I64, I64, I32, I64, I64, U64, U64, I32, P, P, I64, P, P, P]),
     "amdkge_train_shared_workspace_bytes": (I64, [C.POINTER(Model), I64, I64, I32]),
     "amdkge_train_shared_fwdbwd": (C.c_int, [C.POINTER(Model), C.POINTER(Loss), P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P, P]),
 }
 
-# include/amdkge_shared_mask.h (shared negatives with known statements masked; the all-entities list): again a table of its own
-SHARED_LIST_MODES = {"given": 0, "identity": 1}
-SHARED_MASK_SIGNATURES = {
+ABI["amdkge_types.h"] = {   # type-constrained negatives and evaluation: per-relation domain / range sets
+    "amdkge_relation_sets_build": (C.c_int, [P, I64, I32, I64, I64, P, P, P, P, P, P]),
+    "amdkge_relation_sets_ranges": (C.c_int, [P, P, I64, P, I64, I64, I64, I64, P, P, P]),
+    "amdkge_sample_negatives_typed": (C.c_int, [P, I64, I32, I64, I64, U64, U64, I64, I64, I32, P, P, I64, P, P, P, P, P, P, I32, P, P,
+                                                P, P, P, P, P, P, P]),
+}
+
+ABI["amdkge_shared_mask.h"] = {   # shared negatives with known statements masked; the all-entities list
     "amdkge_shared_mask_scores": (C.c_int, [P, I64, I64, I64, I32, P, P, P, P, P, P, P, P, I32, P, P]),
     "amdkge_train_shared_masked_fwdbwd": (C.c_int, [C.POINTER(Model), C.POINTER(Loss), P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P,
                                                     P, P, P, P, P, P, I32, P, P]),
 }
 
-# include/amdkge_shared_dist.h (shared negatives for the distance models, TransE and RotatE, on distance tiles): again a table of its own
-SHARED_DIST_SIGNATURES = {
+ABI["amdkge_shared_dist.h"] = {   # shared negatives for the distance models, TransE and RotatE, on distance tiles
     "amdkge_train_shared_dist_workspace_bytes": (I64, [C.POINTER(Model), I64, I64, I32]),
     "amdkge_train_shared_dist_fwdbwd": (C.c_int, [C.POINTER(Model), C.POINTER(Loss), P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P,
                                                   P, P, P, P, P, P, I32, P, P]),
 }
 
-# include/amdkge_shared_labels.h (KvsAll on the shared step: binary cross-entropy with multi-hot labels): again a table of its own
-SHARED_LABELS_SIGNATURES = {
+ABI["amdkge_batch_reg.h"] = {   # batch regularisers: N3 and per-occurrence Lp on the rows of a step's positives
+    "amdkge_batch_reg_fwdbwd": (C.c_int, [C.POINTER(Model), P, P, P, I64, I32, C.c_float, I32, I32, C.c_float, I32, P, P, P, P]),
+}
+
+ABI["amdkge_shared_labels.h"] = {   # KvsAll on the shared step: binary cross-entropy with multi-hot labels
     "amdkge_shared_label_loss": (C.c_int, [P, I64, I64, I64, I32, P, P, P, P, P, P, P, P, I32, C.c_float, I32, C.c_float, P, P, P, P, P]),
     "amdkge_train_shared_labels_fwdbwd": (C.c_int, [C.POINTER(Model), C.c_float, I32, P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P,
                                                     P, P, P, P, P, P, I32, P, P, P, P]),
@@ -211,27 +224,11 @@ SHARED_LABELS_SIGNATURES = {
                                                          P, P, P, P, P, P, I32, P, P, P, P]),
 }
 
-# include/amdkge_batch_reg.h (batch regularisers: N3 and per-occurrence Lp on the rows of a step's positives): again a table of its own
-BATCH_REG_NORMS = {"float": 0, "modulus": 1}
-BATCH_REG_SIGNATURES = {
-    "amdkge_batch_reg_fwdbwd": (C.c_int, [C.POINTER(Model), P, P, P, I64, I32, C.c_float, I32, I32, C.c_float, I32, P, P, P, P]),
-}
-
-# include/amdkge_relation_objective.h (the relation-prediction training objective: a softmax over the relation table): again a table of its own
-RELATION_OBJECTIVE_SIGNATURES = {
+ABI["amdkge_relation_objective.h"] = {   # the relation-prediction training objective: a softmax over the relation table
     "amdkge_train_relation_workspace_bytes": (I64, [C.POINTER(Model), I64]),
     "amdkge_train_relation_fwdbwd": (C.c_int, [C.POINTER(Model), C.POINTER(Loss), C.c_float, P, P, P, I64, P, P, P, P, P, P, P, P, P, P, P]),
 }
 
-# include/amdkge_types.h (type-constrained negatives and evaluation: per-relation domain / range sets): again a table of its own
-TYPES_SIGNATURES = {
-    "amdkge_relation_sets_build": (C.c_int, [P, I64, I32, I64, I64, P, P, P, P, P, P]),
-    "amdkge_relation_sets_ranges": (C.c_int, [P, P, I64, P, I64, I64, I64, I64, P, P, P]),
-    "amdkge_sample_negatives_typed": (C.c_int, [P, I64, I32, I64, I64, U64, U64, I64, I64, I32, P, P, I64, P, P, P, P, P, P, I32, P, P,
-                                                P, P, P, P, P, P, P]),
-}
-
-SIGNATURE_TABLES = (SIGNATURES, EXT_SIGNATURES, NEG_SIGNATURES, SHARED_SIGNATURES, SHARED_MASK_SIGNATURES, SHARED_DIST_SIGNATURES, SHARED_LABELS_SIGNATURES, BATCH_REG_SIGNATURES, RELATION_OBJECTIVE_SIGNATURES, TYPES_SIGNATURES)
 _lib = None
 
 
@@ -248,7 +245,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in [entry for table in SIGNATURE_TABLES for entry in table.items()]:
+    for name, (res, args) in [entry for table in ABI.values() for entry in table.items()]:
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -8,7 +8,7 @@ the training id map's.  The index is built once per evaluate() call; a test trip
 [lo, hi) range into one shared id array, so no per-batch host work remains."""
 import numpy as np
 
-
+from .. import _ffi
 
 # The three key forms of the CSR index -- the same definition as filter_group_key (kge_filter.hip): the GROUP a triple belongs
 # to and the triple column listed under it.  The packed sort key is group * divisor + value, the divisor being the value's range.
@@ -115,7 +115,7 @@ class _CsrIndex:
         if form == "pair":
             lo, hi = engine.pair_filter_ranges(keys, start, triples_dev, self.n_ents)
         else:
-            lo, hi = engine.filter_ranges(keys, start, triples_dev, 1 if form == "s" else 2, self.n_ents, self.n_rels)
+            lo, hi = engine.filter_ranges(keys, start, triples_dev, _ffi.SIDE_S if form == "s" else _ffi.SIDE_O, self.n_ents, self.n_rels)
         return lo, hi, ids
 
 

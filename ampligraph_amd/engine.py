@@ -206,13 +206,14 @@ class KgeEngine:
         (bitwise reproducible tables: sorted tile accumulation, staged relation gradient; excludes pos_atomic)."""
         B = int(triples.shape[0])
         hot = getattr(self, "_hot_ids", None) is not None and not pos_atomic and not deterministic
-        flags = (1 if pos_atomic else 0) | (2 if deterministic else 0) | (4 if hot else 0) | (16 if deterministic and det_wide else 0)
+        flags = ((_ffi.TILED_POS_ATOMIC if pos_atomic else 0) | (_ffi.TILED_DETERMINISTIC if deterministic else 0) | (_ffi.TILED_HOT_ROWS if hot else 0)
+                 | (_ffi.TILED_DET_WIDE_SORT if deterministic and det_wide else 0))
         if given is not None:
             if pos_atomic or deterministic or int(given.numel()) != B * (1 + int(eta)) or given.dtype != torch.float32:
                 raise ValueError("given: one float32 buffer of B (1 + eta) coefficients; excludes pos_atomic / deterministic")
-            flags = 8
+            flags = _ffi.TILED_GIVEN_COEFFS
             pos_scores, neg_scores = given, given.view(-1)[B:]
-        if getattr(self, "_twork_flags", flags) & 2 != flags & 2:
+        if getattr(self, "_twork_flags", flags) & _ffi.TILED_DETERMINISTIC != flags & _ffi.TILED_DETERMINISTIC:
             self._twork = None   # the two modes lay out the bookkeeping differently: a workspace serves one of them
         self._twork_flags = flags
         self._last_tiled = (B, int(eta), flags)
@@ -284,7 +285,7 @@ class KgeEngine:
         """Sticky status of the owner-computes steps since the last query: 1 = a DETERMINISTIC step fell back to unsorted
         accumulation in some tile.  Only a deterministic step can set it, so only then is the stream synchronised to read it (the
         row-direct pass of long rows handles an overflowing LDS list by rescanning the spill: complete sums, no status)."""
-        if self._twork is None or not hasattr(self, "_last_tiled") or not (self._last_tiled[2] & 2):
+        if self._twork is None or not hasattr(self, "_last_tiled") or not (self._last_tiled[2] & _ffi.TILED_DETERMINISTIC):
             return 0
         st = C.c_int32(0)
         B, eta, flags = self._last_tiled
@@ -653,7 +654,7 @@ class KgeEngine:
         if need < 0:
             raise ValueError(name + ": bad sizes")
         work = self._buf("filter_build_work", (need,), torch.uint8)
-        form = () if side is None else (1 if side == "s" else 2,)
+        form = () if side is None else (_ffi.SIDE_S if side == "s" else _ffi.SIDE_O,)
         check(getattr(self.lib, "amdkge_" + name)(_ptr(triples), m, *form, int(n_ents), int(n_rels), _ptr(keys), _ptr(start), _ptr(ids),
                                                   _ptr(counts), _ptr(work), _stream()))
         ng, nu = (int(c) for c in counts.tolist())

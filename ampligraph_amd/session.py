@@ -42,7 +42,7 @@ def _config(scoring_type, k, n_ents, n_rels, eta, loss, optimizer, regularizer, 
     if rl1 == 0.0 and rl2 != 0.0:
         rp1, rl1, rl2 = rp2, rl2, 0.0
     cfg.rel_reg_lambda, cfg.opt.rel_reg_p, cfg.opt.rel_reg2_p, cfg.opt.rel_reg2_lambda = rl1, rp1, rp2, rl2
-    cfg.eta, cfg.seed, cfg.device, cfg.flags = int(eta), int(seed), int(device), (1 if pos_atomic else 0) | (2 if deterministic else 0)
+    cfg.eta, cfg.seed, cfg.device, cfg.flags = int(eta), int(seed), int(device), (_ffi.TILED_POS_ATOMIC if pos_atomic else 0) | (_ffi.TILED_DETERMINISTIC if deterministic else 0)
     return cfg
 
 
@@ -162,19 +162,19 @@ class SessionGroup:
         cfg = _config(scoring_type, k, n_ents, n_rels, eta, loss, optimizer, regularizer, rel_regularizer, seed, 0, pos_atomic,
                       focus_nonlinearity, deterministic)
         dev = _i32(list(devices))
+        rccl, threads = _ffi.GROUP_FORCE_RCCL if force_rccl else 0, _ffi.GROUP_FORCE_THREADS if force_threads else 0
         self._g = C.c_void_p()
         self.rows, self.n_ents, self.n_rels = bool(rows), int(n_ents), int(n_rels)
         self.cols = bool(cols)
         if cols:
-            check(self.lib.amdkge_session_group_create_cols(C.byref(cfg), _p(dev), int(dev.shape[0]), 1 if force_rccl else 0, C.byref(self._g)))
+            check(self.lib.amdkge_session_group_create_cols(C.byref(cfg), _p(dev), int(dev.shape[0]), rccl, C.byref(self._g)))
         elif rows:
             if max_batch is None:
                 raise ValueError("rows=True needs max_batch (the largest batch a step will be given)")
-            check(self.lib.amdkge_session_group_create_rows(C.byref(cfg), _p(dev), int(dev.shape[0]), (1 if force_rccl else 0) | (4 if global_negatives else 0) | (16 if force_threads else 0),
-                                                            int(max_batch), C.byref(self._g)))
+            check(self.lib.amdkge_session_group_create_rows(C.byref(cfg), _p(dev), int(dev.shape[0]),
+                                                            rccl | (_ffi.GROUP_GLOBAL_NEGATIVES if global_negatives else 0) | threads, int(max_batch), C.byref(self._g)))
         else:
-            check(self.lib.amdkge_session_group_create_ex(C.byref(cfg), _p(dev), int(dev.shape[0]), (1 if force_rccl else 0) | (16 if force_threads else 0),
-                                                          C.byref(self._g)))
+            check(self.lib.amdkge_session_group_create_ex(C.byref(cfg), _p(dev), int(dev.shape[0]), rccl | threads, C.byref(self._g)))
         self.size = int(self.lib.amdkge_session_group_size(self._g))
 
     def info(self):

@@ -3,7 +3,6 @@
 and exports every symbol include/amdkge.h declares (no compute without a GPU)."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,15 +11,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
+    """lib() raises unless the library exports every entry of _ffi.ABI, which tests/test_abi_host.py holds equal to the headers"""
     from ampligraph_amd import _ffi
 
-    hdr = open(os.path.join(ROOT, "include", "amdkge.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
-    assert declared, "no declarations parsed"
     lib = _ffi.lib()
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in include/amdkge.h but not exported"
-    assert declared == set(_ffi.SIGNATURES), declared ^ set(_ffi.SIGNATURES)
     assert lib.amdkge_abi_version() == 5 == _ffi.ABI_VERSION
     assert lib.amdkge_internal_k(2, 200) == 400 and lib.amdkge_internal_k(0, 50) == 50
 
@@ -240,4 +234,4 @@ def test_session_group_argument_validation_without_gpu():
     p = ctypes.cast(buf, ctypes.c_void_p)
     assert lib.amdkge_cols_partial_scores(ctypes.byref(m), p, p, p, 1, 5, 0, 100, 0, 0, 0, 1, None, p, None) == -5
     assert b"256 units per half" in lib.amdkge_last_error()
-    assert "AMDKGE_ERCCL (-3)" in open(os.path.join(ROOT, "include", "amdkge.h")).read()
+    assert _ffi.ERCCL == -3   # the header's value: tests/test_abi_host.py

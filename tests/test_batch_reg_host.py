@@ -320,13 +320,9 @@ def test_symbol_is_exported_and_bound(built):
 
     from ampligraph_amd import _ffi
 
-    assert hasattr(C.CDLL(built), "amdkge_batch_reg_fwdbwd")
-    assert set(_ffi.BATCH_REG_SIGNATURES) == {"amdkge_batch_reg_fwdbwd"} and _ffi.ABI_VERSION == 5
-    res, args = _ffi.BATCH_REG_SIGNATURES["amdkge_batch_reg_fwdbwd"]
+    # export, types against the header, binding and the header's values of BATCH_REG_NORMS: tests/test_abi_host.py
+    res, args = _ffi.ABI["amdkge_batch_reg.h"]["amdkge_batch_reg_fwdbwd"]
     assert res is C.c_int and len(args) == 15 and args[6] is C.c_float and args[9] is C.c_float
-    assert _ffi.lib().amdkge_batch_reg_fwdbwd.argtypes == args
-    hdr = open(os.path.join(ROOT, "include", "amdkge_batch_reg.h")).read()
-    assert "AMDKGE_BATCH_REG_FLOAT 0" in hdr and "AMDKGE_BATCH_REG_MODULUS 1" in hdr and _ffi.BATCH_REG_NORMS == {"float": 0, "modulus": 1}
 
 
 def test_kernel_has_no_scratch_and_no_spills(built):

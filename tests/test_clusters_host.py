@@ -16,7 +16,7 @@ def test_library_exports_the_dbscan_symbols_and_validates_without_gpu():
     from ampligraph_amd import _ffi
 
     lib = _ffi.lib()
-    assert {"amdkge_join_dbscan_workspace_bytes", "amdkge_join_dbscan"} <= set(_ffi.SIGNATURES)
+    assert {"amdkge_join_dbscan_workspace_bytes", "amdkge_join_dbscan"} <= set(_ffi.ABI["amdkge.h"])
     assert hasattr(lib, "amdkge_join_dbscan") and hasattr(lib, "amdkge_join_dbscan_workspace_bytes")
     buf = C.c_void_p(16)   # never dereferenced: every call below returns before touching the device
     ok = (buf, 5, 4, 1.0, 2, buf, buf, buf, buf, None)

@@ -20,7 +20,7 @@ def test_topk_rows_excluding_argument_validation_without_gpu():
     from ampligraph_amd import _ffi
 
     lib = _ffi.lib()
-    assert "amdkge_topk_rows_excluding" in _ffi.SIGNATURES and lib.amdkge_abi_version() == 5
+    assert "amdkge_topk_rows_excluding" in _ffi.ABI["amdkge.h"] and lib.amdkge_abi_version() == 5
     assert _call(lib, n=0) == 0                                           # an empty batch is a no-op
     assert _call(lib, n=0, vals=0, out_idx=0, out_val=0) == 0
     assert _call(lib, k=0) == -1 and b"topk_rows_excluding" in lib.amdkge_last_error()

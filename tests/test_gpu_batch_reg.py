@@ -12,12 +12,12 @@ import pytest
 import torch
 
 import batch_reg_ref as BR
+from ampligraph_amd._ffi import EINVAL, EUNSUPPORTED
 from test_gpu_guard_bands import stored, unstored
 from test_gpu_kernels import dev
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, EUNSUPPORTED = -1, -5
 PAD_MARK = 7.0   # what the padding floats of a gradient table hold on entry
 
 

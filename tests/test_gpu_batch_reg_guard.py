@@ -3,18 +3,15 @@
 tables and gradient tables 16 bytes behind a 256-byte boundary (the 16-byte path stays legal) and 4 bytes behind one (the call
 falls back to one float per lane).  The batch touches the first and the last row of both tables."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import batch_reg_ref as BR
+from abi_decl import declared_names
 from test_gpu_guard_bands import F32, F64, P, Tables, edge_triples, run_case
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def case_batch_reg(ar, model, k, pad, offset, p, B=37, N=130, R=4):
@@ -63,6 +60,5 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 
 def test_every_extension_header_entry_has_a_case():
-    hdr = open(os.path.join(ROOT, "include", "amdkge_batch_reg.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_batch_reg.h")
     assert declared and declared == set(BATCH_REG_CASES) and all(BATCH_REG_CASES.values())

@@ -2,18 +2,16 @@
 numpy restatement of the draw (tests/negatives_ref.py) bit for bit, the trivial configuration against amdkge_sample_corruptions,
 the accounting identity on a dense planted graph, the Bernoulli thresholds, compile(negatives=...) end to end, guard bands."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import negatives_ref as NR
+from abi_decl import declared_names
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, STEP = 12345678901234, (1 << 33) + 5
 
 
@@ -409,6 +407,5 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 
 def test_every_extension_header_entry_has_a_case():
-    hdr = open(os.path.join(ROOT, "include", "amdkge_negatives.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_negatives.h")
     assert declared and declared == set(NEG_CASES) and all(NEG_CASES.values())

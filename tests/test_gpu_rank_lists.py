@@ -2,20 +2,18 @@
 exact.  The yardstick is the declared-order oracle (oracle/rank_ordered.py) called one triple at a time with that triple's list as
 the candidate rows; dyadic tables (entries j / 8, j in -4 .. 4) make equal scores and filter hits occur by the hundred."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from abi_decl import declared_names
 from oracle import kge_oracle as O
 from oracle import rank_ordered as RO
 from test_gpu_kernels import dev, dyadic_tables, make_engine, rand_triples
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_ENT, N_REL, NQ = 3000, 11, 67          # 67 queries: no multiple of any queries-per-workgroup choice
 LENS = (0, 1, 63, 64, 65, 500, 9000)     # 9000 > N_ENT: drawn with repeats, and long enough for several workgroups per query
 SIDES = (("s", 1), ("o", 2))
@@ -349,8 +347,7 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 def test_every_extension_header_entry_has_a_case_or_a_reason():
     """include/amdkge_lists.h's twin of tests/test_guard_bands_host.py::test_every_header_entry_has_a_case_or_a_reason"""
-    hdr = open(os.path.join(ROOT, "include", "amdkge_lists.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_lists.h")
     assert declared and declared == set(LIST_CASES) | set(LIST_EXEMPT), declared ^ (set(LIST_CASES) | set(LIST_EXEMPT))
     assert not set(LIST_CASES) & set(LIST_EXEMPT) and all(LIST_CASES.values()) and all(LIST_EXEMPT.values())
 

@@ -3,18 +3,16 @@ include/amdkge_relation_objective.h are handed: no write outside a buffer, no re
 handed over with exactly amdkge_train_relation_workspace_bytes bytes at an unaligned offset -- as tests/test_gpu_shared_mask_guard.py
 does for the masked shared step.  The padded layout, NULL ranges and NULL optional outputs are cases of their own."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import relation_objective_ref as RR
+from abi_decl import declared_names
 from test_gpu_guard_bands import F32, F64, P, Tables, assert_grads_close, edge_triples, loss_desc, run_case
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I64 = np.int64
 
 
@@ -94,6 +92,5 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 
 def test_every_extension_header_entry_has_a_case():
-    hdr = open(os.path.join(ROOT, "include", "amdkge_relation_objective.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_relation_objective.h")
     assert declared and declared == set(RELATION_CASES) and all(RELATION_CASES.values())

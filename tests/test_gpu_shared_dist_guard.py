@@ -4,8 +4,6 @@ over with exactly amdkge_train_shared_dist_workspace_bytes bytes -- as tests/tes
 The scores (plain stores of a fixed summation order) are bitwise equal between the runs; the gradients and the loss (atomics) are
 held to the header's arithmetic restated in numpy (tests/shared_dist_ref.py), which needs no condition on the inputs."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,11 +11,11 @@ import pytest
 import shared_dist_ref as DR
 import shared_mask_ref as MR
 import shared_ref as SR
+from abi_decl import declared_names
 from test_gpu_guard_bands import F32, F64, I32, P, Tables, assert_grads_close, edge_triples, loss_desc, run_case
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I64 = np.int64
 
 
@@ -95,6 +93,5 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 
 def test_every_extension_header_entry_has_a_case():
-    hdr = open(os.path.join(ROOT, "include", "amdkge_shared_dist.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_shared_dist.h")
     assert declared and declared == set(DIST_CASES) and all(DIST_CASES.values())

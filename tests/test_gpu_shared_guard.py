@@ -2,19 +2,17 @@
 include/amdkge_shared.h are handed: no write outside a buffer, no result that depends on bytes outside one, and the size
 amdkge_train_shared_workspace_bytes returns is what the step uses -- the workspace is handed over with exactly that many bytes."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import shared_ref as SR
+from abi_decl import declared_names
 from oracle import kge_oracle as O
 from test_gpu_guard_bands import F32, F64, I32, P, Tables, assert_grads_close, edge_triples, loss_desc, run_case
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, STEP = 12345678901234, (1 << 33) + 5
 
 
@@ -99,6 +97,5 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 
 def test_every_extension_header_entry_has_a_case():
-    hdr = open(os.path.join(ROOT, "include", "amdkge_shared.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_shared.h")
     assert declared and declared == set(SHARED_CASES) and all(SHARED_CASES.values())

@@ -3,20 +3,17 @@ include/amdkge_shared_labels.h are handed: no write outside a buffer, no result 
 handed over with exactly its *_workspace_bytes bytes -- as tests/test_gpu_shared_mask_guard.py does for the masked step.  The id
 arrays are exact to the byte and the last row's range ends at their last id: the identity walk's 64-id window must stop there."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import shared_labels_ref as LR
 import shared_ref as SR
+from abi_decl import declared_names
 from test_gpu_guard_bands import F32, F64, I32, P, Tables, assert_grads_close, edge_triples, run_case
 from test_gpu_shared_mask_guard import I64, _lib, _ranges
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _weights(ar, B):
@@ -125,6 +122,5 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 
 def test_every_extension_header_entry_has_a_case():
-    hdr = open(os.path.join(ROOT, "include", "amdkge_shared_labels.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_shared_labels.h")
     assert declared and declared == set(LABEL_CASES) and all(LABEL_CASES.values())

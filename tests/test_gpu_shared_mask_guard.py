@@ -2,19 +2,17 @@
 include/amdkge_shared_mask.h are handed: no write outside a buffer, no result that depends on bytes outside one, the workspace
 handed over with exactly amdkge_train_shared_workspace_bytes bytes -- as tests/test_gpu_shared_guard.py does for the unmasked step."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import shared_mask_ref as MR
+from abi_decl import declared_names
 import shared_ref as SR
 from test_gpu_guard_bands import F32, F64, I32, P, Tables, assert_grads_close, edge_triples, loss_desc, run_case
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I64 = np.int64
 
 
@@ -122,6 +120,5 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 
 def test_every_extension_header_entry_has_a_case():
-    hdr = open(os.path.join(ROOT, "include", "amdkge_shared_mask.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_shared_mask.h")
     assert declared and declared == set(MASK_CASES) and all(MASK_CASES.values())

@@ -1,19 +1,16 @@
 """Guard bands (tests/guarded.py, the harness of tests/test_gpu_guard_bands.py) around every buffer the entry points of
 include/amdkge_types.h are handed: no write outside a buffer, no result that depends on bytes outside one.  d_stats has exactly
 the three words the typed sampler adds to; the build's outputs have exactly the capacity m."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 import negatives_ref as NR
 import types_ref as TR
+from abi_decl import declared_names
 from test_gpu_guard_bands import I32, I64, P, run_case
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, STEP = 12345678901234, (1 << 33) + 5
 
 
@@ -127,6 +124,5 @@ def test_guard_bands(gpu_lib, fn, kw):
 
 
 def test_every_extension_header_entry_has_a_case():
-    hdr = open(os.path.join(ROOT, "include", "amdkge_types.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge_types.h")
     assert declared and declared == set(TYPES_CASES) and all(TYPES_CASES.values())

@@ -1,15 +1,11 @@
 """The guard-band harness itself (tests/guarded.py) and the coverage of include/amdkge.h by the case table of
 tests/test_gpu_guard_bands.py -- no GPU needed."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
+from abi_decl import declared_names
 from guarded import BAND, FILLS, guarded, guarded_host
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # Entry points without a guard-band case, each with its reason.  Everything else the header declares must be a key of CASES.
 EXEMPT = {
@@ -122,8 +118,7 @@ def test_every_header_entry_has_a_case_or_a_reason():
     from test_gpu_guard_bands import CASES
     import test_gpu_guard_bands as G
 
-    hdr = open(os.path.join(ROOT, "include", "amdkge.h")).read()
-    declared = set(re.findall(r"\b(amdkge_[a-z0-9_]+)\s*\(", hdr))
+    declared = declared_names("amdkge.h")
     assert len(declared) > 80, "no declarations parsed"
     assert not set(CASES) & set(EXEMPT), set(CASES) & set(EXEMPT)
     assert not (set(CASES) | set(EXEMPT)) - declared, (set(CASES) | set(EXEMPT)) - declared        # no stale names

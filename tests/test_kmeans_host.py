@@ -108,7 +108,7 @@ def test_library_exports_the_kmeans_symbols_and_validates_without_gpu():
 
     lib = _ffi.lib()
     names = {"amdkge_kmeans_workspace_bytes", "amdkge_kmeans_assign", "amdkge_kmeans_lloyd"}
-    assert names <= set(_ffi.SIGNATURES) and all(hasattr(lib, s) for s in names)
+    assert names <= set(_ffi.ABI["amdkge.h"]) and all(hasattr(lib, s) for s in names)
     buf = C.c_void_p(16)   # never dereferenced: every call below returns before touching the device
 
     def assign(**kw):

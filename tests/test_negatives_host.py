@@ -1,42 +1,27 @@
-"""The training negative samplers without a GPU: the extension header's symbol table (include/amdkge_negatives.h ==
-_ffi.NEG_SIGNATURES, the two older tables untouched), the argument validation of both entry points, the numpy restatement of the
+"""The training negative samplers without a GPU: what is the extension header's own (include/amdkge_negatives.h; names
+and types: tests/test_abi_host.py), the argument validation of both entry points, the numpy restatement of the
 draw (tests/negatives_ref.py) against oracle/philox.py, the threshold formula on hand-counted relations, and NegativeSampling's /
 compile()'s validation."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_decl
 import negatives_ref as NR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DECL = r"\b(amdkge_[a-z0-9_]+)\s*\("
-EINVAL = -1
+from ampligraph_amd._ffi import EINVAL
 
 
 # ------------------------------------------------------------------------------------------------------------ header and binding table
 def test_extension_header_and_its_signature_table():
     from ampligraph_amd import _ffi
 
-    ext = set(re.findall(DECL, open(os.path.join(ROOT, "include", "amdkge_negatives.h")).read()))
-    assert ext == {"amdkge_sample_negatives", "amdkge_negatives_side_thresholds"} == set(_ffi.NEG_SIGNATURES)
-    assert not ext & set(_ffi.SIGNATURES) and not ext & set(_ffi.EXT_SIGNATURES)
-    lib = _ffi.lib()
-    for name in ext:
-        fn = getattr(lib, name)                       # exported by the built library ...
-        assert fn.argtypes == _ffi.NEG_SIGNATURES[name][1] and fn.restype == _ffi.NEG_SIGNATURES[name][0]   # ... and bound
-    assert lib.amdkge_abi_version() == 5 == _ffi.ABI_VERSION
-    hdr = open(os.path.join(ROOT, "include", "amdkge.h")).read()
+    hdr = abi_decl.text("amdkge.h")
     assert hdr.count('#include "amdkge_negatives.h"') == 1
     assert hdr.rstrip().endswith('#include "amdkge_negatives.h"\n#endif /* AMDKGE_H */')
-    assert set(re.findall(DECL, hdr)) == set(_ffi.SIGNATURES)
-    # the enum of the header and the names the engine passes
-    text = open(os.path.join(ROOT, "include", "amdkge_negatives.h")).read()
+    # the names the engine passes and the numpy restatement's
     for name, val in (("UNIFORM", "uniform"), ("BERNOULLI", "bernoulli"), ("S_ONLY", "s"), ("O_ONLY", "o")):
-        assert int(re.search(r"AMDKGE_NEG_SIDE_%s = (\d+)" % name, text).group(1)) == _ffi.NEG_SIDE_MODES[val] == getattr(NR, name)
-    assert int(re.search(r"#define AMDKGE_NEG_MAX_TRIES (\d+)", text).group(1)) == _ffi.NEG_MAX_TRIES == 32
+        assert _ffi.NEG_SIDE_MODES[val] == getattr(NR, name)
 
 
 # ------------------------------------------------------------------------------------------------------------ argument validation

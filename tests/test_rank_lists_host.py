@@ -1,15 +1,12 @@
-"""evaluate_candidates without a GPU: the list normalisation (evaluation/candidates.py), the extension header's symbol table
-(include/amdkge_lists.h == _ffi.EXT_SIGNATURES, include/amdkge.h untouched), amdkge_rank_lists' argument validation, and the
+"""evaluate_candidates without a GPU: the list normalisation (evaluation/candidates.py), what is the extension header's own
+(include/amdkge_lists.h; names and types: tests/test_abi_host.py), amdkge_rank_lists' argument validation, and the
 sharded placements' refusal."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DECL = r"\b(amdkge_[a-z0-9_]+)\s*\("
+import abi_decl
 
 
 def test_as_csr_two_forms_give_the_same_csr():
@@ -80,17 +77,8 @@ def test_as_csr_refuses_what_is_not_n_integer_lists():
 def test_extension_header_and_its_signature_table():
     from ampligraph_amd import _ffi
 
-    ext = set(re.findall(DECL, open(os.path.join(ROOT, "include", "amdkge_lists.h")).read()))
-    assert ext == {"amdkge_rank_lists", "amdkge_rank_lists_workspace_bytes"} == set(_ffi.EXT_SIGNATURES)
-    assert not ext & set(_ffi.SIGNATURES)
     lib = _ffi.lib()
-    for name in ext:
-        fn = getattr(lib, name)                       # exported by the built library ...
-        assert fn.argtypes == _ffi.EXT_SIGNATURES[name][1] and fn.restype == _ffi.EXT_SIGNATURES[name][0]   # ... and bound
-    assert lib.amdkge_abi_version() == 5 == _ffi.ABI_VERSION                       # purely additive
-    hdr = open(os.path.join(ROOT, "include", "amdkge.h")).read()
-    assert set(re.findall(DECL, hdr)) == set(_ffi.SIGNATURES)                       # the frozen header declares what it declared
-    assert hdr.count('#include "amdkge_lists.h"') == 1
+    assert abi_decl.text("amdkge.h").count('#include "amdkge_lists.h"') == 1
     m = _ffi.Model(2, 10, 50, 5, 0, 12)
     assert lib.amdkge_rank_lists_workspace_bytes(C.byref(m), 100) == lib.amdkge_rank_workspace_bytes(C.byref(m), 100) > 0
     assert lib.amdkge_rank_lists_workspace_bytes(C.byref(m), -1) == -1
@@ -109,7 +97,7 @@ def test_rank_lists_argument_validation_without_gpu():
         return lib.amdkge_rank_lists(C.byref(model), ent, rel, n_ents, tri, n, side, lo, hi, ids, max_len, flo, fhi, fids, counts, sub, scores,
                                      work, None)
 
-    EINVAL = -1
+    EINVAL = _ffi.EINVAL
     assert call(tri=None) == EINVAL and b"NULL" in lib.amdkge_last_error()
     for missing in ("ent", "rel", "lo", "hi", "ids", "counts", "work"):
         assert call(**{missing: None}) == EINVAL, missing

@@ -1,22 +1,18 @@
-"""Shared negatives for the distance models without a GPU: the extension header's symbol table (include/amdkge_shared_dist.h ==
-_ffi.SHARED_DIST_SIGNATURES, the older headers untouched), the argument validation of both entry points (returned before any device
+"""Shared negatives for the distance models without a GPU: what is the extension header's own (include/amdkge_shared_dist.h;
+names and types: tests/test_abi_host.py), the argument validation of both entry points (returned before any device
 work), SharedDistanceNegatives and compile(), the step loop's choice of call, and the numpy restatement of the header's arithmetic
 (tests/shared_dist_ref.py) against the oracle on the override rows."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import shared_dist_ref as DR
 import shared_ref as SR
+from ampligraph_amd._ffi import EINVAL, EUNSUPPORTED
 from bound_samplers import bound
 from oracle import kge_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DECL = r"\b(amdkge_[a-z0-9_]+)\s*\("
-EINVAL, EUNSUPPORTED = -1, -5
 CONTRACTION, DISTANCE = ("DistMult", "ComplEx", "HolE"), ("TransE", "RotatE")
 
 
@@ -24,25 +20,10 @@ CONTRACTION, DISTANCE = ("DistMult", "ComplEx", "HolE"), ("TransE", "RotatE")
 def test_extension_header_and_its_signature_table():
     from ampligraph_amd import _ffi
 
-    text = open(os.path.join(ROOT, "include", "amdkge_shared_dist.h")).read()
-    ext = set(re.findall(DECL, text))
-    assert ext == {"amdkge_train_shared_dist_workspace_bytes", "amdkge_train_shared_dist_fwdbwd"} == set(_ffi.SHARED_DIST_SIGNATURES)
-    assert not ext & (set(_ffi.SIGNATURES) | set(_ffi.EXT_SIGNATURES) | set(_ffi.NEG_SIGNATURES) | set(_ffi.SHARED_SIGNATURES) | set(_ffi.SHARED_MASK_SIGNATURES)
-                      | set(_ffi.TYPES_SIGNATURES))
-    lib = _ffi.lib()
-    for name in ext:
-        fn = getattr(lib, name)                       # exported by the built library ...
-        assert fn.argtypes == _ffi.SHARED_DIST_SIGNATURES[name][1] and fn.restype == _ffi.SHARED_DIST_SIGNATURES[name][0]   # ... and bound
-    assert lib.amdkge_abi_version() == 5 == _ffi.ABI_VERSION
+    dist = _ffi.ABI["amdkge_shared_dist.h"]
     # exactly the argument lists of the entry points they stand next to
-    assert _ffi.SHARED_DIST_SIGNATURES["amdkge_train_shared_dist_fwdbwd"] == _ffi.SHARED_MASK_SIGNATURES["amdkge_train_shared_masked_fwdbwd"]
-    assert _ffi.SHARED_DIST_SIGNATURES["amdkge_train_shared_dist_workspace_bytes"] == _ffi.SHARED_SIGNATURES["amdkge_train_shared_workspace_bytes"]
-    # the older headers do not know about this one
-    for older, table in (("amdkge.h", None), ("amdkge_shared.h", _ffi.SHARED_SIGNATURES), ("amdkge_shared_mask.h", _ffi.SHARED_MASK_SIGNATURES)):
-        old = open(os.path.join(ROOT, "include", older)).read()
-        assert "shared_dist" not in old
-        if table is not None:
-            assert set(re.findall(DECL, old)) == set(table)
+    assert dist["amdkge_train_shared_dist_fwdbwd"] == _ffi.ABI["amdkge_shared_mask.h"]["amdkge_train_shared_masked_fwdbwd"]
+    assert dist["amdkge_train_shared_dist_workspace_bytes"] == _ffi.ABI["amdkge_shared.h"]["amdkge_train_shared_workspace_bytes"]
 
 
 def _model(_ffi, name, k=8, N=50, R=4):

@@ -1,21 +1,18 @@
-"""Shared-negative training without a GPU: the extension header's symbol table (include/amdkge_shared.h == _ffi.SHARED_SIGNATURES, the
-older tables and include/amdkge.h untouched), the entry points' argument validation (returned before any device work), the numpy
+"""Shared-negative training without a GPU: what is the extension header's own (include/amdkge_shared.h; names and
+types: tests/test_abi_host.py), the entry points' argument validation (returned before any device work), the numpy
 restatement of the draw and of the step's definition (tests/shared_ref.py), SharedNegatives' validation and every refusal of
 compile() that needs no device."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_decl
 import shared_ref as SR
+from ampligraph_amd._ffi import EINVAL, EUNSUPPORTED
 from bound_samplers import bound
 from oracle import kge_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DECL = r"\b(amdkge_[a-z0-9_]+)\s*\("
-EINVAL, EUNSUPPORTED = -1, -5
 SEED, STEP = 12345678901234, (1 << 33) + 5
 
 
@@ -28,22 +25,9 @@ def _graph(seed, B, N, R):
 def test_extension_header_and_its_signature_table():
     from ampligraph_amd import _ffi
 
-    text = open(os.path.join(ROOT, "include", "amdkge_shared.h")).read()
-    ext = set(re.findall(DECL, text))
-    assert ext == {"amdkge_sample_shared", "amdkge_train_shared_workspace_bytes", "amdkge_train_shared_fwdbwd"} == set(_ffi.SHARED_SIGNATURES)
-    assert not ext & (set(_ffi.SIGNATURES) | set(_ffi.EXT_SIGNATURES) | set(_ffi.NEG_SIGNATURES))
-    lib = _ffi.lib()
-    for name in ext:
-        fn = getattr(lib, name)                       # exported by the built library ...
-        assert fn.argtypes == _ffi.SHARED_SIGNATURES[name][1] and fn.restype == _ffi.SHARED_SIGNATURES[name][0]   # ... and bound
-    assert lib.amdkge_abi_version() == 5 == _ffi.ABI_VERSION
-    hdr = open(os.path.join(ROOT, "include", "amdkge.h")).read()
-    assert "amdkge_shared" not in hdr and set(re.findall(DECL, hdr)) == set(_ffi.SIGNATURES)   # the frozen header is what it was
-    assert int(re.search(r"#define AMDKGE_SHARED_MAX_NEGS \(\(1 << (\d+)\) - 1\)", text).group(1)) == 24
+    text = abi_decl.text("amdkge_shared.h")
     assert _ffi.SHARED_MAX_NEGS == SR.MAX_NEGS == (1 << 24) - 1
     assert "0xF0 << 24" in text and "0xF1 << 24" in text and (SR.TAG_IDS, SR.TAG_SIDE) == (0xF0 << 24, 0xF1 << 24)
-    for name, val in (("EINVAL", EINVAL), ("EUNSUPPORTED", EUNSUPPORTED)):
-        assert int(re.search(r"#define AMDKGE_%s \((-?\d+)\)" % name, hdr).group(1)) == val
 
 
 def _model(_ffi, name, k=8, N=50, R=4):

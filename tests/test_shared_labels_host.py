@@ -230,19 +230,13 @@ def built():
 def test_symbols_are_exported_and_bound(built):
     from ampligraph_amd import _ffi
 
-    names = {"amdkge_shared_label_loss", "amdkge_train_shared_labels_fwdbwd", "amdkge_train_shared_dist_labels_fwdbwd"}
-    assert set(_ffi.SHARED_LABELS_SIGNATURES) == names and _ffi.ABI_VERSION == 5
-    raw, lib = C.CDLL(built), _ffi.lib()
-    hdr = open(os.path.join(ROOT, "include", "amdkge_shared_labels.h")).read()
-    for n in names:
-        res, args = _ffi.SHARED_LABELS_SIGNATURES[n]
-        assert hasattr(raw, n) and getattr(lib, n).argtypes == args and res is C.c_int and ("int " + n + "(") in hdr
-    assert len(_ffi.SHARED_LABELS_SIGNATURES["amdkge_shared_label_loss"][1]) == 22
+    labels = _ffi.ABI["amdkge_shared_labels.h"]   # names, types against the header and binding: tests/test_abi_host.py
+    assert len(labels["amdkge_shared_label_loss"][1]) == 22
     # the step entry points: the masked ones' arguments, the amdkge_loss* replaced by (float, int32), two weight pointers added
-    masked = _ffi.SHARED_MASK_SIGNATURES["amdkge_train_shared_masked_fwdbwd"][1]
+    masked = _ffi.ABI["amdkge_shared_mask.h"]["amdkge_train_shared_masked_fwdbwd"][1]
     want = [masked[0], C.c_float, _ffi.I32] + masked[2:-2] + [_ffi.P, _ffi.P] + masked[-2:]
-    assert _ffi.SHARED_LABELS_SIGNATURES["amdkge_train_shared_labels_fwdbwd"][1] == want
-    assert _ffi.SHARED_LABELS_SIGNATURES["amdkge_train_shared_dist_labels_fwdbwd"][1] == want
+    assert labels["amdkge_train_shared_labels_fwdbwd"][1] == want
+    assert labels["amdkge_train_shared_dist_labels_fwdbwd"][1] == want
 
 
 def test_argument_checks_return_before_touching_a_device(built):

@@ -1,46 +1,26 @@
-"""Masked shared negatives and the all-entities list without a GPU: the extension header's symbol table
-(include/amdkge_shared_mask.h == _ffi.SHARED_MASK_SIGNATURES, the older headers untouched), the argument validation of both entry
+"""Masked shared negatives and the all-entities list without a GPU: what is the extension header's own
+(include/amdkge_shared_mask.h; names and types: tests/test_abi_host.py), the argument validation of both entry
 points (returned before any device work), SharedNegatives' new arguments, the step loop's choice of call, and the numpy
 restatement of the mask (tests/shared_mask_ref.py) on a case written out by hand."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import shared_mask_ref as MR
+from ampligraph_amd._ffi import EINVAL, EUNSUPPORTED
 from bound_samplers import bound
 from oracle import kge_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DECL = r"\b(amdkge_[a-z0-9_]+)\s*\("
-EINVAL, EUNSUPPORTED = -1, -5
 
 
 # ------------------------------------------------------------------------------------------------------------ header and binding table
 def test_extension_header_and_its_signature_table():
     from ampligraph_amd import _ffi
 
-    text = open(os.path.join(ROOT, "include", "amdkge_shared_mask.h")).read()
-    ext = set(re.findall(DECL, text))
-    assert ext == {"amdkge_shared_mask_scores", "amdkge_train_shared_masked_fwdbwd"} == set(_ffi.SHARED_MASK_SIGNATURES)
-    assert not ext & (set(_ffi.SIGNATURES) | set(_ffi.EXT_SIGNATURES) | set(_ffi.NEG_SIGNATURES) | set(_ffi.SHARED_SIGNATURES) | set(_ffi.TYPES_SIGNATURES))
-    lib = _ffi.lib()
-    for name in ext:
-        fn = getattr(lib, name)                       # exported by the built library ...
-        assert fn.argtypes == _ffi.SHARED_MASK_SIGNATURES[name][1] and fn.restype == _ffi.SHARED_MASK_SIGNATURES[name][0]   # ... and bound
-    assert lib.amdkge_abi_version() == 5 == _ffi.ABI_VERSION
     # the masked step's arguments are the unmasked step's, then the six range arrays, list_mode and d_stats, then the stream
-    plain, masked = _ffi.SHARED_SIGNATURES["amdkge_train_shared_fwdbwd"][1], _ffi.SHARED_MASK_SIGNATURES["amdkge_train_shared_masked_fwdbwd"][1]
+    plain, masked = _ffi.ABI["amdkge_shared.h"]["amdkge_train_shared_fwdbwd"][1], _ffi.ABI["amdkge_shared_mask.h"]["amdkge_train_shared_masked_fwdbwd"][1]
     assert masked[:len(plain) - 1] == plain[:-1] and len(masked) == len(plain) + 8
-    for mode, val in _ffi.SHARED_LIST_MODES.items():
-        assert int(re.search(r"AMDKGE_SHARED_LIST_%s = (\d+)" % mode.upper(), text).group(1)) == val
-    assert sorted(_ffi.SHARED_LIST_MODES.values()) == [0, 1]
-    # the two older headers do not know about this one
-    for older in ("amdkge.h", "amdkge_shared.h"):
-        assert "amdkge_shared_mask" not in open(os.path.join(ROOT, "include", older)).read()
-    assert set(re.findall(DECL, open(os.path.join(ROOT, "include", "amdkge_shared.h")).read())) == set(_ffi.SHARED_SIGNATURES)
 
 
 def _model(_ffi, name, k=8, N=50, R=4):

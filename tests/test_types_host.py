@@ -1,43 +1,32 @@
-"""Type-constrained negatives and evaluation without a GPU: the extension header's symbol table (include/amdkge_types.h ==
-_ffi.TYPES_SIGNATURES, the older tables untouched), the argument validation of the three entry points, the typed sampler kernel's
+"""Type-constrained negatives and evaluation without a GPU: what is the extension header's own (include/amdkge_types.h; names and
+types: tests/test_abi_host.py), the argument validation of the three entry points, the typed sampler kernel's
 resources in the built code object, the numpy restatement's own identities (tests/types_ref.py), and the validation of
 RelationTypes / TypedNegatives / compile() / evaluate_typed()."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_decl
 import negatives_ref as NR
 import types_ref as TR
+from ampligraph_amd._ffi import EINVAL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DECL = r"\b(amdkge_[a-z0-9_]+)\s*\("
-EINVAL = -1
-NAMES = {"amdkge_relation_sets_build", "amdkge_relation_sets_ranges", "amdkge_sample_negatives_typed"}
 
 
 # ------------------------------------------------------------------------------------------------------------ header and binding table
 def test_extension_header_and_its_signature_table():
     from ampligraph_amd import _ffi
 
-    ext = set(re.findall(DECL, open(os.path.join(ROOT, "include", "amdkge_types.h")).read()))
-    assert ext == NAMES == set(_ffi.TYPES_SIGNATURES)
-    for older in (_ffi.SIGNATURES, _ffi.EXT_SIGNATURES, _ffi.NEG_SIGNATURES, _ffi.SHARED_SIGNATURES):
-        assert not ext & set(older)
-    lib = _ffi.lib()
-    for name in ext:
-        fn = getattr(lib, name)                       # exported by the built library ...
-        assert fn.argtypes == _ffi.TYPES_SIGNATURES[name][1] and fn.restype == _ffi.TYPES_SIGNATURES[name][0]   # ... and bound
-    assert lib.amdkge_abi_version() == 5 == _ffi.ABI_VERSION
-    hdr = open(os.path.join(ROOT, "include", "amdkge.h")).read()
+    types = _ffi.ABI["amdkge_types.h"]
+    hdr = abi_decl.text("amdkge.h")
     assert hdr.count('#include "amdkge_types.h"') == 1 and hdr.index('#include "amdkge_types.h"') > hdr.index("amdkge_session_group_rank(")
-    assert set(re.findall(DECL, hdr)) == set(_ffi.SIGNATURES)                       # the frozen header declares what it declared
     # the typed sampler takes amdkge_sample_negatives' arguments in their order, then six pointers, then the stream
-    plain, typed = _ffi.NEG_SIGNATURES["amdkge_sample_negatives"][1], _ffi.TYPES_SIGNATURES["amdkge_sample_negatives_typed"][1]
+    plain, typed = _ffi.ABI["amdkge_negatives.h"]["amdkge_sample_negatives"][1], types["amdkge_sample_negatives_typed"][1]
     assert typed[:len(plain) - 1] == plain[:-1] and typed[len(plain) - 1:] == [C.c_void_p] * 7
-    assert _ffi.TYPES_SIGNATURES["amdkge_relation_sets_build"] == _ffi.SIGNATURES["amdkge_filter_build"]
+    assert types["amdkge_relation_sets_build"] == _ffi.ABI["amdkge.h"]["amdkge_filter_build"]
 
 
 def test_typed_sampler_kernel_uses_no_scratch_and_no_lds():
