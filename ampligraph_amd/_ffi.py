@@ -229,6 +229,16 @@ ABI["amdkge_relation_objective.h"] = {   # the relation-prediction training obje
     "amdkge_train_relation_fwdbwd": (C.c_int, [C.POINTER(Model), C.POINTER(Loss), C.c_float, P, P, P, I64, P, P, P, P, P, P, P, P, P, P, P]),
 }
 
+# ABI_EXT: the same table for the headers under include/ext/.  There are two tables because ABI is held, name for name and header for
+# header, to the closed set of headers directly under include/ (tests/test_abi_host.py); what is added behind that set is declared one
+# directory down and listed here (tests/test_abi_ext_host.py holds it to its headers by the same rules).
+ABI_EXT = {}
+ABI_EXT["ext/amdkge_sparse.h"] = {   # sparse optimizer mode: a step's candidate rows and the sweep of a list of rows
+    "amdkge_step_rows_workspace_bytes": (I64, [I64, I64]),
+    "amdkge_step_rows": (C.c_int, [I64, P, I64, P, I64, P, I64, P, P, P]),
+    "amdkge_opt_step_rows": (C.c_int, [C.POINTER(Opt), P, P, P, P, I64, P, P, I64, P, P]),
+}
+
 _lib = None
 
 
@@ -245,7 +255,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise AmdKgeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in [entry for table in ABI.values() for entry in table.items()]:
+    for name, (res, args) in [entry for table in list(ABI.values()) + list(ABI_EXT.values()) for entry in table.items()]:
         try:
             fn = getattr(handle, name)
         except AttributeError as e:

@@ -129,42 +129,47 @@ __device__ __forceinline__ float opt_sweep(const OptArgs& a, int64_t first, int6
     return reg_acc;
 }
 
-// Touched-rows sweep: one wave per row (grid-stride over rows).  The wave first reads the gradient row and ORs "non-zero";
-// an all-zero row is left alone -- x, the slots and the regulariser are not even read.  A touched row is re-read from
-// cache and goes through the same opt_elem as the dense sweep, and its gradient row is reset.
+// One row of the touched-rows sweeps, by one wave (THE row body: opt_sweep_rows below and the listed-rows sweep of kge_opt_rows.hip
+// both walk with it).  The wave first reads the gradient row and ORs "non-zero"; an all-zero row is left alone -- x, the slots and
+// the regulariser are not even read.  A touched row is re-read from cache and goes through the same opt_elem as the dense sweep, and
+// its gradient row is reset.  r: the row, wave-uniform; nq = row_floats / 4.
+template <int KIND>
+__device__ __forceinline__ void opt_row(const OptArgs& a, int nq, int64_t r, int lane, float& reg_acc) {
+    const int64_t base = r * (int64_t)nq;
+    const float4* g4 = reinterpret_cast<const float4*>(a.g) + base;
+    bool nz = false;
+    for (int q = lane; q < nq; q += KGE_WAVE) {
+        const float4 g = g4[q];
+        nz |= (g.x != 0.f) | (g.y != 0.f) | (g.z != 0.f) | (g.w != 0.f);
+    }
+    if (!__ballot(nz)) return;
+    float4* x4 = reinterpret_cast<float4*>(a.x) + base;
+    float4* m4 = reinterpret_cast<float4*>(a.s0) + base;
+    float4* v4 = reinterpret_cast<float4*>(a.s1) + base;
+    float4* gw4 = reinterpret_cast<float4*>(a.g) + base;
+    for (int q = lane; q < nq; q += KGE_WAVE) {
+        float4 x = x4[q], g = gw4[q];
+        float4 m = make_float4(0, 0, 0, 0), v = make_float4(0, 0, 0, 0);
+        if constexpr (opt_nslots(KIND) >= 1) m = m4[q];
+        if constexpr (opt_nslots(KIND) == 2) v = v4[q];
+        opt_elem<KIND>(a, x.x, g.x, m.x, v.x, reg_acc);
+        opt_elem<KIND>(a, x.y, g.y, m.y, v.y, reg_acc);
+        opt_elem<KIND>(a, x.z, g.z, m.z, v.z, reg_acc);
+        opt_elem<KIND>(a, x.w, g.w, m.w, v.w, reg_acc);
+        x4[q] = x;
+        gw4[q] = make_float4(0, 0, 0, 0);
+        if constexpr (opt_nslots(KIND) >= 1) m4[q] = m;
+        if constexpr (opt_nslots(KIND) == 2) v4[q] = v;
+    }
+}
+
+// Touched-rows sweep over the whole table: one wave per row (grid-stride over rows), opt_row on each.
 template <int KIND>
 __device__ __forceinline__ float opt_sweep_rows(const OptArgs& a, int64_t first_row, int64_t row_stride, int lane) {
     const int nq = a.row_floats >> 2;
     const int64_t rows = a.n / a.row_floats;
     float reg_acc = 0.f;
-    for (int64_t r = first_row; r < rows; r += row_stride) {
-        const int64_t base = r * (int64_t)nq;
-        const float4* g4 = reinterpret_cast<const float4*>(a.g) + base;
-        bool nz = false;
-        for (int q = lane; q < nq; q += KGE_WAVE) {
-            const float4 g = g4[q];
-            nz |= (g.x != 0.f) | (g.y != 0.f) | (g.z != 0.f) | (g.w != 0.f);
-        }
-        if (!__ballot(nz)) continue;
-        float4* x4 = reinterpret_cast<float4*>(a.x) + base;
-        float4* m4 = reinterpret_cast<float4*>(a.s0) + base;
-        float4* v4 = reinterpret_cast<float4*>(a.s1) + base;
-        float4* gw4 = reinterpret_cast<float4*>(a.g) + base;
-        for (int q = lane; q < nq; q += KGE_WAVE) {
-            float4 x = x4[q], g = gw4[q];
-            float4 m = make_float4(0, 0, 0, 0), v = make_float4(0, 0, 0, 0);
-            if constexpr (opt_nslots(KIND) >= 1) m = m4[q];
-            if constexpr (opt_nslots(KIND) == 2) v = v4[q];
-            opt_elem<KIND>(a, x.x, g.x, m.x, v.x, reg_acc);
-            opt_elem<KIND>(a, x.y, g.y, m.y, v.y, reg_acc);
-            opt_elem<KIND>(a, x.z, g.z, m.z, v.z, reg_acc);
-            opt_elem<KIND>(a, x.w, g.w, m.w, v.w, reg_acc);
-            x4[q] = x;
-            gw4[q] = make_float4(0, 0, 0, 0);
-            if constexpr (opt_nslots(KIND) >= 1) m4[q] = m;
-            if constexpr (opt_nslots(KIND) == 2) v4[q] = v;
-        }
-    }
+    for (int64_t r = first_row; r < rows; r += row_stride) opt_row<KIND>(a, nq, r, lane, reg_acc);
     return reg_acc;
 }
 

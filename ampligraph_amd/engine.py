@@ -319,6 +319,42 @@ class KgeEngine:
                                            n_el, reg_ptr, _stream()))
         opt_desc.reg_p = p0
 
+    def step_rows(self, triples, ids):
+        """amdkge_step_rows (include/ext/amdkge_sparse.h): the candidate rows of a step -- the ascending unique union of the s and o
+        of the int32 device triples [B, 3] and the int32 device ids (any shape, contiguous; None: no list) -> (rows int32 [cap],
+        n_rows int64 [1]), cap = min(2 B + ids.numel(), n_ents) being what the count can reach.  The count stays on the device.
+        Both live in the engine's buffer cache (and so does the workspace): the next call overwrites them."""
+        B, n_ids = int(triples.shape[0]), 0 if ids is None else int(ids.numel())
+        if ids is not None and not ids.is_contiguous():
+            raise ValueError("step_rows: the id tensor must be contiguous")
+        cap = min(2 * B + n_ids, self.n_ents)
+        rows = self._buf("step_rows", (cap,), torch.int32)
+        n_rows = self._buf("step_n_rows", (1,), torch.int64)
+        need = int(self.lib.amdkge_step_rows_workspace_bytes(self.n_ents, 2 * B + n_ids))
+        if need < 0:
+            raise ValueError("step_rows: batch and list too large for one call")
+        work = self._buf("step_rows_work", (need,), torch.uint8)
+        check(self.lib.amdkge_step_rows(self.n_ents, _ptr(triples), B, _ptr(ids), n_ids, _ptr(rows), cap, _ptr(n_rows), _ptr(work), _stream()))
+        return rows, n_rows
+
+    def opt_step_rows(self, opt_desc, reg_e, reg_r, rows, n_rows, cap, reg_slots=(1, 1)):
+        """The sweep of the sparse optimizer mode: the entity table through amdkge_opt_step_rows on the listed rows (rows int32 [cap],
+        strictly ascending in [0, n_rows[0]); n_rows int64 [1] on the device), then the relation table through the row-wise lazy
+        sweep of amdkge_opt_step (the descriptor's lazy = 1 for that call, restored afterwards).  On a list that holds every entity
+        row with a non-zero gradient the result is opt_step's with lazy = 1; nothing of size n_ents * Ks is walked."""
+        opt_desc.row_floats = self.Ks
+        p0, lazy0 = int(opt_desc.reg_p), int(opt_desc.lazy)
+        _set_reg(opt_desc, reg_e, p0)
+        s0, s1 = self._slots_of("e")
+        check(self.lib.amdkge_opt_step_rows(C.byref(opt_desc), _ptr(self.ent), _ptr(self.g_ent), _ptr(s0), _ptr(s1), self.n_ents, _ptr(rows),
+                                            _ptr(n_rows), int(cap), C.c_void_p(self.loss_acc.data_ptr() + 8 * int(reg_slots[0])), _stream()))
+        _set_reg(opt_desc, reg_r, p0)
+        opt_desc.lazy = 1
+        s0, s1 = self._slots_of("r")
+        check(self.lib.amdkge_opt_step(C.byref(opt_desc), _ptr(self.rel), _ptr(self.g_rel), _ptr(s0), _ptr(s1), self.rel.numel(),
+                                       C.c_void_p(self.loss_acc.data_ptr() + 8 * int(reg_slots[1])), _stream()))
+        opt_desc.lazy, opt_desc.reg_p = lazy0, p0
+
     def _flat_segments(self, lo, hi, reg_e, reg_r):
         """[lo, hi) of the flat parameter vector -> [(a, b, regulariser)]: its entity part and its relation part (the padding
         between / behind the tables holds zero parameters and zero gradients: nothing to sweep)"""

@@ -18,7 +18,7 @@ from .. import _ffi
 from ..datasets.filters import FilterIndex, PairFilterIndex
 from ..datasets.indexer import DataIndexer
 from ..evaluation.metrics import hits_at_n_score, mr_score, mrr_score
-from ..trainer import BATCH_REG, StepLoop, fit_modes, refuse_modes
+from ..trainer import BATCH_REG, StepLoop, fit_modes, refuse_modes, refuse_sparse
 from . import loss_functions, optimizers, regularizers
 from .initializers import RowSource, initialise, stream_cost
 
@@ -99,7 +99,7 @@ class ScoringBasedEmbeddingModel:
             model._relation_prediction = RelationPrediction.get(relp)
         if regs is not None:   # carried until compile() sets its own
             model._regularizers = [regularizers.from_config(r) for r in regs]
-        if negs is not None:   # a KvsAll sampler in its dict form: carried the same way (restore_model compiles with it)
+        if negs is not None:   # a KvsAll sampler, or the sampler of optimizer_mode="sparse", in its dict form: carried the same way
             from .negatives import NegativeSampling
 
             model._negatives = NegativeSampling.get(negs)
@@ -109,14 +109,17 @@ class ScoringBasedEmbeddingModel:
         """The constructor arguments, like the reference's Keras config (:84-98) -- and, for a model whose [entity, relation]
         regularisers include a batch regulariser (regularizers.BatchLPRegularizer), the pair in its JSON form: the step it
         trains with differs in kind, not in a number; for a model compiled with a KvsAll sampler, the sampler's dict form under
-        "negatives" (its loss, BCELoss, compiles with nothing else); for a model compiled with relation_prediction=..., the term's dict
+        "negatives" (its loss, BCELoss, compiles with nothing else), and so for a model compiled with optimizer_mode="sparse" (the mode
+        compiles with nothing else); for a model compiled with relation_prediction=..., the term's dict
         form under "relation_prediction".  Every other model's config is the constructor arguments alone."""
         cfg = {"eta": self.eta, "k": self.k, "scoring_type": self.scoring_type, "seed": self.seed,
                "max_ent_size": self.max_ent_size, "max_rel_size": self.max_rel_size}
         regs = getattr(self, "_regularizers", None)
         if regs and any(regularizers.is_batch(r) for r in regs):
             cfg["entity_relation_regularizer"] = [regularizers.to_config(r) for r in regs]
-        if getattr(self._negatives, "kvsall", False):   # KvsAll: its loss (BCELoss) cannot be compiled without it
+        # KvsAll: its loss (BCELoss) cannot be compiled without it; optimizer_mode="sparse": neither can the mode without its sampler
+        if getattr(self._negatives, "kvsall", False) or (getattr(getattr(self, "optimizer", None), "sparse", False)
+                                                         and self._negatives is not None):
             cfg["negatives"] = self._negatives.get_config()
         if self._relation_prediction is not None:   # the relation-prediction term: the step it trains with has one call more
             cfg["relation_prediction"] = self._relation_prediction.get_config()
@@ -146,7 +149,10 @@ class ScoringBasedEmbeddingModel:
         0.41 instead of 0.15 ms per step; on a shared-negative step it adds 0.06 ms.
 
         Extra keywords of this engine: optimizer_mode="dense" (default, the reference's semantics) | "lazy" (touched rows
-        only; see amdkge_opt.lazy); deterministic=True: bitwise reproducible training (AMDKGE_TILED_DETERMINISTIC);
+        only; see amdkge_opt.lazy) | "sparse" (the result of "lazy" for a SharedNegatives / SharedDistanceNegatives step with finite
+        lists -- num_negs a number, or "all" over an `entities` pool; mask_known or not --, whose closing sweep visits only the step's
+        candidate rows: its positives' s and o and its list ids, include/ext/amdkge_sparse.h; refused without such a sampler;
+        save_model / restore_model carry the mode and its sampler); deterministic=True: bitwise reproducible training (AMDKGE_TILED_DETERMINISTIC);
         negatives=None (the train kernels' own draw: a fair coin for the side, a uniform entity) | NegativeSampling | a dict of its
         keywords {"filter", "side", "entities", "max_tries"} (latent_features/negatives.py: rejection of known statements, Bernoulli
         side choice, an entity pool; replicated tables only; model.negative_sampling_stats_ after fit()) | TypedNegatives | its dict
@@ -181,8 +187,9 @@ class ScoringBasedEmbeddingModel:
         (DESIGN.md section 5): the term adds 0.44 ms per step (DistMult 0.36) -- 0.40 -> 0.83 ms on SharedNegatives(256), 15.1 -> 15.6 ms
         on the all-entities step, 0.15 -> 0.79 ms on the per-corruption step, of which 0.20 are the dense-gradient step's."""
         optimizer_mode = kwargs.pop("optimizer_mode", "dense")
-        if optimizer_mode not in ("dense", "lazy"):
-            raise ValueError("optimizer_mode must be 'dense' (the reference's behaviour) or 'lazy' (touched rows only)")
+        if optimizer_mode not in ("dense", "lazy", "sparse"):
+            raise ValueError("optimizer_mode must be 'dense' (the reference's behaviour), 'lazy' (touched rows only) or 'sparse' (the lazy "
+                             "result on the candidate rows of a shared-negative step)")
         self._deterministic = bool(kwargs.pop("deterministic", False))
         self._sharding = kwargs.pop("entity_sharding", "replicated")
         self._sharded_negatives = kwargs.pop("sharded_negatives", "local")
@@ -196,6 +203,8 @@ class ScoringBasedEmbeddingModel:
         if self._negatives is not None and self._sharding != "replicated":
             raise NotImplementedError("negatives: the row- and column-sharded step loops (entity_sharding='rows' / 'columns') build "
                                       "their own corruption overrides and do not take a negative sampler; use replicated tables")
+        if optimizer_mode == "sparse":   # needs a sampler that owns its step and draws finite lists (trainer.refuse_sparse has the reasons)
+            refuse_sparse(self._negatives)
         if getattr(self._negatives, "shared", False):   # SharedNegatives: what it cannot be combined with
             self._negatives.check_model(self, optimizer_mode)
         from .relation_prediction import RelationPrediction
@@ -208,6 +217,10 @@ class ScoringBasedEmbeddingModel:
             # DEVIATION from the reference (its optimizer is dense, optimizers.py:136-168): only rows that received a
             # gradient this step are updated and regularised -- TF-Addons LazyAdam semantics (amdkge_opt.lazy)
             self.optimizer.lazy = True
+        if optimizer_mode == "sparse":
+            # the same DEVIATION with the same result (an entity row moves iff its gradient row is not all zero), at a cost that does
+            # not depend on the table: the sweep visits the rows the sampler names (include/ext/amdkge_sparse.h)
+            self.optimizer.sparse = True
         if loss is None:
             raise ValueError("compile(): a loss is required")
         self.loss = loss_functions.get(loss)

@@ -327,6 +327,11 @@ class SharedNegatives:
             cfg["mask_known"] = self.mask_known
         return cfg
 
+    @property
+    def names_rows(self):
+        """what optimizer_mode="sparse" asks (trainer.refuse_sparse): are the lists finite -- not every entity?"""
+        return self.num_negs != "all" or self.entities is not None
+
     def check_model(self, model, optimizer_mode="dense"):
         """compile()'s refusals: everything that is known before a GPU is touched."""
         if model.scoring_type not in ("DistMult", "ComplEx", "HolE"):
@@ -388,7 +393,11 @@ class BoundSharedNegatives:
     seed, rng_step), which draws -- draw(global_batch, seed, step) -> (ids int32 [n_groups, num_negs], side int32 [B]) -- and hands
     both to engine.train_shared_fwdbwd, or with distance=True (SharedDistanceNegatives) to engine.train_shared_dist_fwdbwd.
     all_list: None, or the int32 device list [num_negs] of num_negs="all": every group's row of ids is that list -- the id tensor
-    is built once (and again only for a batch with more groups than any before), a step draws the sides alone."""
+    is built once (and again only for a batch with more groups than any before), a step draws the sides alone.
+    candidate_rows(global_batch) -> (rows, n_rows): the entity rows the step just run on that batch can have touched
+    (engine.step_rows on the batch and the ids draw() kept; one copy of an all_list), what optimizer_mode="sparse" sweeps.
+    names_rows: False where the list is every entity (all_list without a pool) -- every row is a candidate then and
+    candidate_rows refuses."""
 
     shared = True   # what trainer.StepLoop.step looks for: the sampler runs the backward call itself
 
@@ -396,6 +405,12 @@ class BoundSharedNegatives:
         self.engine, self.num_negs, self.group_size = engine, int(num_negs), int(group_size)
         self.side, self.side_thr, self.pool = side, side_thr, pool
         self.distance, self.all_list, self._all_ids = bool(distance), all_list, None
+        self.names_rows, self._step_ids = all_list is None or pool is not None, None
+
+    def candidate_rows(self, global_batch):
+        if not self.names_rows:
+            raise NotImplementedError("negatives: the list is every entity: every row is a candidate")
+        return self.engine.step_rows(global_batch, self._step_ids if int(global_batch.shape[0]) > 0 else None)
 
     def step(self, global_batch, loss, seed, rng_step):
         """loss: the step's amdkge_loss descriptor"""
@@ -405,14 +420,17 @@ class BoundSharedNegatives:
 
     def draw(self, global_batch, seed, step):
         if self.all_list is None:
-            return self.engine.sample_shared(global_batch, self.group_size, self.num_negs, seed, step, side=self.side,
-                                             side_thr=self.side_thr, pool=self.pool)
+            ids, side = self.engine.sample_shared(global_batch, self.group_size, self.num_negs, seed, step, side=self.side,
+                                                  side_thr=self.side_thr, pool=self.pool)
+            self._step_ids = ids   # (kept for candidate_rows: the engine's buffer, valid until the next draw)
+            return ids, side
         B = int(global_batch.shape[0])
         n_groups = -(-B // min(self.group_size, B)) if B > 0 else 0
         if self._all_ids is None or int(self._all_ids.shape[0]) < n_groups:
             self._all_ids = self.all_list.reshape(1, -1).repeat(n_groups, 1).contiguous()
         # the side of a positive does not depend on the list's length (include/amdkge_shared.h, THE DRAW): one id per group is drawn and dropped
         _, side = self.engine.sample_shared(global_batch, self.group_size, 1, seed, step, side=self.side, side_thr=self.side_thr)
+        self._step_ids = self.all_list   # (every group's row is this list: one copy names its rows)
         return self._all_ids[:n_groups], side
 
 
@@ -471,6 +489,7 @@ class KvsAll:
 
     shared = True   # what trainer.StepLoop.step looks for
     kvsall = True   # what compile() looks for
+    names_rows = False   # the list is every entity: optimizer_mode="sparse" has nothing to leave out
     KEY = "kvsall"
 
     def __init__(self, side="uniform", weight="triple", known=True, group_size=None):

@@ -14,7 +14,7 @@ class OptimizerWrapper:
     momentum, "rmsprop_mom" for RMSprop with momentum): it also names the optimizer-state layout of engine / checkpoints."""
 
     def __init__(self, name, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, momentum=0.0, nesterov=False,
-                 rho=None, amsgrad=False, centered=False, lazy=False, **unused):
+                 rho=None, amsgrad=False, centered=False, lazy=False, sparse=False, **unused):
         name = name.lower()
         if name not in ("sgd", "adagrad", "adam", "rmsprop", "adadelta", "adamax") or name.endswith("_mom"):
             raise ValueError("Could not interpret optimizer identifier: ", name)
@@ -34,6 +34,9 @@ class OptimizerWrapper:
         # touched-rows mode: an opt-in that deviates from the reference's dense optimizer (optimizers.py:136-168), see
         # amdkge_opt.lazy in include/amdkge.h; set by compile(optimizer_mode="lazy") or OptimizerWrapper(lazy=True)
         self.lazy = bool(lazy)
+        # sparse mode: the lazy row sweep's result, computed on the candidate rows a shared-negative step names
+        # (include/ext/amdkge_sparse.h); set by compile(optimizer_mode="sparse").  Not `lazy`: the descriptor's flag stays 0
+        self.sparse = bool(sparse)
         self.num_optimized_vars = 2          # entity and relation tables (optimizers.py:112)
         self.is_partitioned_training = False
         self._engine = None                   # bound by the step loop: where the state tensors live (HBM)
@@ -105,7 +108,7 @@ class OptimizerWrapper:
     def get_config(self):
         return {"name": self.keras_name, "learning_rate": self.learning_rate, "beta_1": self.beta_1,
                 "beta_2": self.beta_2, "epsilon": self.epsilon, "momentum": self.momentum, "nesterov": self.nesterov,
-                "rho": self.rho, "lazy": self.lazy}
+                "rho": self.rho, "lazy": self.lazy, "sparse": self.sparse}
 
 
 def get(identifier, hyperparams=None):

@@ -41,6 +41,21 @@ def refuse_modes(prefix, reason, focus=False, multi=False, deterministic=False, 
     raise NotImplementedError("{}: {}; not offered with {}".format(prefix, reason, ", ".join(on)))
 
 
+# optimizer_mode="sparse" (include/ext/amdkge_sparse.h): the closing sweep visits the step's candidate rows and nothing else
+SPARSE_MODE = "optimizer_mode='sparse'"
+
+
+def refuse_sparse(negatives):
+    """Raise NotImplementedError unless `negatives` (a sampler or a bound sampler) names the rows its step can touch: a sampler that
+    owns its step (`shared`) and draws FINITE lists (`names_rows`).  Whoever can see the sampler asks: compile() and StepLoop.step."""
+    if not getattr(negatives, "shared", False):
+        raise NotImplementedError("{}: the sweep visits the rows the step's sampler names, and a step {} names no rows; per-corruption steps "
+                                  "have optimizer_mode='lazy'".format(SPARSE_MODE, "without a sampler" if negatives is None else "on override rows"))
+    if not getattr(negatives, "names_rows", False):
+        raise NotImplementedError("{}: with a list of every entity (num_negs='all' without an `entities` pool, KvsAll) every row is a candidate: "
+                                  "the dense sweep is that step's sweep".format(SPARSE_MODE))
+
+
 def fit_modes(model):
     """The modes refuse_modes can be asked about once fit() has a loop: what bind() of a sampler or of the relation term, and fit()
     itself for a batch regulariser, pass on."""
@@ -199,7 +214,8 @@ class StepLoop:
 
         Pairing check and refusals -> the optimizer's clock and the descriptors -> hook 0 -> ONE backward call (the sampler's own
         step, the owner-computes step, or train_fwdbwd) -> the dense extras (relation term, batch regulariser) -> hook 1 -> merge
-        and / or sweep -> hook 2.  Everything that can refuse a step does so before anything is touched."""
+        and / or sweep (optimizer_mode="sparse": engine.opt_step_rows on the sampler's candidate_rows) -> hook 2.  Everything that can
+        refuse a step does so before anything is touched."""
         eng, neg, relation = self.engine, self.negatives, self.relation
         bg = int(global_batch.shape[0])
         lo, hi = shard_bounds(bg, self.world, self.rank)
@@ -223,6 +239,9 @@ class StepLoop:
         if relation is not None:
             refuse_modes(*RELATION_TERM, focus is not None, self.multi, self.deterministic, getattr(self.optimizer, "lazy", False))
         owns = getattr(neg, "shared", False)   # the sampler runs the backward call itself (kge_train_shared*.hip), on the whole batch
+        sparse = getattr(self.optimizer, "sparse", False)   # the sweep visits the sampler's candidate rows (include/ext/amdkge_sparse.h)
+        if sparse:
+            refuse_sparse(neg)
         if owns:
             refuse_modes(*SHARED_STEP, focus is not None, self.multi, self.deterministic)
         # owner-computes path (kge_train_tiled.hip) whenever the shape allows it: no global atomics, no dense
@@ -273,7 +292,10 @@ class StepLoop:
             if self.multi:
                 for g in eng.grad_tensors():
                     self.dist.all_reduce(g)
-            if not (tiled and not self.multi):   # the single-GPU owner-computes call is the complete step
+            if sparse:   # (one rank, a sampler that owns its step: refused above otherwise)
+                cand, n_cand = neg.candidate_rows(rows)
+                eng.opt_step_rows(opt_ffi, lam, lam_r, cand, n_cand, int(cand.numel()))
+            elif not (tiled and not self.multi):   # the single-GPU owner-computes call is the complete step
                 eng.opt_step(opt_ffi, lam, lam_r)
         if self.kernel_hook is not None:
             self.kernel_hook(2)

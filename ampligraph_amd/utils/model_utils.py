@@ -60,6 +60,8 @@ def restore_model(model_name_path=None):
         regs = [regularizers.from_config(r) for r in (meta.get("regularizer") or [None, None])]
         # (a KvsAll sampler travels in the config: from_config has put it on the model, and BCELoss compiles only with it)
         kw = {"negatives": model._negatives} if getattr(model._negatives, "kvsall", False) else {}
+        if oc.get("sparse") and model._negatives is not None:   # optimizer_mode="sparse" ("sparse" absent: an older checkpoint) and its sampler
+            kw.update(negatives=model._negatives, optimizer_mode="sparse")
         if getattr(model, "_relation_prediction", None) is not None:   # the relation-prediction term travels the same way
             kw["relation_prediction"] = model._relation_prediction
         model.compile(optimizer=optimizers.get(name, oc), loss=loss_functions.get(meta["loss"]["name"], prm),
