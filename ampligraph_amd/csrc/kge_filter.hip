@@ -101,7 +101,8 @@ __global__ void filter_emit_kernel(const uint64_t* __restrict__ k, const uint64_
 }
 
 struct FilterPlan {
-    size_t off_a, off_b, off_tmp, tmp_bytes, total;
+    int64_t off_a, off_b, off_tmp, off_pos, total;   // the walk (the library aligns d_work up itself)
+    size_t tmp_bytes;
     int key_bits;
 };
 
@@ -114,18 +115,18 @@ static int key_bits_of(int64_t n_ents, int64_t n_rels) {
 }
 
 static int make_filter_plan(int64_t m, int64_t n_ents, int64_t n_rels, FilterPlan& p) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     p.key_bits = key_bits_of(n_ents, n_rels);
     size_t t_sort = 0, t_scan = 0;
     uint64_t* nul = nullptr;
     if (rocprim::radix_sort_keys(nullptr, t_sort, nul, nul, (size_t)m, 0u, (unsigned)p.key_bits, (hipStream_t)0) != hipSuccess) return -1;
     if (rocprim::exclusive_scan(nullptr, t_scan, nul, nul, (uint64_t)0, (size_t)m, rocprim::plus<uint64_t>(), (hipStream_t)0) != hipSuccess) return -1;
     p.tmp_bytes = t_sort > t_scan ? t_sort : t_scan;
-    size_t o = 0;
-    p.off_a = o; o += up((size_t)m * 8);     // unsorted keys, then the flags
-    p.off_b = o; o += up((size_t)m * 8);     // sorted keys
-    p.off_tmp = o; o += up(p.tmp_bytes);     // rocPRIM scratch, then (behind the sort) the scanned positions share off_a's partner
-    p.total = o + up((size_t)m * 8) + 256;   // + scanned positions
+    Layout l;
+    p.off_a = l.take(m, 8);                     // unsorted keys, then the flags
+    p.off_b = l.take(m, 8);                     // sorted keys
+    p.off_tmp = l.take((int64_t)p.tmp_bytes);   // rocPRIM scratch
+    p.off_pos = l.take(m, 8);                   // scanned positions
+    p.total = l.any_base(l.next());
     return 0;
 }
 
@@ -138,7 +139,7 @@ extern "C" int64_t amdkge_filter_build_workspace_bytes(int64_t m, int64_t n_ents
     if (m == 0) return 256;
     FilterPlan p;
     if (make_filter_plan(m, n_ents, n_rels, p)) return -1;
-    return (int64_t)p.total;
+    return p.total;
 }
 
 static int filter_error(int code, const char* who, const char* what) {
@@ -164,11 +165,11 @@ static int filter_build_run(const char* who, const int32_t* d_triples, int64_t m
     FilterPlan p;
     if (make_filter_plan(m, n_ents, n_rels, p)) return set_error(AMDKGE_EHIP, "filter_build: rocPRIM size query failed");
     const uint64_t div = filter_key_divisor(form, (uint64_t)n_ents, (uint64_t)n_rels);   // key = group * div + value
-    char* w = (char*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    char* w = aligned_base(d_work);
     uint64_t* a = (uint64_t*)(w + p.off_a);
     uint64_t* b = (uint64_t*)(w + p.off_b);
     void* tmp = w + p.off_tmp;
-    uint64_t* pos = (uint64_t*)(w + p.off_tmp + ((p.tmp_bytes + 255) & ~(size_t)255));
+    uint64_t* pos = (uint64_t*)(w + p.off_pos);
     const unsigned grid = (unsigned)((m + 255) / 256);
     hipLaunchKernelGGL(filter_keys_kernel, dim3(grid), dim3(256), 0, st, d_triples, m, form, (uint64_t)n_ents, (uint64_t)n_rels, a);
     if (int rc = check_launch("filter_keys")) return rc;

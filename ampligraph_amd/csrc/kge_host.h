@@ -12,6 +12,7 @@
 
 #include "../../include/amdkge.h"
 #include "kge_device.h"
+#include "kge_layout.h"
 #include "kge_once.h"
 
 namespace kge {

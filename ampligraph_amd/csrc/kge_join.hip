@@ -371,6 +371,12 @@ inline int64_t join_tiles(int64_t n) {
     return nt * (nt + 1) / 2;
 }
 
+// the walks; both use the caller's base as it is.  join_nearest: one 64-bit key per row, at the base; join_dbscan: cnt (later the
+// roots' ranks) | parent | border, int32 [n] each
+inline int64_t nearest_work_bytes(int64_t n) { Layout l(8); l.take(n, 8); return l.end(); }
+struct DbscanLayout { int64_t cnt, parent, border, total; };
+inline DbscanLayout dbscan_layout(int64_t n) { Layout l(4); return DbscanLayout{l.take(n, 4), l.take(n, 4), l.take(n, 4), l.end()}; }   // (a braced list is evaluated in order)
+
 }  // namespace kge
 
 using namespace kge;
@@ -383,7 +389,7 @@ extern "C" int amdkge_join_nearest(const float* d_x, int64_t n, int32_t d, float
     if (e != hipSuccess) return set_error_hip(e, "join_nearest: hipMemsetAsync");
     if (n == 0) return AMDKGE_OK;
     unsigned long long* keys = (unsigned long long*)d_work;
-    e = hipMemsetAsync(keys, 0xFF, (size_t)n * sizeof(unsigned long long), st);
+    e = hipMemsetAsync(keys, 0xFF, (size_t)nearest_work_bytes(n), st);
     if (e != hipSuccess) return set_error_hip(e, "join_nearest: hipMemsetAsync");
     const int64_t total = join_tiles(n);
     const dim3 grid((unsigned)(total < JOIN_MAX_BLOCKS ? total : JOIN_MAX_BLOCKS));
@@ -416,7 +422,7 @@ extern "C" int amdkge_join_radius(const float* d_x, int64_t n, int32_t d, double
 
 extern "C" int64_t amdkge_join_dbscan_workspace_bytes(int64_t n) {
     if (n < 0 || n > 0x7FFFFFFFll) return -1;
-    return 3 * n * (int64_t)sizeof(int32_t);   // cnt (later the roots' ranks) | parent | border
+    return dbscan_layout(n).total;
 }
 
 extern "C" int amdkge_join_dbscan(const float* d_x, int64_t n, int32_t d, double thr, int32_t min_samples, int32_t* d_labels, uint8_t* d_core,
@@ -430,9 +436,9 @@ extern "C" int amdkge_join_dbscan(const float* d_x, int64_t n, int32_t d, double
         const hipError_t e = hipMemsetAsync(d_n_clusters, 0, sizeof(int32_t), st);
         return e == hipSuccess ? AMDKGE_OK : set_error_hip(e, "join_dbscan: hipMemsetAsync");
     }
-    int32_t* cnt = (int32_t*)d_work;
-    int32_t* parent = cnt + n;
-    int32_t* border = parent + n;
+    const DbscanLayout wl = dbscan_layout(n);
+    char* w = (char*)d_work;
+    int32_t *cnt = (int32_t*)(w + wl.cnt), *parent = (int32_t*)(w + wl.parent), *border = (int32_t*)(w + wl.border);
     const hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n * sizeof(int32_t), st);
     if (e != hipSuccess) return set_error_hip(e, "join_dbscan: hipMemsetAsync");
     const int64_t total = join_tiles(n);

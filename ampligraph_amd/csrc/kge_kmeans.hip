@@ -292,24 +292,18 @@ struct KmWork {
 };
 inline bool km_layout(int64_t n, int64_t d, int64_t k, int64_t runs, KmWork& w) {
     const int64_t B = km_update_blocks(n), NB = km_assign_blocks(n);
-    int64_t kd, rk, FB, at = 0, sz;
+    int64_t kd, rk, FB;
     if (__builtin_mul_overflow(k, d, &kd) || __builtin_mul_overflow(runs, k, &rk)) return false;
     FB = (kd + 255) / 256;
-    auto take = [&](int64_t count, int64_t each, int64_t& off) {
-        off = at;
-        if (__builtin_mul_overflow(count, each, &sz) || __builtin_add_overflow(at, sz, &at)) return false;
-        at = (at + 7) / 8 * 8;
-        return at >= 0;
-    };
     int64_t rFB, rNB, rB, rBkd;
     if (__builtin_mul_overflow(runs, FB, &rFB) || __builtin_mul_overflow(runs, NB, &rNB) || __builtin_mul_overflow(runs, B, &rB) ||
         __builtin_mul_overflow(rB, kd, &rBkd))
         return false;
-    if (!take(rk, 4, w.counts_acc) || !take(runs, 4, w.changed_acc) || !take(rk, 4, w.counts) || !take(rFB, 8, w.shift_part) ||
-        !take(rNB, 8, w.inert_part) || !take(rBkd, 4, w.P))
-        return false;
-    w.bytes = at;
-    return true;
+    Layout l(8);   // (the caller's base is used as it is)
+    w.counts_acc = l.take(rk, 4); w.changed_acc = l.take(runs, 4); w.counts = l.take(rk, 4);
+    w.shift_part = l.take(rFB, 8); w.inert_part = l.take(rNB, 8);
+    w.P = l.take(rBkd, 4); w.bytes = l.next();
+    return w.bytes >= 0;
 }
 
 inline bool km_sizes_ok(int64_t n, int32_t d, int32_t k, int32_t runs) { return n >= 0 && n <= 0x7FFFFFFFll && d >= 1 && k >= 1 && runs >= 1; }

@@ -44,12 +44,12 @@ __global__ void step_emit_kernel(const uint32_t* __restrict__ k, const uint32_t*
 }
 
 struct StepRowsPlan {
-    size_t off_a, off_b, off_pos, off_tmp, tmp_bytes, total;
+    int64_t off_a, off_b, off_pos, off_tmp, total;   // the walk (the library aligns d_work up itself)
+    size_t tmp_bytes;
     unsigned key_bits;
 };
 
 static int make_step_rows_plan(int64_t n_ents, int64_t m, StepRowsPlan& p) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     p.key_bits = 1;
     while (p.key_bits < 32 && (1ull << p.key_bits) <= (uint64_t)n_ents) ++p.key_bits;   // the keys are 0 .. n_ents
     size_t t_sort = 0, t_scan = 0;
@@ -58,12 +58,12 @@ static int make_step_rows_plan(int64_t n_ents, int64_t m, StepRowsPlan& p) {
     FirstIter flags(rocprim::counting_iterator<uint32_t>(0), FirstOfRow{nul, 0});
     if (rocprim::exclusive_scan(nullptr, t_scan, flags, nul, (uint32_t)0, (size_t)m, rocprim::plus<uint32_t>(), (hipStream_t)0) != hipSuccess) return -1;
     p.tmp_bytes = t_sort > t_scan ? t_sort : t_scan;
-    size_t o = 0;
-    p.off_a = o; o += up((size_t)m * 4);     // the keys
-    p.off_b = o; o += up((size_t)m * 4);     // sorted
-    p.off_pos = o; o += up((size_t)m * 4);   // scanned flags: a first occurrence's place in the output
-    p.off_tmp = o; o += up(p.tmp_bytes);     // rocPRIM scratch
-    p.total = o + 256;                       // (d_work is aligned up to 256 bytes)
+    Layout l;
+    p.off_a = l.take(m, 4);                     // the keys
+    p.off_b = l.take(m, 4);                     // sorted
+    p.off_pos = l.take(m, 4);                   // scanned flags: a first occurrence's place in the output
+    p.off_tmp = l.take((int64_t)p.tmp_bytes);   // rocPRIM scratch
+    p.total = l.any_base(l.next());
     return 0;
 }
 
@@ -100,7 +100,7 @@ extern "C" int64_t amdkge_step_rows_workspace_bytes(int64_t n_ents, int64_t n_ke
     if (n_keys == 0) return 256;
     StepRowsPlan p;
     if (make_step_rows_plan(n_ents, n_keys, p)) return -1;
-    return (int64_t)p.total;
+    return p.total;
 }
 
 extern "C" int amdkge_step_rows(int64_t n_ents, const int32_t* d_triples, int64_t B, const int32_t* d_ids, int64_t n_ids, int32_t* d_rows,
@@ -118,7 +118,7 @@ extern "C" int amdkge_step_rows(int64_t n_ents, const int32_t* d_triples, int64_
     if (!d_work || (B > 0 && !d_triples) || (n_ids > 0 && !d_ids)) return set_error(AMDKGE_EINVAL, "step_rows: NULL triples / ids / workspace");
     StepRowsPlan p;
     if (make_step_rows_plan(n_ents, m, p)) return set_error(AMDKGE_EHIP, "step_rows: rocPRIM size query failed");
-    char* w = (char*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    char* w = aligned_base(d_work);
     uint32_t* a = (uint32_t*)(w + p.off_a);
     uint32_t* b = (uint32_t*)(w + p.off_b);
     uint32_t* pos = (uint32_t*)(w + p.off_pos);

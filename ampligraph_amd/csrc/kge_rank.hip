@@ -90,6 +90,8 @@ int run_prep(const amdkge_model* m, const float* d_ent, const float* d_rel, cons
 }
 
 static inline bool sgn_scale_positive(const ModelConst& mc) { return mc.score_sign * mc.score_scale > 0.f; }
+// admission of a d_screen buffer: behind the fixed part of its walk, a pair list worth having
+static inline bool holds_list(int64_t fixed, int64_t screen_bytes) { return fixed >= 0 && screen_bytes >= fixed + (1 << 16); }
 
 }  // namespace kge
 
@@ -117,7 +119,7 @@ extern "C" int amdkge_set_rank_rotate_fast(int fast) {
 
 extern "C" int64_t amdkge_rank_workspace_bytes(const amdkge_model* m, int64_t n) {
     if (validate_model(m) != AMDKGE_OK || n < 0) return -1;
-    return 1024 + ((n * 4 + 255) / 256) * 256 + n * query_row_floats(m) * 4 + 512 + filter_pair_cap(n) * 8;
+    return rank_layout(m, n).total;
 }
 
 static int rank_counts_impl(const amdkge_model* m, const float* d_ent, const float* d_rel, const int32_t* d_triples,
@@ -132,18 +134,18 @@ extern "C" int amdkge_rank_counts(const amdkge_model* m, const float* d_ent, con
 
 extern "C" int64_t amdkge_rank_screen_workspace_bytes(const amdkge_model* m, int64_t n, int64_t n_cand) {
     if (validate_model(m) != AMDKGE_OK || n < 0 || n_cand < 0) return -1;
-    if (mode_of(m->scoring_type, AMDKGE_SIDE_S) != MODE_DOT) {
-        // TransE / RotatE: the exact early exit (kge_rank_early.h) -- counters, counts, row flags and the list of handed-over pairs
-        // (room for ~3 % of the comparisons; a full list falls back to the plain kernel)
-        if (!g_rank_cfg.early.on) return 0;
-        int64_t pairs = n * n_cand / 32;
-        if (pairs < (1 << 18)) pairs = 1 << 18;
-        if (pairs > (1ll << 27)) pairs = 1ll << 27;
-        return (int64_t)early_fixed_bytes(n, n_cand) + pairs * 8 + 512;
-    }
-    int64_t pairs = n * n_cand / 32;   // room for ~3 % of the comparisons (typically ~0.2 % are undecided)
-    if (pairs < (1 << 20)) pairs = 1 << 20;
-    return (int64_t)screen_fixed_bytes(n, n_cand, row_floats(m)) + pairs * 8 + 512;
+    // the fixed part + a pair list with room for ~3 % of the comparisons (typically ~0.2 % are undecided; a full list falls back to the
+    // plain kernel), for a base of any alignment
+    const bool early = mode_of(m->scoring_type, AMDKGE_SIDE_S) != MODE_DOT;   // TransE / RotatE: the exact early exit (kge_rank_early.h)
+    if (early && !g_rank_cfg.early.on) return 0;
+    int64_t pairs = n * n_cand / 32;
+    const int64_t least = early ? 1 << 18 : 1 << 20;
+    if (pairs < least) pairs = least;
+    if (early && pairs > (1ll << 27)) pairs = 1ll << 27;
+    Layout l;
+    l.take(early ? early_layout(n, n_cand).pairs : screen_layout(n, n_cand, row_floats(m)).pairs);
+    l.take(pairs, sizeof(int2));
+    return l.any_base(l.end());
 }
 
 extern "C" int amdkge_rank_counts_screened(const amdkge_model* m, const float* d_ent, const float* d_rel, const int32_t* d_triples,
@@ -207,7 +209,7 @@ static int rank_counts_impl(const amdkge_model* m, const float* d_ent, const flo
     const int64_t mcand_e = ent_hi - ent_lo;
     const bool rot_m = mode == MODE_ROT_O || mode == MODE_ROT_S;
     bool use_early = !mfma && d_screen && g_rank_cfg.early.on && force == 0 && v4 && (!rot_m || rot_exact) && a.sgn_scale < 0.f && n >= 64 && mcand_e >= 256 &&
-                     g.U >= 64 && mcand_e < 0x7FFFFFFFll && n < 0x7FFFFFFFll && screen_bytes >= (int64_t)early_fixed_bytes(n, mcand_e) + (1 << 16);
+                     g.U >= 64 && mcand_e < 0x7FFFFFFFll && n < 0x7FFFFFFFll && holds_list(early_layout(n, mcand_e).pairs, screen_bytes);
     bool probe_measured = false;
     if (use_early)   // the probe: is the exit going to fire on these tables?  (host decision, see early_probe)
         if (int rc = early_probe(mode, d_ent, d_ent_ids, ent_lo, mcand_e, n, g, w, a.sgn_scale, d_screen, (size_t)screen_bytes, &use_early, &probe_measured, st)) return rc;
@@ -237,7 +239,7 @@ static int rank_counts_impl(const amdkge_model* m, const float* d_ent, const flo
         //      for bit; the exact kernel below then runs only as the fall-back of an overflowing recheck list ----
         const int64_t mcand = ent_hi - ent_lo;
         if (d_screen && force == 0 && v4 && pipe && g.eplane == 0 && g.U <= 2048 && n >= 128 && mcand >= 512 && sgn_scale_positive(mc) &&
-            screen_bytes >= (int64_t)screen_fixed_bytes(n, mcand, g.U) + (1 << 16)) {
+            holds_list(screen_layout(n, mcand, g.U).pairs, screen_bytes)) {
             if (int rc = run_screen(m, d_ent, d_ent_ids, ent_lo, mcand, n, g, w, mc, d_counts, d_screen, (size_t)screen_bytes, st)) return rc;
             a.guard = carve_screen(d_screen, (size_t)screen_bytes, n, mcand, g.U).counter + 1;
         }

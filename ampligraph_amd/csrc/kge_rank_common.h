@@ -201,8 +201,6 @@ struct FilterArgs {
 // ------------------------------------------------------------------------------------------------
 // d_work of a rank_counts / rank_filter / corruption_scores call (amdkge_rank_workspace_bytes)
 // ------------------------------------------------------------------------------------------------
-inline char* align_up(char* p, size_t a) { return (char*)(((uintptr_t)p + a - 1) & ~(uintptr_t)(a - 1)); }
-
 struct Workspace {
     float* Q;
     int* qpos;
@@ -217,17 +215,17 @@ inline int64_t filter_pair_cap(int64_t n) {   // 64 known positives per query on
     return c < (1ll << 30) ? c : (1ll << 30);
 }
 
+// the walk: query positions | query vectors | the filter pass's counter | its pair list.  The library aligns d_work up itself.
+// (a braced list is evaluated in order: the members of a walk's struct stand in the order of its regions)
+struct RankLayout { int64_t qpos, Q, flt_counter, flt_pairs, total; };
+inline RankLayout rank_layout(const amdkge_model* m, int64_t n) {
+    Layout l;
+    return RankLayout{l.take(n, sizeof(int)), l.take(n, query_row_floats(m) * (int64_t)sizeof(float)), l.take(256), l.take(filter_pair_cap(n), sizeof(int2)), l.any_base(l.end())};
+}
 inline Workspace carve(void* d_work, const amdkge_model* m, int64_t n) {
-    Workspace w;
-    char* p = align_up((char*)d_work, 256);
-    w.qpos = (int*)p;
-    p = align_up(p + n * sizeof(int), 256);
-    w.Q = (float*)p;
-    p = align_up(p + n * query_row_floats(m) * sizeof(float), 256);
-    w.flt_counter = (int*)p;
-    w.flt_pairs = (int2*)(p + 256);
-    w.flt_cap = filter_pair_cap(n);
-    return w;
+    const RankLayout r = rank_layout(m, n);
+    char* w = aligned_base(d_work);
+    return Workspace{(float*)(w + r.Q), (int*)(w + r.qpos), (int*)(w + r.flt_counter), (int2*)(w + r.flt_pairs), filter_pair_cap(n)};
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -254,37 +252,29 @@ struct ScreenBufs {
     int S;               // K slabs per row
 };
 
-static inline size_t scr_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// fixed part of the workspace (everything but the pair list), for n queries against m candidates of U units
-static inline size_t screen_fixed_bytes(int64_t n, int64_t m, int U) {
-    const size_t S = (size_t)(U + SCR_K - 1) / SCR_K;
-    const size_t nb = (size_t)(n + 31) / 32 + 4, mb = (size_t)(m + 31) / 32 + 4;   // (+ a tile of slack: loaders read whole 128-row tiles)
-    return 256 + scr_up((size_t)n * 8) + scr_up(nb * S * SCR_BLK_SLAB) + scr_up((size_t)n * 16) + scr_up((size_t)n * 8) +
-           scr_up(mb * S * SCR_BLK_SLAB) + scr_up((size_t)m * 16) + scr_up(((size_t)(m + 63) / 64 + 4) * 16);
+// the walk for n queries against m candidates of U units: the regions of ScreenBufs.  `pairs` is also the size of the fixed part
+// (everything but the pair list), `qlimbs` that of the counters and counts a call zeroes; cap: what a buffer of `usable` bytes behind
+// its aligned base leaves the list.  The library aligns d_screen up itself.
+struct ScreenLayout { int64_t counter, counts, qlimbs, qm, qt, elimbs, em, tm, pairs, cap, S; };
+static inline ScreenLayout screen_layout(int64_t n, int64_t m, int U, int64_t usable = 0) {
+    Layout l;
+    const int64_t S = (U + SCR_K - 1) / SCR_K, nb = (n + 31) / 32 + 4, mb = (m + 31) / 32 + 4;   // (+ a tile of slack: loaders read whole 128-row tiles)
+    return ScreenLayout{l.take(256), l.take(n, 8), l.take(nb, S * SCR_BLK_SLAB), l.take(n, 16), l.take(n, 8), l.take(mb, S * SCR_BLK_SLAB), l.take(m, 16),
+                        l.take((m + 63) / 64 + 4, 16), l.next(), l.rest(usable, 8), S};
 }
-
 static inline ScreenBufs carve_screen(void* d_screen, size_t bytes, int64_t n, int64_t m, int U) {
-    ScreenBufs b;
-    b.S = (U + SCR_K - 1) / SCR_K;
-    char* p = (char*)(((uintptr_t)d_screen + 255) & ~(uintptr_t)255);
-    const char* end = (char*)d_screen + bytes;
-    b.counter = (int*)p; p += 256;
-    b.counts = (int32_t*)p; p += scr_up((size_t)n * 8);
-    b.qlimbs = (int8_t*)p; p += scr_up(((size_t)(n + 31) / 32 + 4) * b.S * SCR_BLK_SLAB);
-    b.qm = (float4*)p; p += scr_up((size_t)n * 16);
-    b.qt = (float2*)p; p += scr_up((size_t)n * 8);
-    b.elimbs = (int8_t*)p; p += scr_up(((size_t)(m + 31) / 32 + 4) * b.S * SCR_BLK_SLAB);
-    b.em = (float4*)p; p += scr_up((size_t)m * 16);
-    b.tm = (float4*)p; p += scr_up(((size_t)(m + 63) / 64 + 4) * 16);
-    b.pairs = (int2*)p;
-    b.cap = end > p ? (int64_t)((end - p) / 8) : 0;
-    return b;
+    const ScreenLayout s = screen_layout(n, m, U, (int64_t)bytes - base_pad(d_screen));
+    char* w = aligned_base(d_screen);
+    return ScreenBufs{(int*)(w + s.counter), (int32_t*)(w + s.counts), (int8_t*)(w + s.qlimbs), (float4*)(w + s.qm), (float2*)(w + s.qt),
+                      (int8_t*)(w + s.elimbs), (float4*)(w + s.em), (float4*)(w + s.tm), (int2*)(w + s.pairs), s.cap, (int)s.S};
 }
 
-// fixed part of the early-exit workspace: counters | this call's counts | row flags (queries, candidates)
-static inline size_t early_fixed_bytes(int64_t n, int64_t m) {
-    return 256 + scr_up((size_t)n * 8) + scr_up((size_t)n) + scr_up((size_t)m);
+// the early exit's walk (kge_rank_early.h: carve_early): counters | this call's counts | row flags (queries, candidates) | pair list;
+// pairs and cap as above, `qbad` the size of the counters and counts
+struct EarlyLayout { int64_t counter, counts, qbad, ebad, pairs, cap; };
+static inline EarlyLayout early_layout(int64_t n, int64_t m, int64_t usable = 0) {
+    Layout l;
+    return EarlyLayout{l.take(256), l.take(n, 8), l.take(n), l.take(m), l.next(), l.rest(usable, 8)};
 }
 
 // exact recheck of listed pairs (rank_recheck_kernel, kge_rank_screen.h): the screening pass's undecided pairs, the filter pass's (query, known positive) pairs

@@ -95,15 +95,11 @@ struct EarlyBufs {
 };
 
 static inline EarlyBufs carve_early(void* d_screen, size_t bytes, int64_t n, int64_t m) {
+    const EarlyLayout l = early_layout(n, m, (int64_t)bytes - base_pad(d_screen));
+    char* w = aligned_base(d_screen);
     EarlyBufs e{};
-    char* p = (char*)(((uintptr_t)d_screen + 255) & ~(uintptr_t)255);
-    const char* end = (char*)d_screen + bytes;
-    e.b.counter = (int*)p; p += 256;
-    e.b.counts = (int32_t*)p; p += scr_up((size_t)n * 8);
-    e.qbad = (uint8_t*)p; p += scr_up((size_t)n);
-    e.ebad = (uint8_t*)p; p += scr_up((size_t)m);
-    e.b.pairs = (int2*)p;
-    e.b.cap = end > p ? (int64_t)((end - p) / 8) : 0;
+    e.b.counter = (int*)(w + l.counter); e.b.counts = (int32_t*)(w + l.counts); e.b.pairs = (int2*)(w + l.pairs); e.b.cap = l.cap;
+    e.qbad = (uint8_t*)(w + l.qbad); e.ebad = (uint8_t*)(w + l.ebad);
     return e;
 }
 

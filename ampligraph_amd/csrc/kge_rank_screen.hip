@@ -14,7 +14,7 @@ int run_screen(const amdkge_model* m, const float* d_ent, const int32_t* d_ent_i
                hipStream_t st) {
     ScreenBufs b = carve_screen(d_screen, screen_bytes, n, mcand, g.U);
     const float sgn_scale = mc.score_sign * mc.score_scale;
-    if (hipError_t e = hipMemsetAsync(b.counter, 0, 256 + scr_up((size_t)n * 8), st)) return set_error_hip(e, "hipMemsetAsync(screen counters)");
+    if (hipError_t e = hipMemsetAsync(b.counter, 0, (size_t)screen_layout(n, mcand, g.U).qlimbs, st)) return set_error_hip(e, "hipMemsetAsync(screen counters)");
     const double u = ldexp(1.0, -24), gam = u * (1.0 + 2.0 * (double)g.U * u);   // x |W q|_2 |W e|_2: the chain's rounding bound
     hipLaunchKernelGGL(rank_limbs_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, w.Q, (int64_t)g.QW, (const int32_t*)nullptr, (int64_t)0, n, g.U, b.S,
                        (float)(gam * (1.0 + 1e-6)), b.qlimbs, b.qm, (const int*)nullptr);

@@ -490,7 +490,7 @@ int run_early(int mode, const amdkge_model* m, const float* d_ent, const int32_t
     // sampled: "yes" -- the host read them before this sequence was enqueued; the recheck and merge kernels still look at them), or
     // are set to 1, 1 when no probe ran (a remembered answer, or the probe switched off)
     if (hipError_t e = hipMemsetAsync(eb.b.counter, 0, 16, st)) return set_error_hip(e, "hipMemsetAsync(early counters)");
-    if (hipError_t e = hipMemsetAsync(eb.b.counter + 8, 0, 256 - 32 + scr_up((size_t)n * 8), st)) return set_error_hip(e, "hipMemsetAsync(early counts)");
+    if (hipError_t e = hipMemsetAsync(eb.b.counter + 8, 0, (size_t)early_layout(n, mcand).qbad - 32, st)) return set_error_hip(e, "hipMemsetAsync(early counts)");
     if (!probe_measured)
         if (hipError_t e = hipMemsetD32Async((hipDeviceptr_t)(eb.b.counter + 4), 1, 2, st)) return set_error_hip(e, "hipMemsetD32Async(probe)");
     // rows that must not be decided early: the query vectors (every plane) and the candidate rows (stored width)

@@ -235,10 +235,13 @@ static int launch_relation(const RelArgs& a0, hipStream_t st) {
 
 using namespace kge;
 
+// the walk (RotatE only): the candidates' prepared rows, at the base that the library aligns up itself
+static int64_t relation_work_bytes(const amdkge_model* m, int64_t n_cand) { Layout l; l.take(n_cand, (int64_t)row_floats(m) * 4); return l.any_base(l.end()); }
+
 extern "C" int64_t amdkge_relation_workspace_bytes(const amdkge_model* m, int64_t n_cand) {
     if (validate_model(m) || n_cand < 0) return -1;
     if (m->scoring_type != AMDKGE_ROTATE) return 0;
-    return n_cand * (int64_t)row_floats(m) * 4 + 256;
+    return relation_work_bytes(m, n_cand);
 }
 
 extern "C" int amdkge_relation_scores(const amdkge_model* m, const float* d_ent, const float* d_rel, const int32_t* d_triples, int64_t n,
@@ -258,7 +261,7 @@ extern "C" int amdkge_relation_scores(const amdkge_model* m, const float* d_ent,
     a.ent = d_ent; a.rel = d_rel; a.triples = d_triples; a.rel_ids = d_rel_ids; a.rel_lo = rel_lo; a.n = n; a.m = (int)mc_;
     a.k = stored_k(m); a.K = row_floats(m); a.mc = model_const(m); a.out = d_scores; a.ld = ld;
     if (m->scoring_type == AMDKGE_ROTATE) {
-        float* w = (float*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+        float* w = (float*)aligned_base(d_work);
         const int64_t units = mc_ * a.k;
         hipLaunchKernelGGL(relation_prep_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, st, d_rel, d_rel_ids, rel_lo, a.m, a.k, a.K, a.mc, w);
         if (int rc = check_launch("relation_prep")) return rc;

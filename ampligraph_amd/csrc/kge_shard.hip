@@ -214,9 +214,13 @@ static inline uint32_t route_table_size(int64_t n_ids) {
 
 using namespace kge;
 
+// the walk: the hash table's keys | its values, H slots each.  The library aligns d_work up itself.
+struct RouteLayout { int64_t hkey, hval, total; };
+static RouteLayout route_layout(uint32_t H) { Layout l; return RouteLayout{l.take(H, 4), l.take(H, 4), l.any_base(l.end())}; }   // (a braced list is evaluated in order)
+
 extern "C" int64_t amdkge_shard_route_workspace_bytes(int64_t b, int64_t nneg) {
     if (b < 0 || nneg < 0 || 2 * (b + nneg) >= (1ll << 29)) return -1;
-    return (int64_t)route_table_size(2 * (b + nneg)) * 8 + 512;
+    return route_layout(route_table_size(2 * (b + nneg))).total;
 }
 
 extern "C" int amdkge_shard_route(int64_t n_ents, int32_t world, int32_t rank, const int32_t* d_triples, int64_t b,
@@ -236,9 +240,10 @@ extern "C" int amdkge_shard_route(int64_t n_ents, int32_t world, int32_t rank, c
     a.hi = a.rows_per * (rank + 1) < n_ents ? a.rows_per * (rank + 1) : n_ents;
     a.n_local = a.hi - a.lo; a.world = world; a.rank = rank; a.cap = cap;
     const uint32_t H = route_table_size(2 * (b + nneg));
+    const RouteLayout r = route_layout(H);
     a.hmask = H - 1;
-    char* w = (char*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
-    a.hkey = (int32_t*)w; a.hval = (int32_t*)(w + (size_t)H * 4);
+    char* w = aligned_base(d_work);
+    a.hkey = (int32_t*)(w + r.hkey); a.hval = (int32_t*)(w + r.hval);
     a.send_ids = d_send_ids; a.counts = d_counts;
     if (hipError_t e = hipMemsetAsync(a.hkey, 0, (size_t)H * 4, st)) return set_error_hip(e, "hipMemsetAsync(route table)");
     // (d_counts[world], the overflow flag, is sticky: only the caller clears it)

@@ -250,15 +250,11 @@ static bool relpred_plan(const amdkge_model* m, int64_t B, RelPlan& p) {
     p.rpc = CHUNK_SCORES / R;
     if (p.rpc < 1) p.rpc = 1;
     if (p.rpc > B) p.rpc = B;
-    int64_t off = 0;
-    p.off_sum = off; off += 256;
-    p.off_q = off; off += align256(B * K * 4);
-    p.off_dq = off; off += align256(B * K * 4);
-    p.off_pos = off; off += align256(B * 4);
-    p.off_cpos = off; off += align256(B * 4);
-    p.off_side = off; off += align256(B * 4);
-    p.off_s = off; off += align256(p.rpc * R * 4);
-    p.total = off;
+    Layout l;   // (the caller's base is used as it is)
+    p.off_sum = l.take(256);
+    p.off_q = l.take(B * K, 4); p.off_dq = l.take(B * K, 4);
+    p.off_pos = l.take(B, 4); p.off_cpos = l.take(B, 4); p.off_side = l.take(B, 4);
+    p.off_s = l.take(p.rpc * R, 4); p.total = l.next();
     return true;
 }
 

@@ -406,13 +406,10 @@ bool shared_plan(const amdkge_model* m, int64_t B, int64_t G, int64_t M, SharedP
     p.gpc = shared_chunk_groups(p.n_groups, G, M);
     int64_t rows = p.gpc * G;
     if (rows > B) rows = B;
-    int64_t off = 0;
-    p.off_q = off; off += align256(B * K * 4);
-    p.off_dq = off; off += align256(B * K * 4);
-    p.off_pos = off; off += align256(B * 4);
-    p.off_cpos = off; off += align256(B * 4);
-    p.off_s = off; off += align256(rows * M * 4);
-    p.total = off;
+    Layout l;   // (the caller's base is used as it is)
+    p.off_q = l.take(B * K, 4); p.off_dq = l.take(B * K, 4);
+    p.off_pos = l.take(B, 4); p.off_cpos = l.take(B, 4);
+    p.off_s = l.take(rows * M, 4); p.total = l.next();
     return true;
 }
 

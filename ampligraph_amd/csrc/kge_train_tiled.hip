@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void rel_phase_kernel(const float* __restrict_
 struct TiledPlan {
     int tile_rows, n_tiles, cap, ovf_cap, rb;
     int ns, sort_cap;   // deterministic mode: 5 staged rows per positive, LDS sort buffer entries (0 otherwise)
-    size_t off_cnt, off_lists, off_ovf, off_rows, off_cs, off_touch, off_loss, off_flag, off_hot_map, off_hot_buf, off_codes, total;
+    int64_t off_cnt, off_lists, off_ovf, off_rows, off_cs, off_touch, off_loss, off_flag, off_hot_map, off_hot_buf, off_codes, total;   // the walk (the library aligns d_work up itself)
     bool own_cache;     // RotatE, queued form, >= 4 corruption entries per table row and step: own rows cached in LDS
     bool codes;         // TransE with one wave per positive: the forward kernel hands the signs of d_j to the tile pass (ENTRY_EXACT)
     bool direct;        // long rows (> 128 quads per half): the row-direct tile pass (kge_train_direct.hip)
@@ -212,24 +212,23 @@ static bool make_plan(const amdkge_model* m, int64_t B, int32_t eta, TiledPlan& 
     // row-direct pass: one wave group per tile, the bucket sorted in LDS, rows through registers -- long rows only, and only
     // while a bucket (+ slack for overflow entries) is a small LDS list
     p.direct = direct_shape && p.cap <= 3000 && p.tile_rows <= 2048;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t o = 0;
-    p.off_loss = o; o += up((size_t)LOSS_PARTS * LOSS_PART_STRIDE * 8);   // first: the same place in every plan (kept zero between steps)
-    p.off_flag = o; o += 256;                                             // sticky status flag (amdkge_train_tiled_status): also plan-independent
-    p.off_hot_map = o; o += up((size_t)m->n_ents);                        // hot-row map and replicas: also independent of B / eta / mode,
-    p.off_hot_buf = o; o += up((size_t)HOT_MAX * HOT_REPL * K * 4);       // written by amdkge_train_tiled_set_hot_rows
-    p.off_touch = o; o += up((size_t)m->n_ents);                          // byte per entity row (lazy optimizer + POS_ATOMIC), kept zero between steps
+    Layout l;
+    p.off_loss = l.take((int64_t)LOSS_PARTS * LOSS_PART_STRIDE, 8);   // first: the same place in every plan (kept zero between steps)
+    p.off_flag = l.take(256);                                        // sticky status flag (amdkge_train_tiled_status): also plan-independent
+    p.off_hot_map = l.take(m->n_ents);                               // hot-row map and replicas: also independent of B / eta / mode,
+    p.off_hot_buf = l.take((int64_t)HOT_MAX * HOT_REPL * K, 4);      // written by amdkge_train_tiled_set_hot_rows
+    p.off_touch = l.take(m->n_ents);                                 // byte per entity row (lazy optimizer + POS_ATOMIC), kept zero between steps
     // Everything from here on moves with the plan (n_tiles and cap depend on B through own_cache, the bucket capacity and the
     // deterministic mode's LDS split): see plan_guard() for what keeps the counters of one plan safe from the lists of another.
-    p.off_cnt = o; o += up((size_t)(p.n_tiles + 2) * 32 * 4);   // bucket fills, overflow count, finished-tiles ticket
-    p.off_lists = o; o += up((size_t)p.n_tiles * p.cap * sizeof(StageEntry));
-    p.off_ovf = o; o += up((size_t)p.ovf_cap * sizeof(StageEntry));
-    p.off_rows = o; o += up((size_t)B * p.ns * K * 4);
-    p.off_cs = o; o += up(m->scoring_type == AMDKGE_ROTATE ? (size_t)m->n_rels * K * 4 : 0);
-    const size_t code_bytes = (size_t)B * eta * (ks / 4) * 4;
-    p.codes = !det && m->scoring_type == AMDKGE_TRANSE && ks <= 512 && eta <= 65535 && code_bytes <= ((size_t)8 << 30);   // (det: sorted path, three-row form)
-    p.off_codes = o; o += up(p.codes ? code_bytes : 0);
-    p.total = o + 256;
+    p.off_cnt = l.take((int64_t)(p.n_tiles + 2) * 32, 4);   // bucket fills, overflow count, finished-tiles ticket
+    p.off_lists = l.take((int64_t)p.n_tiles * p.cap, sizeof(StageEntry));
+    p.off_ovf = l.take(p.ovf_cap, sizeof(StageEntry));
+    p.off_rows = l.take(B * p.ns * K, 4);
+    p.off_cs = l.take(m->scoring_type == AMDKGE_ROTATE ? m->n_rels * K : 0, 4);
+    const int64_t code_bytes = B * eta * (ks / 4) * 4;
+    p.codes = !det && m->scoring_type == AMDKGE_TRANSE && ks <= 512 && eta <= 65535 && code_bytes <= ((int64_t)8 << 30);   // (det: sorted path, three-row form)
+    p.off_codes = l.take(p.codes ? code_bytes : 0);
+    p.total = l.any_base(l.next());
     return true;
 }
 
@@ -304,9 +303,9 @@ extern "C" int64_t amdkge_train_tiled_workspace_bytes(const amdkge_model* m, int
     TiledPlan p, pd;
     if (!make_plan(m, B, eta, p)) return 0;   // 0 = shape not supported by the owner-computes path
     // one buffer serves both modes: the deterministic plan (five staged rows, smaller tiles) is the larger one where it exists
-    size_t det_total = make_plan(m, B, eta, pd, true) ? pd.total : 0;
+    int64_t det_total = make_plan(m, B, eta, pd, true) ? pd.total : 0;
     if (make_plan(m, B, eta, pd, true, true) && pd.total > det_total) det_total = pd.total;   // (AMDKGE_TILED_DET_WIDE_SORT: smaller tiles, more of them)
-    return (int64_t)(p.total > det_total ? p.total : det_total);
+    return p.total > det_total ? p.total : det_total;
 }
 
 extern "C" int amdkge_train_step_tiled(const amdkge_model* m, const amdkge_loss* loss, const amdkge_opt* opt,
@@ -349,7 +348,7 @@ extern "C" int amdkge_train_step_tiled(const amdkge_model* m, const amdkge_loss*
         return set_error(AMDKGE_EINVAL, "train_step_tiled: sampling range outside the entity table");
     const int ks = stored_k(m), K = row_floats(m);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    char* w = aligned_base(d_work);
     if (int rc = plan_guard(d_work, p, w, st)) return rc;
     int* counters = (int*)(w + p.off_cnt);
     StageEntry* lists = (StageEntry*)(w + p.off_lists);
@@ -436,7 +435,7 @@ extern "C" int amdkge_train_tiled_status(const amdkge_model* m, int64_t B, int32
     *status = 0;
     TiledPlan p;
     if (!make_plan(m, B, eta, p, (flags & AMDKGE_TILED_DETERMINISTIC) != 0)) return set_error(AMDKGE_EUNSUPPORTED, "train_tiled_status: shape not supported");
-    char* w = (char*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    char* w = aligned_base(d_work);
     int* flag = (int*)(w + p.off_flag);   // the same place whatever B / flags the flagged step ran with
     hipStream_t st = (hipStream_t)stream;
     if (hipError_t e = hipMemcpyAsync(status, flag, sizeof(int), hipMemcpyDeviceToHost, st)) return set_error_hip(e, "hipMemcpyAsync(status)");
@@ -457,7 +456,7 @@ extern "C" int amdkge_train_tiled_set_hot_rows(const amdkge_model* m, void* d_wo
     if (!d_work || n_hot < 0 || n_hot > HOT_MAX || (n_hot > 0 && !d_hot_ids)) return set_error(AMDKGE_EINVAL, "set_hot_rows: bad arguments (at most 64 hot rows)");
     TiledPlan p;
     if (!make_plan(m, 1, 1, p)) return set_error(AMDKGE_EUNSUPPORTED, "set_hot_rows: shape not supported by the owner-computes path");
-    char* w = (char*)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+    char* w = aligned_base(d_work);
     hipStream_t st = (hipStream_t)stream;
     const int K = row_floats(m);
     if (hipError_t e = hipMemsetAsync(w + p.off_hot_map, 0, (size_t)m->n_ents, st)) return set_error_hip(e, "hipMemsetAsync(hot map)");

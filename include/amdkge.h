@@ -20,7 +20,7 @@
  *     16-byte kernels (owner-computes train pair, pipelined MFMA rank kernel); amdkge_padded_k(k) returns the
  *     smallest such value, amdkge_pack_rows / amdkge_unpack_rows convert to and from the dense [rows, NC*k] form
  *     the reference's get_embeddings / checkpoints use.  k_pad == 0 means dense rows (k_pad = k).
- *   - alignment: the kernels assume every device pointer on a 256-byte boundary (what hipMalloc and torch give; 16 bytes is what the float4 paths need); only the d_work of the rank / filter / corruption-score, relation-score, tiled-step, shard-route and filter-build calls and d_screen may start anywhere: the library aligns them up to 256 bytes itself (their *_workspace_bytes include that slack).
+ *   - alignment: the kernels assume every device pointer on a 256-byte boundary (what hipMalloc and torch give; 16 bytes is what the float4 paths need); only the d_work of the rank / filter / corruption-score / rank-lists, relation-score, tiled-step (with its status and hot-rows calls), shard-route, filter-build (side, pair and relation-set forms) and step-rows calls and d_screen may start anywhere: the library aligns them up to 256 bytes itself (their *_workspace_bytes include that slack).  Every other d_work is used from the pointer it is given: the shared-list train steps' wants 4-byte alignment, the relation objective's, amdkge_join_nearest's and amdkge_kmeans_lloyd's 8, amdkge_join_dbscan's 4.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  All compute entry
  *     points are asynchronous on that stream; the caller owns synchronisation.
  *   - return value: 0 = ok, negative = error class below; amdkge_last_error() gives a message
@@ -457,7 +457,7 @@ int amdkge_pair_distances(const float* d_q, int64_t n, const float* d_table, int
  * of the pair, so a row's nearest distance and the radius decisions agree bit for bit.  Each unordered pair is computed once.
  * amdkge_join_nearest: per row i the nearest OTHER row -- d_dist[i] (squared distance) and d_idx[i] (equal distances: the lower
  *   index; n == 1: +inf and -1) -- and *d_max = the largest squared distance over all pairs (0 when n < 2).  Deterministic.
- *   d_work: 8 n bytes.
+ *   d_work: 8 n bytes, 8-byte aligned.
  * amdkge_join_radius : every unordered pair i < j with d2 <= thr (the fp32 value compared with the double thr as it is) as int32
  *   (i, j) into d_pairs [cap][2], in no particular order; *d_count = the number of such pairs (int64), also when it exceeds
  *   cap (the caller then calls again with a larger buffer). */

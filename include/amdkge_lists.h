@@ -43,7 +43,7 @@ extern "C" {
  *   d_scores      : NULL, or float parallel to d_cand_ids: position p gets the un-quantised score of its (triple, entity) -- the
  *                   bits the 1-vs-all corruption-score call gives that pair --, -inf where the id is no candidate.  Positions
  *                   outside every [lo, hi) are not written.
- *   d_work        : amdkge_rank_lists_workspace_bytes(m, n) bytes (= the rank workspace of n triples)
+ *   d_work        : amdkge_rank_lists_workspace_bytes(m, n) bytes (= the rank workspace of n triples; like it, aligned up by the library)
  *
  * Errors: AMDKGE_EINVAL before any launch for a NULL pointer, a negative size, a filter given in part, a bad side;
  * AMDKGE_EUNSUPPORTED for RotatE's exact mode on rows that are not stored padded (k_pad = the padded k), as the filter pass. */

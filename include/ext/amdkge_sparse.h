@@ -44,7 +44,8 @@ int64_t amdkge_step_rows_workspace_bytes(int64_t n_ents, int64_t n_keys);
  *   d_triples : int32 [B, 3] (columns s, p, o; p is not read); may be NULL when B == 0
  *   d_ids     : int32 [n_ids]; may be NULL when n_ids == 0
  *   d_rows    : int32 [cap], entries at and beyond n are not written;  d_n_rows : int64 [1]
- *   d_work    : amdkge_step_rows_workspace_bytes(n_ents, 2 * B + n_ids) bytes, contents undefined before and after
+ *   d_work    : amdkge_step_rows_workspace_bytes(n_ents, 2 * B + n_ids) bytes, contents undefined before and after; it may start
+ *               anywhere (the library aligns it up to 256 bytes itself, the size includes that slack)
  * An id outside [0, n_ents) is an argument error of the caller that cannot be seen from the host: it is skipped and never used as
  * an index.  B == 0 and n_ids == 0: n = 0.
  * Errors (before any launch): AMDKGE_EINVAL for n_ents outside [1, 2^31 - 1], B < 0, n_ids < 0, 2 * B + n_ids > 2^31 - 1,
