@@ -6,9 +6,9 @@
 //                          live units, exact zeros in the padding units; the positive's raw score comes out of the same pass
 //                          (ComplEx / HolE: in the reference's operation order, which differs from <q_i, rel[p_i]> only where an inf
 //                          makes both halves of q infinite).
-//   relpred_gemm_kernel  : v_mfma_f32_32x32x2_f32 (exact fp32), a 64 x 64 tile per workgroup, a 32 x 32 accumulator per wave, operands
-//                          staged through LDS in chunks of 32 along the contraction -- shared_gemm_kernel's tile loop without groups and
-//                          without an id gather: the list is the table itself.  Three MODES:
+//   relpred_gemm_kernel  : the product tile of kge_product_tile.h (exact fp32 MFMA, 64 x 64 per workgroup; which element a
+//                          thread stages, which a lane feeds and which result a register holds is stated there), without
+//                          groups and without an id gather: the list is the table itself.  Three MODES:
 //                            FWD  : S    = Q Rel^T     (rows x K by K x R)                      -> the score buffer [rows, R]
 //                            DQ   : dQ   = C' Rel      (rows x R by R x K)                      -> dQ [B, K]
 //                            DREL : dRel += C'^T Q     (R x rows by rows x K), C read transposed -> atomic adds into d_grad_rel
@@ -23,17 +23,13 @@
 // shared_loss_kernel of kge_train_shared.hip, through shared_loss_stage (kge_train_shared.h), the loss stage of the shared-list steps.
 // Rows, not groups, are processed in chunks of at most CHUNK_SCORES scores, so the step keeps its own chunk loop.
 #include "kge_train_shared.h"
+#include "kge_product_tile.h"
 #include "../../include/amdkge_relation_objective.h"
 
 namespace kge {
 
 enum { RP_FWD = 0, RP_DQ = 1, RP_DREL = 2 };
-constexpr int RT = 64;          // tile edge
-constexpr int RKC = 32;         // contraction chunk
-constexpr int RLD = RT + 1;     // LDS row stride: a chunk staged along the contraction lands on distinct banks
-constexpr int RP_SLICE = 512;   // DREL: batch rows per workgroup (a multiple of RKC)
-
-typedef float rp_f32x16 __attribute__((ext_vector_type(16)));
+constexpr int RP_SLICE = 512;   // DREL: batch rows per workgroup (a multiple of PKC)
 
 // ---- pair queries -------------------------------------------------------------------------------------------------------------------
 template <bool CPLX>
@@ -91,54 +87,46 @@ struct RelGemmArgs {
     int per_slice;    // tiles_m * tiles_n
 };
 
-// The score of (s_i, j, o_i) of a ComplEx / HolE positive in the reference's own operation order, one lane, serially (what
-// shared_reference_score of kge_train_shared.hip is for the entity side): only for a score that the matrix product made +-inf or NaN.
+// The score of (s_i, j, o_i) of a ComplEx / HolE positive in the reference's own operation order (cplx_reference_score): only for a
+// score that the matrix product made +-inf or NaN.
 __device__ float relpred_reference_score(const RelGemmArgs& a, int64_t i, int j) {
     const int32_t* t = a.triples + 3 * i;
-    const float* S = a.ent + (int64_t)t[0] * a.K;
-    const float* P = a.rel + (int64_t)j * a.K;
-    const float* O = a.ent + (int64_t)t[2] * a.K;
-    float acc = 0.f;
-    for (int u = 0; u < a.k; ++u) {
-        const float s0 = S[u], s1 = S[a.ks + u], p0 = P[u], p1 = P[a.ks + u], o0 = O[u], o1 = O[a.ks + u];
-        acc += s0 * (p0 * o0 + p1 * o1) + s1 * (p0 * o1 - p1 * o0);
-    }
-    return acc;
+    return cplx_reference_score(a.ent + (int64_t)t[0] * a.K, a.rel + (int64_t)j * a.K, a.ent + (int64_t)t[2] * a.K, a.ks, a.k);
 }
 
 template <int MODE>
 __global__ __launch_bounds__(256) void relpred_gemm_kernel(RelGemmArgs a) {
-    __shared__ float As[RKC][RLD];
-    __shared__ float Bs[RKC][RLD];
+    __shared__ float As[PKC][PLD];
+    __shared__ float Bs[PKC][PLD];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int tile = blockIdx.x % a.per_slice;
     const int sl0 = MODE == RP_DREL ? (int)(blockIdx.x / a.per_slice) * RP_SLICE : 0;   // first chunk row of the slice
-    const int m0 = (tile / a.tiles_n) * RT, n0 = (tile % a.tiles_n) * RT;
+    const int m0 = (tile / a.tiles_n) * PT, n0 = (tile % a.tiles_n) * PT;
     const int mdim = MODE == RP_DREL ? a.R : a.rows;
     const int ndim = MODE == RP_FWD ? a.R : a.K;
     const int kdim = MODE == RP_FWD ? a.K : (MODE == RP_DQ ? a.R : ((a.rows - sl0) < RP_SLICE ? (a.rows - sl0) : RP_SLICE));
     const float* Qc = a.Q + a.row0 * a.K;   // the chunk's queries
 
-    rp_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
-    for (int k0 = 0; k0 < kdim; k0 += RKC) {
+    for (int k0 = 0; k0 < kdim; k0 += PKC) {
         // ---- stage A[m][kk] ----
         if (MODE == RP_DREL) {   // contiguous along m: C[kk][m]
-            const int mm = tid & 63;
+            const int mm = product_x_x(tid);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int kk = (tid >> 6) + 4 * r;
+            for (int r = 0; r < PSTAGE; ++r) {
+                const int kk = product_x_kk(tid, r);
                 float v = 0.f;
                 if (m0 + mm < mdim && k0 + kk < kdim) v = a.w * a.S[(int64_t)(sl0 + k0 + kk) * a.R + (m0 + mm)];
                 As[kk][mm] = v;
             }
         } else {                 // contiguous along the contraction: Q[m][kk] / C[m][kk]
-            const int kk = tid & 31;
+            const int kk = product_k_kk(tid);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int mm = (tid >> 5) + 8 * r;
+            for (int r = 0; r < PSTAGE; ++r) {
+                const int mm = product_k_x(tid, r);
                 float v = 0.f;
                 if (m0 + mm < mdim && k0 + kk < kdim)
                     v = MODE == RP_FWD ? Qc[(int64_t)(m0 + mm) * a.K + (k0 + kk)] : a.w * a.S[(int64_t)(m0 + mm) * a.R + (k0 + kk)];
@@ -147,21 +135,21 @@ __global__ __launch_bounds__(256) void relpred_gemm_kernel(RelGemmArgs a) {
         }
         // ---- stage B[kk][n] ----
         if (MODE == RP_FWD) {    // contiguous along the contraction: Rel[n][kk]; a padding unit is staged as zero
-            const int kk = tid & 31;
+            const int kk = product_k_kk(tid);
             const bool live = k0 + kk < kdim && (k0 + kk) % a.ks < a.k;
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int nn = (tid >> 5) + 8 * r;
+            for (int r = 0; r < PSTAGE; ++r) {
+                const int nn = product_k_x(tid, r);
                 float v = 0.f;
                 if (n0 + nn < ndim && live) v = a.rel[(int64_t)(n0 + nn) * a.K + (k0 + kk)];
                 Bs[kk][nn] = v;
             }
         } else {                 // contiguous along n: Rel[kk][n] / Q[kk][n]
-            const int nn = tid & 63;
+            const int nn = product_x_x(tid);
             const bool live = n0 + nn < ndim && (n0 + nn) % a.ks < a.k;
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int kk = (tid >> 6) + 4 * r;
+            for (int r = 0; r < PSTAGE; ++r) {
+                const int kk = product_x_kk(tid, r);
                 float v = 0.f;
                 if (live && k0 + kk < kdim)
                     v = MODE == RP_DQ ? a.rel[(int64_t)(k0 + kk) * a.K + (n0 + nn)] : Qc[(int64_t)(sl0 + k0 + kk) * a.K + (n0 + nn)];
@@ -169,20 +157,19 @@ __global__ __launch_bounds__(256) void relpred_gemm_kernel(RelGemmArgs a) {
             }
         }
         __syncthreads();
-        const int wm = (wv & 1) * 32 + (lane & 31), wn = (wv >> 1) * 32 + (lane & 31), kh = lane >> 5;
+        const int wm = product_quad_row(wv) * PQ + product_in_quad(lane), wn = product_quad_col(wv) * PQ + product_in_quad(lane), kh = product_kh(lane);
 #pragma unroll
-        for (int kk = 0; kk < RKC; kk += 2)
+        for (int kk = 0; kk < PKC; kk += 2)
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + kh][wm], Bs[kk + kh][wn], acc, 0, 0, 0);
         __syncthreads();
     }
-    // ---- results: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31 of the wave's 32 x 32 ----
-    const int col = n0 + (wv >> 1) * 32 + (lane & 31);
+    const int col = product_col(n0, product_quad_col(wv), lane);
     if (col >= ndim) return;
     // the padding floats of a gradient row are never written (DQ's padding columns are exact zeros or NaN: the chain kernel skips them)
     if (MODE == RP_DREL && col % a.ks >= a.k) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = m0 + (wv & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int row = product_row(m0, product_quad_row(wv), lane, r);
         if (row >= mdim) continue;
         float v = acc[r];
         if (MODE == RP_FWD) {
@@ -285,10 +272,10 @@ static int run_relpred(const amdkge_model* m, const amdkge_loss* loss, float w, 
     SharedStep ls{};
     ls.S = S; ls.pos_raw = pos_raw; ls.cpos = cpos; ls.B = B; ls.G = 1; ls.M = R; ls.side = side; ls.st = st; ls.scale = scale; ls.loss = loss; ls.mask = mask;
     ls.loss_sum = step_sum; ls.pos_scores = d_pos_scores; ls.neg_scores = d_rel_scores;
-    const int64_t tr = (R + RT - 1) / RT, tk = (K + RT - 1) / RT;
+    const int64_t tr = (R + PT - 1) / PT, tk = (K + PT - 1) / PT;
     for (int64_t row0 = 0; row0 < B; row0 += p.rpc) {
         const int64_t rows = (B - row0) < p.rpc ? (B - row0) : p.rpc;
-        const int64_t tb = (rows + RT - 1) / RT, slices = (rows + RP_SLICE - 1) / RP_SLICE;
+        const int64_t tb = (rows + PT - 1) / PT, slices = (rows + RP_SLICE - 1) / RP_SLICE;
         const int64_t nb_fwd = tb * tr, nb_dq = tb * tk, nb_drel = tr * tk * slices;
         if (nb_fwd > 0x7FFFFFFFll || nb_dq > 0x7FFFFFFFll || nb_drel > 0x7FFFFFFFll) return set_error(AMDKGE_EUNSUPPORTED, "train_relation: too many tiles for one launch");
         a.row0 = row0; a.rows = (int)rows;

@@ -9,6 +9,7 @@
 //                       the optional shared_mask_kernel, then shared_loss_kernel.  The driver and the relation objective's row loop
 //                       both call it; the fill of a masked entry is decided here alone.
 //   the workspace plan, the mask's and the labels' arguments with their checks, and shared_model_ok / add_nz.
+// The device side of the two matrix-product units, the 64 x 64 fp32 MFMA tile, is kge_product_tile.h (it includes this header).
 #pragma once
 #include "kge_host.h"
 #include "../../include/amdkge_shared_labels.h"

@@ -5,9 +5,9 @@
 //   shared_draw_kernel  : ids [n_groups, M] and sides [B], one Philox block per value (the draw of the header).
 //   shared_query_kernel : a wave per positive.  q_i = s*p or p*o (DistMult), the a|b halves of survey row a9 (ComplEx / HolE), built
 //                         for the positive's OWN side; the positive's raw score <q_i, own_i> falls out of the same pass.
-//   shared_gemm_kernel  : v_mfma_f32_32x32x2_f32 (exact fp32), a 64 x 64 tile per workgroup, a 32 x 32 accumulator per wave, operands
-//                         staged through LDS in chunks of 32 along the contraction.  Three MODES share the tile loop and differ in
-//                         where an operand element comes from and where a result goes:
+//   shared_gemm_kernel  : the product tile of kge_product_tile.h (exact fp32 MFMA, 64 x 64 per workgroup; which element a
+//                         thread stages, which a lane feeds and which result a register holds is stated there).  Three
+//                         MODES differ in where an operand element comes from and where a result goes:
 //                           FWD : S_g  = Q_g E^T     (G x K by K x M)   E gathered by id          -> the score buffer [rows, M]
 //                           DQ  : dQ_g = C_g E       (G x M by M x K)   E gathered by id          -> dQ [B, K]
 //                           DE  : dE   = C_g^T Q_g   (M x G by G x K)   C read transposed         -> atomic row-adds into d_grad_ent
@@ -30,6 +30,7 @@
 // kge_train_shared_dist.hip alike: the checks, the plan and the chunk loop once, each family's launches in its own unit
 // (product_launch here).  The loss stage of a chunk is shared_loss_stage, also the relation objective's (kge_train_relpred.hip).
 #include "kge_train_shared.h"
+#include "kge_product_tile.h"
 #include "kge_loss.h"
 #include <string>
 
@@ -111,9 +112,6 @@ __global__ __launch_bounds__(256) void shared_query_kernel(const float* __restri
 
 // ---- the three matrix products ------------------------------------------------------------------------------------------------------
 enum { GEMM_FWD = 0, GEMM_DQ = 1, GEMM_DE = 2 };
-constexpr int GT = 64;        // tile edge
-constexpr int GKC = 32;       // contraction chunk
-constexpr int GLD = GT + 1;   // LDS row stride: a chunk staged along the contraction lands on distinct banks
 
 struct SharedGemmArgs {
     const float* ent;
@@ -133,36 +131,29 @@ struct SharedGemmArgs {
     int tiles_m, tiles_n;
 };
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// The score of ONE corruption of a ComplEx / HolE positive in the reference's own operation order (ComplEx.py:58-62, score_unit of
-// kge_device.h: what amdkge_train_fwdbwd computes on the override row), one lane, serially.  Only for a score that the matrix product
-// made +-inf: <q, e> with an inf in e is (a - b) * inf = +-inf where the reference forms a * inf - b * inf, which is NaN when a and b
-// have one sign -- a NaN loss and NaN coefficients for the whole positive, where +-inf is clipped to a finite loss.  Which of the
-// three non-finite values it is depends only on the units' terms, not on the order of their sum.
+// The score of ONE corruption of a ComplEx / HolE positive in the reference's own operation order (cplx_reference_score).  Only for a
+// score that the matrix product made +-inf: <q, e> with an inf in e is (a - b) * inf = +-inf where the reference forms
+// a * inf - b * inf, which is NaN when a and b have one sign -- a NaN loss and NaN coefficients for the whole positive, where +-inf
+// is clipped to a finite loss.  Which of the three non-finite values it is depends only on the units' terms, not on the order of
+// their sum.
 __device__ float shared_reference_score(const SharedGemmArgs& a, int64_t i, int id) {
     const int32_t* t = a.triples + 3 * i;
     const bool subj = a.side[i] != 0;
     const float* S = a.ent + (int64_t)(subj ? id : t[0]) * a.K;
     const float* P = a.rel + (int64_t)t[1] * a.K;
     const float* O = a.ent + (int64_t)(subj ? t[2] : id) * a.K;
-    float acc = 0.f;
-    for (int u = 0; u < a.k; ++u) {
-        const float s0 = S[u], s1 = S[a.ks + u], p0 = P[u], p1 = P[a.ks + u], o0 = O[u], o1 = O[a.ks + u];
-        acc += s0 * (p0 * o0 + p1 * o1) + s1 * (p0 * o1 - p1 * o0);
-    }
-    return acc;
+    return cplx_reference_score(S, P, O, a.ks, a.k);
 }
 
 template <int MODE>
 __global__ __launch_bounds__(256) void shared_gemm_kernel(SharedGemmArgs a) {
-    __shared__ float As[GKC][GLD];
-    __shared__ float Bs[GKC][GLD];
+    __shared__ float As[PKC][PLD];
+    __shared__ float Bs[PKC][PLD];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int per_group = a.tiles_m * a.tiles_n;
     const int64_t g = a.g0 + blockIdx.x / per_group;
     const int tile = blockIdx.x % per_group;
-    const int m0 = (tile / a.tiles_n) * GT, n0 = (tile % a.tiles_n) * GT;
+    const int m0 = (tile / a.tiles_n) * PT, n0 = (tile % a.tiles_n) * PT;
     const int64_t row_first = g * a.G;                                         // the group's first positive
     const int Gg = (int)((a.B - row_first) < a.G ? (a.B - row_first) : a.G);   // its positives
     const int64_t srow = row_first - a.g0 * a.G;                               // its first row in the score buffer
@@ -176,22 +167,22 @@ __global__ __launch_bounds__(256) void shared_gemm_kernel(SharedGemmArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
-    for (int k0 = 0; k0 < kdim; k0 += GKC) {
+    for (int k0 = 0; k0 < kdim; k0 += PKC) {
         // ---- stage A[m][kk] ----
         if (MODE == GEMM_DE) {   // contiguous along m: C[kk][m]
-            const int mm = tid & 63;
+            const int mm = product_x_x(tid);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int kk = (tid >> 6) + 4 * r;
+            for (int r = 0; r < PSTAGE; ++r) {
+                const int kk = product_x_kk(tid, r);
                 float v = 0.f;
                 if (m0 + mm < mdim && k0 + kk < kdim) v = a.S[(srow + k0 + kk) * a.M + (m0 + mm)];
                 As[kk][mm] = v;
             }
         } else {                 // contiguous along the contraction: Q[m][kk] / C[m][kk]
-            const int kk = tid & 31;
+            const int kk = product_k_kk(tid);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int mm = (tid >> 5) + 8 * r;
+            for (int r = 0; r < PSTAGE; ++r) {
+                const int mm = product_k_x(tid, r);
                 float v = 0.f;
                 if (m0 + mm < mdim && k0 + kk < kdim)
                     v = MODE == GEMM_FWD ? a.Q[(row_first + m0 + mm) * a.K + (k0 + kk)] : a.S[(srow + m0 + mm) * a.M + (k0 + kk)];
@@ -200,19 +191,19 @@ __global__ __launch_bounds__(256) void shared_gemm_kernel(SharedGemmArgs a) {
         }
         // ---- stage B[kk][n] ----
         if (MODE == GEMM_FWD) {  // contiguous along the contraction: E[id_n][kk]
-            const int kk = tid & 31;
+            const int kk = product_k_kk(tid);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int nn = (tid >> 5) + 8 * r;
+            for (int r = 0; r < PSTAGE; ++r) {
+                const int nn = product_k_x(tid, r);
                 float v = 0.f;
                 if (n0 + nn < ndim && k0 + kk < kdim) v = a.ent[(int64_t)gid[n0 + nn] * a.K + (k0 + kk)];
                 Bs[kk][nn] = v;
             }
         } else {                 // contiguous along n: E[id_kk][n] / Q[kk][n]
-            const int nn = tid & 63;
+            const int nn = product_x_x(tid);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int kk = (tid >> 6) + 4 * r;
+            for (int r = 0; r < PSTAGE; ++r) {
+                const int kk = product_x_kk(tid, r);
                 float v = 0.f;
                 if (n0 + nn < ndim && k0 + kk < kdim)
                     v = MODE == GEMM_DQ ? a.ent[(int64_t)gid[k0 + kk] * a.K + (n0 + nn)] : a.Q[(row_first + k0 + kk) * a.K + (n0 + nn)];
@@ -220,20 +211,19 @@ __global__ __launch_bounds__(256) void shared_gemm_kernel(SharedGemmArgs a) {
             }
         }
         __syncthreads();
-        const int wm = (wv & 1) * 32 + (lane & 31), wn = (wv >> 1) * 32 + (lane & 31), kh = lane >> 5;
+        const int wm = product_quad_row(wv) * PQ + product_in_quad(lane), wn = product_quad_col(wv) * PQ + product_in_quad(lane), kh = product_kh(lane);
 #pragma unroll
-        for (int kk = 0; kk < GKC; kk += 2)
+        for (int kk = 0; kk < PKC; kk += 2)
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + kh][wm], Bs[kk + kh][wn], acc, 0, 0, 0);
         __syncthreads();
     }
-    // ---- results: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31 of the wave's 32 x 32 ----
-    const int col = n0 + (wv >> 1) * 32 + (lane & 31);
+    const int col = product_col(n0, product_quad_col(wv), lane);
     if (col >= ndim) return;
     // A padding unit of Q is an exact zero, but a NaN coefficient times it is NaN: the padding floats of d_grad_ent stay untouched.
     if (MODE == GEMM_DE && col % a.ks >= a.k) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = m0 + (wv & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int row = product_row(m0, product_quad_row(wv), lane, r);
         if (row >= mdim) continue;
         float v = acc[r];
         if (MODE == GEMM_FWD) {
@@ -492,7 +482,6 @@ int shared_step(const SharedFamily& f, const amdkge_model* m, const amdkge_loss*
 }
 
 // ---- the product family: its kernels' launches ----------------------------------------------------------------------------------------
-static_assert(GT == SHARED_TILE, "the driver counts the tiles");
 template <bool CPLX>
 static int product_launch(const SharedStep& s, SharedStage stage, unsigned blocks, int64_t g0, int tiles_m, int tiles_n) {
     const int ks = stored_k(s.m), k = s.m->k;
@@ -511,7 +500,7 @@ static int product_launch(const SharedStep& s, SharedStage stage, unsigned block
 }
 static const SharedFamily PRODUCTS = {
     "train_shared", shared_model_ok, "TransE and RotatE score a distance, not a contraction: only DistMult, ComplEx and HolE share negatives",
-    [](const amdkge_model* m) { return (row_floats(m) + GT - 1) / GT; },
+    [](const amdkge_model* m) { return (row_floats(m) + PT - 1) / PT; },
     [](const SharedStep& s, SharedStage stage, unsigned blocks, int64_t g0, int tiles_m, int tiles_n) {
         return s.m->scoring_type != AMDKGE_DISTMULT ? product_launch<true>(s, stage, blocks, g0, tiles_m, tiles_n)   // ComplEx, and HolE on its instantiation (the 2/k scale travels in ModelConst)
                                                     : product_launch<false>(s, stage, blocks, g0, tiles_m, tiles_n);
